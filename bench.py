@@ -21,6 +21,9 @@ Protocol
   4. a second identical replay with HIP events around the stages gives per-stage device time -> `roofline`.
   5. rank 0, N=1 only: the CPU oracle (NumPy restatement of the reference, 1 thread) is timed on a bounded sample
      of the same scan stream -> `cpu_baseline`.
+A plain run does steps 1-3 and prints the headline line (value, ms_per_step, the workload); the end-state check of step 3,
+steps 4 and 5 and every other figure (API rate, ILP accounting, multi-sector runs, HBM counter passes, value_steady, configs 2
+and 5) run with --full only.  --dump-outputs DIR writes the per-target report of the last timed scan as DIR/<name>.npy.
 Multi-GPU (--gpus N under torch.distributed.run): every rank tracks its own independent sensor sector
 (BASELINE config 4: disjoint sectors = no data-path collective), weak scaling; value = total scans / max time.
 """
@@ -70,7 +73,7 @@ def pmc_traffic_live(config, timeout_s=180.0):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="mht_pmc_", dir="/tmp")
         try:
-            cmd = [exe, "--pmc", counter, "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--config", config,
+            cmd = [exe, "--pmc", counter, "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--full", "--config", config,
                    "--cpu-scans", "0", "--sectors", "0", "--steps", "40", "--warmup", "8", "--pmc", "off", "--extras", "off"]
             left = timeout_s - (time.time() - t0)
             if left < 20:
@@ -262,6 +265,20 @@ class Replay:
 
     def close(self):
         self.trk.close()
+
+
+REPORT_COUNTS = ("scan", "n_targets", "n_alive", "n_leaves_in", "n_children", "n_leaves_out", "n_clusters", "n_ilp", "n_branched",
+                 "n_limit", "blp_iters_max", "error", "used_words", "n_births")
+
+
+def dump_outputs(d, rep, recs, suffix=""):
+    """What a caller of the timed path receives after its last scan: the per-target report (one array per field, float64, rows in
+    target-id order) and the scan's counts (device clock stamps left out), as d/<name><suffix>.npy."""
+    os.makedirs(d, exist_ok=True)
+    recs = recs[np.argsort(recs["id"], kind="stable")]
+    for f in recs.dtype.names:
+        np.save(os.path.join(d, "target_%s%s.npy" % (f, suffix)), recs[f].astype(np.float64))
+    np.save(os.path.join(d, "scan_counts%s.npy" % suffix), np.array([getattr(rep, f) for f in REPORT_COUNTS], dtype=np.float64))
 
 
 def ilp_accounting(sc, births, device, n_warm, n_scans):
@@ -457,6 +474,11 @@ def main():
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--config", default="cfg3")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the end-state check against the pre-pass, per-stage device times and roofline, API rate, "
+                         "ILP accounting, multi-sector figures, HBM counter passes, the extras and the CPU baseline (--sectors, --cpu-scans, "
+                         "--cpu-warm, --extras and --pmc act in --full runs only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the per-target report of the last timed scan as DIR/<name>.npy (float64)")
     ap.add_argument("--sectors", default="4,16,64", help="concurrent independent sectors per GPU for the multi_sector figures, comma separated (0 disables)")
     ap.add_argument("--cpu-scans", type=int, default=16, help="timed oracle scans for cpu_baseline (0 disables)")
     ap.add_argument("--cpu-warm", type=int, default=8)
@@ -544,13 +566,38 @@ def main():
     t1 = time.perf_counter()
     barrier()
     elapsed = t1 - t0
-    rep, recs = rp.report()
-    got = [(int(r["id"]), int(r["sel_meas"])) for r in recs if int(r["status"]) == 0]
-    same_work = (got == final) and rep.error == 0
-    uf_ovl = np.zeros(2, dtype=np.int32)      # scans clustered inside the grow launch, grow launches that overlapped the previous scan's ILP launch
-    rp.lib.mht_forest_debug_read(rp.h, b"uf_ovl", uf_ovl.ctypes.data_as(C.c_void_p), 8)
+    if args.dump_outputs or args.full:
+        rep, recs = rp.report()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rep, recs, "" if world == 1 else "_rank%d" % rank)
+    same_work = True
+    if args.full:
+        got = [(int(r["id"]), int(r["sel_meas"])) for r in recs if int(r["status"]) == 0]
+        same_work = (got == final) and rep.error == 0
+        uf_ovl = np.zeros(2, dtype=np.int32)      # scans clustered inside the grow launch, grow launches that overlapped the previous scan's ILP launch
+        rp.lib.mht_forest_debug_read(rp.h, b"uf_ovl", uf_ovl.ctypes.data_as(C.c_void_p), 8)
     rp.close()
     elapsed, same_work = parallel.reduce_clock(elapsed, same_work, dist, device="cuda")
+    timed = stats[W:W + K]
+    Lm, Gm, Mm = float(timed[:, 0].mean()), float(timed[:, 1].mean()), float(timed[:, 2].mean())
+    head = {
+        "metric": "scans/sec at ~5k+ leaf hypotheses x 500 measurements (per-scan gate + cluster + ILP + N-scan prune)",
+        "value": (1 if strong else world) * K / elapsed, "unit": "scans/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": "f64 state / f32 covariance (the reference's own mix)", "data": "synthetic",
+        "config": {"workload": ("BASELINE configs[2]: 500 targets, ~500 meas/scan, N-scan=5, P_d=0.9, eta2=5.99; " if args.config == "cfg3" else
+                                "config %s of pymht_amd/utils/scenario.py (NOT the headline workload): %d targets, N-scan=%d, %d-state model %s; " % (args.config, len(sc["x0"]), sc["N"], nx, model_of(sc).__name__.split(".")[-1])) +
+                               "one independent sector per GPU" + (" -- STRONG: the same sector on every GPU, ILPs spread by cluster" if strong else ""), "name": args.config, "targets": int(timed[:, 6].mean()),
+                   "leaves_per_scan": Lm, "gated_pairs_per_scan": Gm, "meas_per_scan": Mm, "n_scan": int(sc["N"]),
+                   "ilps_per_scan": float(timed[:, 3].mean()), "ilps_branched": int(timed[:, 4].sum()),
+                   "blp_dual_iters_max": int(timed[:, 5].max()), "host_us_per_scan_queued": round(1e6 * (t_enq - t0) / K, 2), "pre_roll_scans": PRE},
+    }
+    if not args.full:      # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(head))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # one picture of all sectors (outside the timed region; KB-sized all-gather over RCCL)
     alive = [r for r in recs if int(r["status"]) == 0]
     picture = parallel.gather_tracks([int(r["id"]) for r in alive], np.array([r["sel_x"] for r in alive]).reshape(-1, nx)[:, :4],
@@ -697,8 +744,6 @@ def main():
                 multi_all.append({"sectors_per_gpu": S, "ok": False, "error": repr(e)[:300]})
     multi = multi_all[0] if multi_all else None
 
-    timed = stats[W:W + K]
-    Lm, Gm, Mm = float(timed[:, 0].mean()), float(timed[:, 1].mean()), float(timed[:, 2].mean())
     # algorithmic bytes of the grow stage per scan: per leaf read x, P, cNLLR, P_d and write x_bar, P_bar, cNLLR, P_hat;
     # per gated pair x_hat, cNLLR, measurement index, parent index; 8 B per measurement -- 280 / 48 / 8 at four states, 552 / 64 / 8 at six
     b_gate = float(per_leaf) * Lm + float(per_pair) * Gm + 8.0 * Mm
@@ -729,18 +774,10 @@ def main():
                 configs_extra.append(config_extra(nm, local, wm, st_, cw, ct if args.cpu_scans > 0 else 0, 25.0))
             except Exception as e:      # noqa: BLE001
                 configs_extra.append({"name": nm, "error": repr(e)[:300]})
-    out = {
-        "metric": "scans/sec at ~5k+ leaf hypotheses x 500 measurements (per-scan gate + cluster + ILP + N-scan prune)",
-        "value": (1 if strong else world) * K / elapsed, "unit": "scans/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": "f64 state / f32 covariance (the reference's own mix)", "data": "synthetic",
-        "config": {"workload": ("BASELINE configs[2]: 500 targets, ~500 meas/scan, N-scan=5, P_d=0.9, eta2=5.99; " if args.config == "cfg3" else
-                                "config %s of pymht_amd/utils/scenario.py (NOT the headline workload): %d targets, N-scan=%d, %d-state model %s; " % (args.config, len(sc["x0"]), sc["N"], nx, model_of(sc).__name__.split(".")[-1])) +
-                               "one independent sector per GPU" + (" -- STRONG: the same sector on every GPU, ILPs spread by cluster" if strong else ""), "name": args.config, "targets": int(timed[:, 6].mean()),
-                   "leaves_per_scan": Lm, "gated_pairs_per_scan": Gm, "meas_per_scan": Mm, "n_scan": int(sc["N"]),
-                   "ilps_per_scan": float(timed[:, 3].mean()), "ilps_branched": int(timed[:, 4].sum()), "tracks_all_sectors": int(sum(len(i) for i, _ in picture)),
-                   "blp_dual_iters_max": int(timed[:, 5].max()), "replay_matches_prepass": same_work, "host_us_per_scan_queued": round(1e6 * (t_enq - t0) / K, 2), "scans_clustered_in_grow_launch": int(uf_ovl[0]), "grow_launches_overlapping_ilp": int(uf_ovl[1]),
-                   "pre_roll_scans": PRE},
+    out = head
+    out["config"].update({"tracks_all_sectors": int(sum(len(i) for i, _ in picture)), "replay_matches_prepass": same_work,
+                          "scans_clustered_in_grow_launch": int(uf_ovl[0]), "grow_launches_overlapping_ilp": int(uf_ovl[1])})
+    out.update({
         "stage_ms": {"gate": float(ms[0]), "cluster": float(ms[1]), "ilp": float(ms[2]), "prune": float(ms[3]),
                      "device_total": float(ms[4])},
         "value_steady": value_steady,
@@ -757,7 +794,7 @@ def main():
                      "frac": gate_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      "kernel": "fgrow_kernel (gate + update + score + child creation + next scan's gains, 1 launch), HIP events on the ctx stream",
                      "algorithmic_bytes": b_gate},
-    }
+    })
     if strong:
         # the Amdahl split of the sharded scan, from the device wall-clock stamps of the LAST timed scan on this rank (10 ns ticks in the
         # report header): grow and clustering are replicated on every rank, only the ILP stage shrinks with the rank count

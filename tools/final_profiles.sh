@@ -5,9 +5,9 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/final
 mkdir -p $out
 cd $root
-python bench.py --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
-MHT_BENCH_FORCE_DIST=1 python bench.py --gpus 1 --steps 20 --warmup 5 --sectors 0 --cpu-scans 0 --pmc off --extras off > $out/bench_force_dist.json 2> $out/bench_force_dist.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench_driver_args.json 2> $out/bench_driver_args.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+MHT_BENCH_FORCE_DIST=1 python bench.py --full --gpus 1 --steps 20 --warmup 5 --sectors 0 --cpu-scans 0 --pmc off --extras off > $out/bench_force_dist.json 2> $out/bench_force_dist.err
 # headline: kernel trace + HBM counters (separate passes)
 bash tools/profile_round.sh final/cfg3 > $out/profile_cfg3.log 2>&1
 # BASELINE config 5 (constant-turn forest): the same three passes
@@ -17,7 +17,7 @@ WAVES="1" bash tools/batch_profile.sh final/batch "4 16" > $out/batch_kernels.tx
 ( cd /tmp && export TMPDIR=/tmp
   for c in FETCH_SIZE WRITE_SIZE; do
     d=$out/bpmc_$c; rm -rf $d
-    MHT_BENCH_GROUPS=1 rocprofv3 --pmc $c -d $d -o p -- python $root/bench.py --cpu-scans 0 --pmc off --extras off --sectors 16 --steps 20 --warmup 5 > $out/bench_bpmc_$c.log 2>&1
+    MHT_BENCH_GROUPS=1 rocprofv3 --pmc $c -d $d -o p -- python $root/bench.py --full --cpu-scans 0 --pmc off --extras off --sectors 16 --steps 20 --warmup 5 > $out/bench_bpmc_$c.log 2>&1
     echo "== $c, S = 16, one group"; python $root/tools/rocpd_pmc.py $(find $d -name '*_results.db' | head -1) | grep -E "batch|kernel " | cut -c1-200
     rm -rf $d
   done ) > $out/batch_pmc.txt 2>&1

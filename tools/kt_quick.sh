@@ -6,7 +6,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $out/kt -o kt -- python $root/bench.py --cpu-scans 0 --sectors 0 --pmc off --steps $steps --warmup 40 > $out/bench_kt.log 2>&1
+rocprofv3 --kernel-trace -d $out/kt -o kt -- python $root/bench.py --full --cpu-scans 0 --sectors 0 --pmc off --steps $steps --warmup 40 > $out/bench_kt.log 2>&1
 cd $root
 python tools/rocpd_stats.py $(find $out/kt -name '*_results.db' | head -1) > $out/kernel_stats.txt 2>&1
 tail -1 $out/bench_kt.log | cut -c1-260 >> $out/kernel_stats.txt
