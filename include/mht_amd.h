@@ -238,8 +238,9 @@ typedef struct mht_forest_config {
 /* ---- AIS-aided forest (Tracker.addMeasurementList(scanList, aisList), tracker.py:162, :394-396, :417-552) ---------------------
  * mht_forest_create_ex(..., MHT_FOREST_AIS): a forest whose nodes also carry the identity of the AIS message they were updated
  * with and the identity their track is bound to (pyTarget.py:34, :297-302) and whose ILP rows include the AIS messages
- * (tracker.py:1057-1064, :1083-1090).  4-state build, n_scan <= 7 (n_scan <= 3: 8-entry path records, the ILPs stay in LDS;
- * above: 16-entry records, the ILPs run on the HBM policy).  mht_forest_set_ais hands over the messages of the NEXT scan, grouped as
+ * (tracker.py:1057-1064, :1083-1090).  4-state build, any n_scan a forest takes (<= 12).  Path records of two halves, radar rows and
+ * AIS rows: n_scan <= 3: 8 entries (32 bytes), the ILPs stay in LDS; n_scan <= 7: 16 entries (64 bytes); n_scan >= 8: 32 entries
+ * (128 bytes); from n_scan 4 on the ILPs run on the HBM policy.  mht_forest_set_ais hands over the messages of the NEXT scan, grouped as
  * for mht_fuse_ais; the next mht_forest_step / _step_host / _scan consumes them: radar M + nA <= max_meas (rounded up to a multiple
  * of 64).  A scan without messages needs no call.  Messages start tracks through the initiator (mht_initiator_set_ais).
  * Not available to members of a group.  The cluster-sharded step takes the messages (ABI 5): every shard makes the fused children itself.

@@ -266,6 +266,7 @@ static int fgrow_lds_attr(mht_ctx* ctx, size_t lds) {
         MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_adm_kernel<4, FG_CAP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ais_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ais_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ais_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 #if MHT_NX == 6
         MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ct_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ct_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -350,7 +351,8 @@ int launch_fgrow(mht_ctx* ctx, const FGrowArgs& a, FDyn& d, int n_targets_ub, co
         const PublishArgs pa = pub ? *publish : PublishArgs{};
         const CommitArgs cm = commit ? *commit : CommitArgs{};
         if (a.pds == 8) hipLaunchKernelGGL(fgrow_ais_kernel<2>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-        else hipLaunchKernelGGL(fgrow_ais_kernel<4>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
+        else if (a.pds == 16) hipLaunchKernelGGL(fgrow_ais_kernel<4>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
+        else hipLaunchKernelGGL(fgrow_ais_kernel<8>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);      // (32-int records: N >= 8)
         MHT_HIP_CHECK(hipGetLastError());
         return MHT_OK;
     }

@@ -437,9 +437,10 @@ __device__ __forceinline__ void fg_single_leaf(const ARGS& a, int src, bool f32s
     out.zhx = (float)zh[0]; out.zhy = (float)zh[1];
 }
 
-// PQ = 16-byte pieces of a path / ancestor record (2: records of 8 ints, N-scan <= 7; 4: 16 ints) -- a template parameter because
-// a leaf's two records sit in registers between their load and their LDS store: 32 registers at PQ = 4, and the kernel is at the
-// edge of its budget (128 for four workgroups per CU in the batched launch).
+// PQ = 16-byte pieces of a path / ancestor record (2: records of 8 ints, N-scan <= 7; 4: 16 ints; 8: 32 ints, AIS forests with
+// N-scan >= 8 only) -- a template parameter because a leaf's two records sit in registers between their load and their LDS store: 32
+// registers at PQ = 4, and the kernel is at the edge of its budget (128 for four workgroups per CU in the batched launch).  PQ = 8
+// holds four pieces at a time (target_part: PQL).
 // bslot: the slot whose static block of the node index space the target's children take (its own; a target admitted inside this launch
 // takes one behind the slots of the uncommitted table, which the other workgroups of the launch are using).  born = 1: such a target --
 // slot t of the COMMITTED table (d.fused = 0 for it), count and root columns of that table
@@ -624,12 +625,14 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                 double xd[NX];
 #pragma unroll
                 for (int k = 0; k < NX; ++k) xd[k] = a.x[(size_t)k * a.cap + src];
-                // the leaf's path / ancestor records (pds ints each: 2 or 4 x 16 bytes)
+                // the leaf's path / ancestor records (pds ints each: 2, 4 or 8 x 16 bytes).  At most four pieces of each are held in registers
+                // from here on; the rest of a 32-int record (PQ = 8, AIS forests with N >= 8) is loaded where it is parked, in a second pass
+                constexpr int PQL = PQ < 4 ? PQ : 4;
                 const int4* prec = reinterpret_cast<const int4*>(a.in_path + (size_t)src * PDS);
                 const int4* arec = reinterpret_cast<const int4*>(a.in_apath + (size_t)src * PDS);
-                int4 pq[PQ], aq[PQ];
+                int4 pq[PQL], aq[PQL];
 #pragma unroll
-                for (int q = 0; q < PQ; ++q) { pq[q] = prec[q]; aq[q] = arec[q]; }
+                for (int q = 0; q < PQL; ++q) { pq[q] = prec[q]; aq[q] = arec[q]; }
                 // batch B: the gains of the leaf's covariance column
                 float4 gr[GKQ];
 #pragma unroll
@@ -676,15 +679,21 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                 g.pd = pd;
                 // records parked raw (the root advance `shift` is applied when they are read back); last real measurement on the path
 #pragma unroll
-                for (int q = 0; q < PQ; ++q) {
+                for (int h = 0; h < PQ; h += PQL) {
+                    if (h > 0) {
+#pragma unroll
+                        for (int q = 0; q < PQL; ++q) { pq[q] = prec[h + q]; aq[q] = arec[h + q]; }
+                    }
+#pragma unroll
+                    for (int q = 0; q < PQL; ++q) {
                         if (keep) {
-                            reinterpret_cast<int4*>(s_pp + tid * PDS)[q] = pq[q];
-                            reinterpret_cast<int4*>(s_ap + tid * PDS)[q] = aq[q];
+                            reinterpret_cast<int4*>(s_pp + tid * PDS)[h + q] = pq[q];
+                            reinterpret_cast<int4*>(s_ap + tid * PDS)[h + q] = aq[q];
                         }
                         const int pe[4] = {pq[q].x, pq[q].y, pq[q].z, pq[q].w};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            const int i = q * 4 + e;
+                            const int i = (h + q) * 4 + e;
                             if (!AIS) {
                                 if (i >= shift && i < shift + depth && pe[e] >= 0) last = pe[e];
                             } else {      // two halves: the deepest level that has a row contributes its row(s); lvl_* ride in nfv / offv until the loads below
@@ -696,6 +705,7 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                             }
                         }
                     }
+                }
                 if (AIS) {
                     if (nfv < offv) last = -1;          // (a deeper AIS-only level: the radar row further up belongs to an ancestor's own all-miss leaf)
                     if (offv < nfv) last2 = -1;

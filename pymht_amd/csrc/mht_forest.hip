@@ -308,7 +308,7 @@ struct Forest {
     Arena arena;
     mht_nodes layer[MAXR];
     int32_t* path[2]; int32_t* apath[2]; double* cost2[2]; int32_t* tchild; int32_t* tcend;      // cost2: ILP costs of the newest layer's nodes, by scan parity (the next scan's grow launch may overlap this scan's ILP launch)
-    int pds = 8;                      // ints per path / ancestor record (8 or 16)
+    int pds = 8;                      // ints per path / ancestor record (8 or 16; an AIS forest 8, 16 or 32)
     // AIS forest (mht_forest_create_ex, MHT_FOREST_AIS; mht_kernels.h: AisGrow): identities per node, record pool of the fused children,
     // the messages of the next scan (mht_forest_set_ais arms them, the next step consumes them)
     // constant-turn forest (six-state build, MHT_FOREST_CT; mht_kernels.h: CtGrow): per ring layer the covariances of its nodes' children and of
@@ -635,7 +635,6 @@ static int forest_create_impl(mht_ctx* ctx, const mht_model* model, const mht_fo
     MHT_REQUIRE((flags & ~(uint32_t)(MHT_FOREST_AIS | MHT_FOREST_CT)) == 0, "mht_forest_create_ex: unknown flags 0x%x", flags);
     if (flags & MHT_FOREST_AIS) {
         MHT_REQUIRE(NX == 4, "mht_forest_create_ex: AIS messages report four states (models/ais.py); this is the %d-state build", NX);
-        MHT_REQUIRE(cfg->n_scan <= 7, "mht_forest_create_ex: an AIS forest keeps two rows per level in a 16-entry path record: n_scan must be <= 7 (got %d)", cfg->n_scan);
     }
     MHT_REQUIRE(!ctx->forest, "mht_forest_create: the ctx already owns a forest");
     MHT_REQUIRE(cfg->n_scan >= 1 && cfg->n_scan + RING_EXTRA <= MAXR, "mht_forest_create: n_scan must be in [1, %d]", MAXR - RING_EXTRA);
@@ -712,9 +711,9 @@ static int forest_create_impl(mht_ctx* ctx, const mht_model* model, const mht_fo
         f->ct_T = (double)model->A[(NX >= 6 ? 4 : 0) * NX + (NX >= 6 ? 5 : 0)];
         f->ovl_ok = false;
     }
-    if (flags & MHT_FOREST_AIS) {      // two halves per record: radar rows, AIS rows
+    if (flags & MHT_FOREST_AIS) {      // two halves per record: radar rows, AIS rows (records of 8, 16 or 32 ints)
         f->ais = true;
-        f->ais_half = f->PD <= 4 ? 4 : 8;
+        f->ais_half = f->PD <= 4 ? 4 : (f->PD <= 8 ? 8 : 16);
         f->pds = 2 * f->ais_half;
     }
 

@@ -99,7 +99,7 @@ struct FGrowArgs {
     VTab vt;
     const int32_t* in_path;        // [cap][pds] measurement nodes below the root, one record per node of the input layer
     const int32_t* in_apath;       // [cap][pds] ancestor node per level
-    int pds;                       // ints per record: 8 (PD <= 8) or 16
+    int pds;                       // ints per record: 8 (PD <= 8) or 16; an AIS forest 8, 16 or 32 (two halves of 4, 8 or 16 levels)
     // the target table this scan runs on.  fused (FDyn) = 1: the commit of the previous scan has not run (it rides in workgroup 0):
     // the per-target results of that scan (p_*), indexed by old slot, stand in for the compacted table
     const int32_t* nT_dev;
