@@ -252,7 +252,8 @@ typedef struct mht_forest_config {
  * (pymht_amd/models/ct.py; state [x, y, vx, vy, w, a]).  The transition is not model->A but Phi(T, w) rebuilt for every hypothesis from its
  * own turn rate x[4], T = model->A[4][5] (give A = Phi(T, 0)); every leaf runs the reference's per-hypothesis form kalman.predict_single +
  * kalman.precalc on a batch of one (kalman.py:67-70, :82-101) -- what mht_gate_scan_x does with mht_model_x.transition = 1 -- and nothing
- * is shared by value: the forest keeps the children's covariances per node.  No device initiator, no similar-state pruning, no groups. */
+ * is shared by value: the forest keeps the children's covariances per node.  The device initiator starts tracks in it (as in any forest of
+ * the six-state build) once its births are lifted (mht_initiator_set_lift); they begin on the straight-line branch of Phi(T, 0).  No groups. */
 #define MHT_FOREST_CT 2u
 int mht_forest_create_ex(mht_ctx* ctx, const mht_model* model, const struct mht_forest_config* cfg, uint32_t flags);
 int mht_forest_set_ais(mht_ctx* ctx, const mht_ais_group* groups, int32_t nG, const mht_ais_msg* msgs, int32_t nA, double eta2_ais, double lambda_ais);
@@ -436,6 +437,13 @@ int mht_initiator_set_ais(mht_initiator* in, const mht_ais_init_msg* msgs, int32
  * initiator's lists.  Synchronises. */
 int mht_initiator_born(mht_initiator* in, int32_t capacity, double* x0, float* P0, int32_t* meas, int32_t* n_born,
                        int32_t* n_prelim, int32_t* n_seeds);
+/* Six-state build only: the births of this 4-state initiator enter a forest behind mht_forest_initiate / mht_forest_scan LIFTED into its
+ * state space, x0 [x, y, vx, vy] (float32 values) and P0 (4 x 4) becoming
+ *     x = [x0, x_tail[0], x_tail[1]],   P = [[P0, 0], [0, P_tail]]   (P_tail 2 x 2 row-major, the cross blocks exactly 0)
+ * -- in the forest's layers, its root covariances and the report's mht_birth_report rows.  nx must be 6.  The initiator itself (its
+ * preliminary tracks, gates, assignments, merging, mht_initiator_born's x0 [n][4] / P0 [n][16]) is unchanged.  Without this call the
+ * six-state build refuses an initiator in mht_forest_initiate / mht_forest_scan; the 4-state build refuses the call (MHT_E_INVALID). */
+int mht_initiator_set_lift(mht_initiator* in, int32_t nx, const float* x_tail, const float* P_tail);
 
 /* Step 7 behind a forest step, on the stream, no host round trip: runs the scan's commit, offers the scan's unused measurements
  * (tracker.py:266) to the initiator and hands its confirmed candidates to Tracker.initiateTarget's device twin

@@ -168,6 +168,7 @@ def _declare(lib, nx=4):
         "mht_initiator_destroy": [vp],
         "mht_initiator_step": [vp, vp, i32, vp, dbl],
         "mht_initiator_born": [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)],
+        "mht_initiator_set_lift": [vp, i32, vp, vp],
         "mht_forest_initiate": [vp, vp, vp, i32, dbl],
         "mht_forest_scan": [vp, vp, vp, i32, dbl],
         "mht_forest_step_sharded_begin": [vp, vp, i32, i32, i32, vp],

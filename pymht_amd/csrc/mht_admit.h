@@ -22,7 +22,36 @@ struct AddArgs {
     const int32_t* n_dev;      // number of candidates in device memory (or null: n)
     int32_t* mmsi; int32_t* hmmsi;      // AIS forest: identities of the newest layer's nodes (a root has none), else null
     ReportHeader* hdr; mht_birth_report* births;      // report block of the device initiator's candidates (or null)   // gains of the new roots (row cov_base + r of the newest layer's gain table); first root node
+#if MHT_NX == 6
+    // births of the 4-state device initiator in a six-state forest (mht_initiator_set_lift): x0 [n][4], P0 [n][16] are lifted on admission to
+    // x = [x4, lift_x], P = [[P4, 0], [0, lift_P]] (cross blocks exactly 0).  lift = 0: x0 [n][NX], P0 [n][NP] as given (mht_forest_add_targets)
+    int lift; double lift_x[NX - 4]; float lift_P[(NX - 4) * (NX - 4)];
+#endif
 };
+
+// entry k of candidate q's state / entry e of its covariance, in the forest's state space (the 4-state build: the arrays as given)
+__device__ __forceinline__ int adm_stride(const AddArgs& a) {
+#if MHT_NX == 6
+    return a.lift ? 4 : NX;
+#else
+    (void)a; return NX;
+#endif
+}
+__device__ __forceinline__ double adm_x(const AddArgs& a, int q, int k) {
+#if MHT_NX == 6
+    if (a.lift) return k < 4 ? a.x0[q * 4 + k] : a.lift_x[k - 4];
+#endif
+    return a.x0[q * NX + k];
+}
+__device__ __forceinline__ float adm_P(const AddArgs& a, int q, int e) {
+#if MHT_NX == 6
+    if (a.lift) {
+        const int i = e / NX, j = e % NX;
+        return (i < 4 && j < 4) ? a.P0[q * 16 + i * 4 + j] : (i >= 4 && j >= 4) ? a.lift_P[(i - 4) * (NX - 4) + (j - 4)] : 0.f;
+    }
+#endif
+    return a.P0[q * NP + e];
+}
 
 // Tracker.initiateTarget (tracker.py:147-160) for a batch of candidates.  The test against the existing leaves
 // (pyTarget.haveNoNeightbours, pyTarget.py:181-189) runs for all candidates in one parallel sweep; the candidates are
@@ -39,6 +68,7 @@ __device__ __forceinline__ void add_targets_body(const AddArgs& a, int* sm) {
     }
     for (int q = tid; q < an; q += NT) a.near[q] = 0;
     __syncthreads();
+    const int SX = adm_stride(a);      // (candidates' state stride: NX, or 4 for lifted births)
     if (a.check) {
         // every live leaf against every candidate.  The leaf -> node map (target ranges: leaf_off, first) goes through LDS, a chunk of
         // 2047 targets at a time, and every thread has eight leaves in flight: a binary search through global memory per leaf (nine
@@ -69,7 +99,7 @@ __device__ __forceinline__ void add_targets_body(const AddArgs& a, int* sm) {
                 for (int u = 0; u < UN; ++u) {
                     if (!ok[u] || (fl[u] & F_DEAD)) continue;      // (F_DEAD: taken out of the tree by similar-state pruning)
                     for (int q = 0; q < an; ++q) {
-                        const double dx = lx[u] - a.x0[q * NX], dy = ly[u] - a.x0[q * NX + 1];
+                        const double dx = lx[u] - a.x0[q * SX], dy = ly[u] - a.x0[q * SX + 1];
                         if (sqrt(dx * dx + dy * dy) < a.thr) a.near[q] = 1;
                     }
                 }
@@ -96,12 +126,12 @@ __device__ __forceinline__ void add_targets_body(const AddArgs& a, int* sm) {
         if (tid == 0) s_near = q < 2048 ? s_nearv[q] : a.near[q];
         __syncthreads();
         if (a.check && !s_near) {
-            const double qx = a.x0[q * NX], qy = a.x0[q * NX + 1];
+            const double qx = a.x0[q * SX], qy = a.x0[q * SX + 1];
             const int na = s_nadm;
             int hit = 0;
             for (int i = tid; i < na; i += NT) {
                 const int pc = s_adm[i & 2047];
-                const double dx = a.x0[pc * NX] - qx, dy = a.x0[pc * NX + 1] - qy;
+                const double dx = a.x0[pc * SX] - qx, dy = a.x0[pc * SX + 1] - qy;
                 if (sqrt(dx * dx + dy * dy) < a.thr) hit = 1;
             }
             if (hit) s_near = 1;
@@ -112,7 +142,7 @@ __device__ __forceinline__ void add_targets_body(const AddArgs& a, int* sm) {
             const int ok = !near && c_nT < a.Tcap && c_roots < a.Tcap;
             if (!near && !ok) a.cnt->overflow = 1;
             double xq[NX];
-            for (int k = 0; k < NX; ++k) xq[k] = a.x0[q * NX + k];
+            for (int k = 0; k < NX; ++k) xq[k] = adm_x(a, q, k);
             const int mq = a.meas[q];
             if (ok) {
                 // roots born into a layer live at its end (node root_base + r): the children of a scan are spread over the regions
@@ -153,7 +183,7 @@ __device__ __forceinline__ void add_targets_body(const AddArgs& a, int* sm) {
                 b.id = ok ? c_id - 1 : -1;
                 b.meas = mq;
                 for (int k = 0; k < NX; ++k) b.x0[k] = xq[k];
-                for (int e = 0; e < NP; ++e) b.P0[e] = a.P0[q * NP + e];
+                for (int e = 0; e < NP; ++e) b.P0[e] = adm_P(a, q, e);
             }
         }
         __syncthreads();
@@ -165,7 +195,7 @@ __device__ __forceinline__ void add_targets_body(const AddArgs& a, int* sm) {
     for (int k = tid; k < s_nadm; k += NT) {
         const int q = s_adm[k & 2047];
         float P[NP];
-        for (int e = 0; e < NP; ++e) P[e] = a.P0[q * NP + e];
+        for (int e = 0; e < NP; ++e) P[e] = adm_P(a, q, e);
         if (a.ct_Proot) {      // (nothing is shared by value: the root's covariance goes to its layer's root array, its key names the slot)
             for (int e = 0; e < NP; ++e) a.ct_Proot[(size_t)(r0 + k) * NP + e] = P[e];
             a.layer.cov[a.root_base + r0 + k] = -2 - (r0 + k);

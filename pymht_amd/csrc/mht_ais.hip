@@ -320,6 +320,21 @@ __global__ __launch_bounds__(64) void forest_ct_kernel(const CtForestArgs a) {
         row[GK_RY] = sqrtf((float)a.model.eta2 * fabsf(S[3]));
 #pragma unroll
         for (int q = 0; q < GKQ; ++q) a.gains[(size_t)nd * GKQ + q] = make_float4(row[4 * q], row[4 * q + 1], row[4 * q + 2], row[4 * q + 3]);
+        if (a.flags[nd] & F_STATE_F32) {
+            // a float32 chain (a track the device initiator started): A.dot(x) and C.dot(x_bar) in float32, as the reference computes them for
+            // a float32 state (the covariance part does not depend on the state's dtype).  Redone here, once the rest is stored: holding the
+            // transition and both states across it costs the kernel its register budget
+            float A[36], xf[6], xbf[6];
+            ct_phi(a.T, a.x[(size_t)4 * a.cap + nd], A);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) xf[k] = (float)a.x[(size_t)k * a.cap + nd];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) xbf[i] = gemv_row<float, 6>(A + i * 6, xf);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) a.xbar[(size_t)k * a.cap + nd] = (double)xbf[k];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) a.zhat[(size_t)i * a.cap + nd] = (double)gemv_row<float, 6>(a.model.C + i * 6, xbf);
+        }
     }
 }
 #endif

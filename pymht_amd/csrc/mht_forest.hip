@@ -1206,6 +1206,7 @@ void initiator_born_ptrs(const mht_initiator* in, const double** x, const float*
                          const int32_t** n, int* cap, mht_ctx** ctx);
 int initiator_ais_pending(const mht_initiator* in);
 int initiator_mreq(const mht_initiator* in);
+bool initiator_lift(const mht_initiator* in, double* x, float* P);
 void initiator_ais_ptrs(mht_initiator* in, const AisInitMsg** msgs, unsigned char** used);
 }
 
@@ -1831,13 +1832,23 @@ static int forest_initiate_impl(mht_ctx* ctx, mht_initiator* in, const float* z,
     if (f->ais) { a.mmsi = f->l_mmsi[f->scan % f->R]; a.hmmsi = f->l_hmmsi[f->scan % f->R]; }
     a.hdr = reinterpret_cast<ReportHeader*>(report_dev);
     a.births = reinterpret_cast<mht_birth_report*>(report_dev + f->birth_off);
+#if MHT_NX == 6
+    {   // the initiator's births are 4-state: lifted into the forest's state space on admission (checked by the callers: the lift is set)
+        double lx[2]; float lP[4];
+        a.lift = initiator_lift(in, lx, lP) ? 1 : 0;
+        for (int k = 0; k < 2; ++k) a.lift_x[k] = lx[k];
+        for (int e = 0; e < 4; ++e) a.lift_P[e] = lP[e];
+    }
+#endif
     // commit (if it is still pending: the used-measurement mask of the scan is part of it) + initiator + admission: one launch
     { const int rc = flush_publish(ctx, f); if (rc) return rc; }      // (an older report still waiting for a ride: its device block is about to be reused)
     // the report goes to the host from this launch, or -- streaming: mht_forest_scan -- with the next scan's grow launch
     PublishArgs pub = publish_args(f);
     if (defer_publish) { f->pub_args = pub; pub.dst = nullptr; }
     // streaming (mht_forest_scan) and nothing left to do here but the commit and the admission: both ride in the next scan's grow launch
-    const bool ride = defer_publish && init_done && f->adm_fuse && f->commit_pending && !f->ais && au.nA == 0 && ia.nA == 0;
+    // (fgrow_adm_kernel, whose grow is the shared-transition one: a constant-turn forest's grow kernel carries no admission -- its commit and
+    // admission run as post_scan_kernel here)
+    const bool ride = defer_publish && init_done && f->adm_fuse && f->commit_pending && !f->ais && !f->ct && au.nA == 0 && ia.nA == 0;
     if (!ride) { const int rc = wait_init_ev(ctx, f); if (rc) return rc; }
     if (!ride) { const int rc = flush_z_wait(ctx, f); if (rc) return rc; }      // (post_scan_kernel may read the scan)
     if (ride) { f->adm = a; f->adm_pending = true; }
@@ -1860,8 +1871,15 @@ static int forest_initiate_impl(mht_ctx* ctx, mht_initiator* in, const float* z,
     return MHT_OK;
 }
 
+// the six-state build takes the 4-state initiator's births only lifted into its state space (mht_initiator_set_lift)
+static bool initiator_fits(const mht_initiator* in) {
+    double x[2]; float P[4];
+    return NX == 4 || initiator_lift(in, x, P);
+}
+
 extern "C" int mht_forest_initiate(mht_ctx* ctx, mht_initiator* in, const float* z, int32_t M, double now) {
-    MHT_REQUIRE(NX == 4, "mht_forest_initiate: the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv); this is the %d-state build", NX);
+    MHT_REQUIRE(!in || initiator_fits(in), "mht_forest_initiate: the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv); "
+                "this is the %d-state build: call mht_initiator_set_lift first", NX);
     return forest_initiate_impl(ctx, in, z, M, now, false);
 }
 
@@ -1941,7 +1959,8 @@ extern "C" int mht_forest_step_host(mht_ctx* ctx, const float* z_host, int32_t M
 extern "C" int mht_forest_scan(mht_ctx* ctx, mht_initiator* in, const float* z_host, int32_t M, double now) {
     hp_begin();
     if (in) {      // (checked before the scan is stepped: nothing may fail between the initiator's run and the admission of its births)
-        MHT_REQUIRE(NX == 4, "mht_forest_scan: the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv); this is the %d-state build", NX);
+        MHT_REQUIRE(initiator_fits(in), "mht_forest_scan: the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv); "
+                    "this is the %d-state build: call mht_initiator_set_lift first", NX);
         MHT_REQUIRE(ctx && ctx->forest, "mht_forest_scan: no forest");
         const double* bx; const float* bP; const uint8_t* bfl; const double* bpd; const int32_t* bme; const int32_t* bn; int cap; mht_ctx* ictx;
         initiator_born_ptrs(in, &bx, &bP, &bfl, &bpd, &bme, &bn, &cap, &ictx);

@@ -38,6 +38,8 @@ struct mht_initiator {
     int ais_pending = 0;              // messages handed in for the next run (mht_initiator_set_ais)
     bool ais_used_valid = false;      // ... with caller-provided used flags (else: the forest computes them, or none was taken)
     bool ais_used_by_forest = false;
+    int lift_nx = 0;                  // six-state build: births enter the forest lifted to lift_nx states (mht_initiator_set_lift), 0: not set
+    double lift_x[2] = {}; float lift_P[4] = {};
 };
 
 namespace mht {
@@ -106,6 +108,12 @@ void initiator_born_ptrs(const mht_initiator* in, const double** x, const float*
     const InitArgs& a = in->args;
     *x = a.born_x; *P = a.born_P; *fl = a.born_flags; *pd = a.born_pd; *meas = a.born_meas; *n = a.born_n; *cap = in->cfg.max_born; *ctx = in->ctx;
 }
+// six-state build: has mht_initiator_set_lift been called (its births can enter this build's forests)?  x [2], P [4]: the tail it set
+bool initiator_lift(const mht_initiator* in, double* x, float* P) {
+    for (int k = 0; k < 2; ++k) x[k] = in->lift_x[k];
+    for (int e = 0; e < 4; ++e) P[e] = in->lift_P[e];
+    return in->lift_nx == NX;
+}
 }  // namespace mht
 
 using namespace mht;
@@ -166,6 +174,18 @@ extern "C" int mht_initiator_set_ais(mht_initiator* in, const mht_ais_init_msg* 
     if (nA && used) MHT_HIP_CHECK(hipMemcpyAsync(const_cast<unsigned char*>(in->args.ais_used), used, (size_t)nA, hipMemcpyHostToDevice, in->ctx->stream));
     in->ais_pending = nA;
     in->ais_used_valid = nA > 0 && used != nullptr;
+    return MHT_OK;
+}
+
+// The six-state build: births of this (4-state) initiator enter a forest as x = [x4, x_tail], P = [[P4, 0], [0, P_tail]] (mht_admit.h: AddArgs::lift).
+// The initiator itself is unchanged; only the admission behind mht_forest_initiate / mht_forest_scan lifts.
+extern "C" int mht_initiator_set_lift(mht_initiator* in, int32_t nx, const float* x_tail, const float* P_tail) {
+    MHT_REQUIRE(in && x_tail && P_tail, "mht_initiator_set_lift: null argument");
+    MHT_REQUIRE(NX == 6, "mht_initiator_set_lift: births of the 4-state initiator enter 4-state forests as they are; this is the %d-state build", NX);
+    MHT_REQUIRE(nx == NX, "mht_initiator_set_lift: nx=%d, this is the %d-state build", nx, NX);
+    for (int k = 0; k < 2; ++k) in->lift_x[k] = (double)x_tail[k];
+    for (int e = 0; e < 4; ++e) in->lift_P[e] = P_tail[e];
+    in->lift_nx = nx;
     return MHT_OK;
 }
 

@@ -40,6 +40,14 @@ class Initiator:
         _lib.check(self._lib.mht_initiator_create(ctx.handle, C.byref(self.handle), C.byref(cfg)))
         self.n_preliminary = self.n_initiators = 0
 
+    def set_lift(self, nx, x_tail, P_tail):
+        """Six-state library only (mht_initiator_set_lift): the births enter a six-state forest as x = [x4, x_tail], P = [[P4, 0], [0, P_tail]].
+        The initiator itself stays the reference's 4-state one; `processMeasurements` still returns 4-state targets."""
+        xt = np.ascontiguousarray(np.asarray(x_tail, np.float32).reshape(-1))
+        Pt = np.ascontiguousarray(np.asarray(P_tail, np.float32).reshape(-1))
+        assert xt.size == int(nx) - 4 and Pt.size == (int(nx) - 4) ** 2, "the tail of a lift to %d states has %d + %d entries" % (nx, nx - 4, (nx - 4) ** 2)
+        _lib.check(self._lib.mht_initiator_set_lift(self.handle, int(nx), xt.ctypes.data_as(C.c_void_p), Pt.ctypes.data_as(C.c_void_p)), self._lib)
+
     def processMeasurements(self, radar_measurement_list, ais_measurement_list=()):
         """m_of_n.py:233-244: the list holds the measurements no track gated; returns the new `Target`s."""
         import torch

@@ -21,6 +21,7 @@ import numpy as np
 from . import _lib
 from .device import Context, make_model
 from .initiators import m_of_n
+from .models import pv
 from .pyTarget import Target
 from .utils.classDefinitions import AisMessageList, MeasurementList  # noqa: F401
 from .utils import xmlDefinitions as xmltags
@@ -141,8 +142,16 @@ class Tracker():
         assert self.nx in (4, 6), "pymht_amd is built for 4- and 6-state models"
         self._REPORT_DTYPE, self._BIRTH_DTYPE = _report_dtypes(self.nx)
         self.useInitiator = kwargs.get('useInitiator', self.nx == 4)
-        if self.useInitiator and self.nx != 4:
-            raise NotImplementedError("the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv): useInitiator=False for a six-state model")
+        # six-state model: the 4-state initiator's births enter the forest lifted, x = [x4, t], P = [[P4, 0], [0, Pt]] (mht_initiator_set_lift);
+        # (t, Pt) = birthTail, by default zeros and the model's own P0[4:, 4:]
+        self.liftBirths = bool(kwargs.get('liftBirths', False))
+        if self.useInitiator and self.nx != 4 and not self.liftBirths:
+            raise NotImplementedError("the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv): useInitiator=False for a "
+                                      "six-state model, or liftBirths=True to start its births as [x, y, vx, vy] + birthTail (default: zeros, model.P0[4:, 4:])")
+        birth_tail = kwargs.get('birthTail', None)
+        if birth_tail is None:
+            birth_tail = (np.zeros(self.nx - 4), np.asarray(model.P0)[4:, 4:])
+        self._birth_tail = (np.asarray(birth_tail[0], np.float32).reshape(self.nx - 4), np.asarray(birth_tail[1], np.float32).reshape(self.nx - 4, self.nx - 4))
         self._ctx = Context(kwargs.get('device', 0), nx=self.nx)
         self._lib = self._ctx.lib
         self._model = make_model(self.A, self.Q, self.C, self.R_RADAR, self.eta2, self.lambda_ex, self.default_P_d)
@@ -180,10 +189,14 @@ class Tracker():
             _lib.check(self._lib.mht_forest_create(self._ctx.handle, C.byref(self._model), C.byref(cfg)))
         if self._blp_time_limit is not None:
             _lib.check(self._lib.mht_forest_set_blp_time_limit(self._ctx.handle, 1e3 * float(self._blp_time_limit)))
-        # Target initiator (tracker.py:61-72): on the device, behind every scan's commit (mht_forest_initiate)
-        self.initiator = m_of_n.Initiator(self.M_required, self.N_checks, self.maxSpeedMS, self.C, self.R_RADAR, self.mergeThreshold,
+        # Target initiator (tracker.py:61-72): on the device, behind every scan's commit (mht_forest_initiate).  It is the reference's 4-state one
+        # whatever the model: a six-state tracker hands it models/pv's measurement matrices, and the forest lifts its births
+        init_C, init_R = (self.C, self.R_RADAR) if self.nx == 4 else (pv.C_RADAR, pv.R_RADAR())
+        self.initiator = m_of_n.Initiator(self.M_required, self.N_checks, self.maxSpeedMS, init_C, init_R, self.mergeThreshold,
                                           ctx=self._ctx, maxMeasurements=cfg.max_meas, default_pd=self.default_P_d) \
             if self.useInitiator else None
+        if self.initiator is not None and self.nx != 4:
+            self.initiator.set_lift(self.nx, *self._birth_tail)
         # per-stage device times (toc['Process'], ['Cluster'], ['Optim'], ['N-Prune']: five HIP events per scan and a stream
         # synchronisation to read them): off by default, it keeps the host from running ahead of the device
         self._timing = bool(kwargs.get('deviceTiming', False))
