@@ -19,6 +19,7 @@
 #ifndef MHT_AMD_H
 #define MHT_AMD_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -29,8 +30,8 @@ extern "C" {
 
 /* State dimension of the library build the header is used with: 4 (libmht_amd.so: the reference's CV model, models/pv.py) or 6
  * (libmht_amd6.so: the same sources compiled with -DMHT_NX=6 for BASELINE config 5's six-state model).  It sizes the model matrices
- * and the state vectors / covariances of the forest's reports; the stateless seams mht_gate_scan (4 states) and mht_gate_scan_x
- * (4 or 6 at run time) do not depend on it. */
+ * and the state vectors / covariances of the forest's reports; the stateless seams mht_gate_scan (4 states), mht_gate_scan_x and
+ * mht_smooth_tracks (4 or 6 at run time) do not depend on it. */
 #ifndef MHT_NX
 #define MHT_NX 4
 #endif
@@ -176,6 +177,35 @@ int mht_solve_blp(mht_ctx* ctx, int32_t nHyp, int32_t nT, int32_t nRows, int32_t
  * Asynchronous on the ctx stream. */
 int mht_prune(mht_ctx* ctx, int32_t n_nodes, const int32_t* parent, int32_t T, const int32_t* sel, const int32_t* window,
               int32_t* new_root, uint8_t* keep);
+
+/* ---- seam (v): Target.getSmoothTrack (pyTarget.py:580-609) for ALL tracks of an export -- Tracker.getSmoothTracks, and the
+ * <SmoothedStates> of every <Track> (pyTarget.py:745-802) -- stateless ---------------------------------------------------------
+ * A fixed-interval Rauch-Tung-Striebel smoother over a batch of track histories, float64 throughout.  The reference hands each
+ * history to pykalman, whose EM step re-estimates the noise covariances and is not reproducible; here the model is the tracker's
+ * own (model: nx, A, Q, C, R are read and widened to float64; transition must be 0 -- a state-dependent transition has no linear
+ * smoother: MHT_E_INVALID).  Q and R are covariances: their upper triangles are read.
+ * Track t (0 <= t < n_tracks) has len[t] nodes, 1 <= len[t] <= L_max; node 0 is its initial state, node k >= 1 carries a radar
+ * measurement or none (a missed detection, or a node updated by an AIS message alone):
+ *   forward   xf_0 = x_init, Pf_0 = P_init;  xp_k = A xf_{k-1}, Pp_k = A Pf_{k-1} A' + Q;  with a measurement S = C Pp_k C' + R,
+ *             K = Pp_k C' S^-1, xf_k = xp_k + K (z_k - C xp_k), Pf_k = Pp_k - K C Pp_k;  without one xf_k = xp_k, Pf_k = Pp_k
+ *   backward  xs_{L-1} = xf_{L-1}, Ps_{L-1} = Pf_{L-1};  G = Pf_k A' Pp_{k+1}^-1 (through a Cholesky factor of Pp_{k+1}),
+ *             xs_k = xf_k + G (xs_{k+1} - xp_{k+1}),  Ps_k = Pf_k + G (Ps_{k+1} - Pp_{k+1}) G'
+ * One track per lane; all device arrays are track-minor so that a wavefront's accesses coalesce:
+ *   len      HOST [n_tracks] int32 (checked before anything is launched)
+ *   x_init   dev [nx][n_tracks] f64          P_init  dev [nx*nx][n_tracks] f64 (row-major entries; the upper triangle is read)
+ *   z        dev [L_max][2][n_tracks] f64    has_z   dev [L_max][n_tracks] uint8, non-zero = node k of the track has a measurement
+ *            (row 0 of both is ignored; rows >= len[t] of track t are not read)
+ *   xs       dev [L_max][nx][n_tracks] f64 out
+ *   Ps       dev [L_max][nx (nx + 1) / 2][n_tracks] f64 out, or NULL (means only): the upper triangle row by row -- (0,0), (0,1), ..
+ *            (0,nx-1), (1,1), ..; the result is symmetric by construction.  Rows >= len[t] of track t are left as they were.
+ *   work     dev, work_bytes >= mht_smooth_work_bytes(nx, n_tracks, L_max) (the filtered states of every node; 0 for a bad nx or
+ *            a negative size): MHT_E_CAPACITY if it is smaller.
+ * A wavefront runs as long as the longest of its 64 tracks: put tracks of similar length next to each other.  No track's result
+ * depends on its place in the batch or on the other tracks.  Synchronises.  On MHT_E_INVALID / MHT_E_CAPACITY nothing has been written. */
+size_t mht_smooth_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max);
+int mht_smooth_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                      const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* xs, double* Ps,
+                      void* work, size_t work_bytes);
 
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in

@@ -6,7 +6,8 @@ the hypothesis forest itself lives in HBM (structure-of-arrays layers, see DESIG
 objects are what the host hands in (`Tracker.initiateTarget`) and what it gets back as *views* of
 device nodes (`Tracker.getTrackNodes()`, `Tracker.__targetList__`): plain Python objects whose
 `parent` / `trackHypotheses` links are materialised lazily from a snapshot of the device layers.
-The XML result export (`_storeNode`, `_storeNodeSparse`) is here; plotting and pykalman smoothing of the reference class are out of scope.
+The XML result export (`_storeNode`, `_storeNodeSparse`) is here, and `getSmoothTrack` (a Rauch-Tung-Striebel smoother on the device with
+the tracker's own model in place of the reference's pykalman call: pymht_amd/smoothing.py); plotting of the reference class is out of scope.
 """
 import copy
 import datetime
@@ -224,18 +225,51 @@ class Target:
             el.attrib[stateTag] = node.status
         return el
 
-    def _storeNode(self, simulationElement, radarPeriod, **kwargs):
-        """Every node of the chain root-of-time .. self (pyTarget.py:745-802).  The reference also writes a pykalman-smoothed copy
-        (`getSmoothTrack`); smoothing is outside this package: the <SmoothedStates> element is there and empty, which is what the
-        reference writes when its smoother reports failure."""
+    def getSmoothTrack(self, radarPeriod, model=None, device=0):
+        """pyTarget.py:580-609: (smoothed positions [L, 2], smoothed velocities [L, 2], ok) of the chain that ends in this node, from its
+        initial state and backtrackMeasurement().  A chain of fewer than two nodes returns its measurements, NaN velocities and False, as
+        the reference does.  The smoother is pymht_amd.smoothing (device, fixed model, no EM) -- not pykalman.  The model is the
+        tracker's for a node that came from one, else `model`, else models/pv as in the reference; many nodes at once:
+        Tracker.getSmoothTracks()."""
+        from . import smoothing
+        tracker = getattr(self, "_tracker", None)
+        if model is None:
+            if tracker is not None:
+                model = tracker._model_mod
+            else:
+                from .models import pv as model
+        return smoothing.smooth_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx)[0]
+
+    @staticmethod
+    def _smoothed_state_element(states, node, position, velocity, precision=2):
+        """One <S> of <SmoothedStates>, in the layout of _state_element: the node's time, smoothed position and velocity (north before east)."""
+        el = ET.SubElement(states, stateTag, attrib={timeTag: str(node.time)})
+        for tag, pair_values in ((positionTag, position), (velocityTag, velocity)):
+            pair = ET.SubElement(el, tag)
+            ET.SubElement(pair, northTag).text = str(round(pair_values[1], precision))
+            ET.SubElement(pair, eastTag).text = str(round(pair_values[0], precision))
+        return el
+
+    def _storeNode(self, simulationElement, radarPeriod, smooth=False, **kwargs):
+        """Every node of the chain root-of-time .. self (pyTarget.py:745-802).  The reference also writes a smoothed copy of the chain into
+        <SmoothedStates>; here that is opt-in: smooth=True runs getSmoothTrack for this node, smooth=(positions, velocities, ok) takes a
+        result computed elsewhere (Tracker._storeRun smooths a whole run in one device call).  By default, and where the smoother has
+        nothing to say (ok False: a chain of one node), the element is there and empty -- what the reference writes when its smoother
+        reports failure."""
         track, states = self._track_element(simulationElement, kwargs)
         chain = self.backtrackNodes()
         track.attrib[lengthTag] = str(len(chain))
-        ET.SubElement(track, smoothedstatesTag)
+        smoothed = ET.SubElement(track, smoothedstatesTag)
         for node in chain:
             el = self._state_element(states, node)
             if getattr(node, "S_inv", None) is not None:
                 ET.SubElement(el, inverseResidualCovarianceTag).text = np.array_str(node.S_inv, max_line_width=9999)
+        if smooth is not False and smooth is not None:
+            positions, velocities, ok = self.getSmoothTrack(radarPeriod) if smooth is True else smooth
+            if ok:
+                assert len(positions) == len(velocities) == len(chain)
+                for node, position, velocity in zip(chain, positions, velocities):
+                    self._smoothed_state_element(smoothed, node, position, velocity)
         return track
 
     def _storeNodeSparse(self, simulationElement, **kwargs):

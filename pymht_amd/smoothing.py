@@ -1,0 +1,142 @@
+"""Fixed-interval Rauch-Tung-Striebel smoothing of track histories on the device (`mht_smooth_tracks`, include/mht_amd.h seam (v)).
+
+The reference smooths one track at a time with pykalman (`Target.getSmoothTrack`, pyTarget.py:580-609: five EM iterations that
+re-estimate the noise covariances, then a smoother).  pykalman's EM step is not reproducible and nothing here depends on pykalman:
+the smoother below runs with the tracker's OWN model -- A = Phi(T), Q = Q(T), C_RADAR, R_RADAR(), float64 -- which is a documented
+difference from the reference.  The inputs are the reference's: the initial state of the chain and
+`backtrackMeasurement()` with None for a missed detection.
+
+All tracks of a call go to the device in ONE launch, one track per lane; there is no host fallback."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .device import Context
+
+
+def _check_model(model):
+    if getattr(model, "transition", None) == "ct":
+        raise NotImplementedError("smoothing: the transition of model %r depends on the state (Phi(T, w) per hypothesis, models/ct.py); the "
+                                  "linear Rauch-Tung-Striebel recursion does not apply and it is not run with Phi(T, 0) in its place"
+                                  % getattr(model, "__name__", model))
+    nx = int(np.asarray(model.C_RADAR).shape[1])
+    if nx not in (4, 6):
+        raise ValueError("smoothing: 4- or 6-state models (got %d states)" % nx)
+    return nx
+
+
+def _measurement_array(measurements):
+    """[L, 2] float64, NaN rows where the node has no measurement (None, or NaN already)."""
+    if isinstance(measurements, np.ndarray) and measurements.dtype != object:
+        return np.asarray(measurements, dtype=np.float64).reshape(-1, 2)
+    z = np.full((len(measurements), 2), np.nan)
+    for k, m in enumerate(measurements):
+        if m is not None:
+            z[k] = np.asarray(m, dtype=np.float64).reshape(2)
+    return z
+
+
+def smooth_tracks(model, radarPeriod, tracks, device=0, ctx=None, covariances=True):
+    """Smooth a batch of track histories.
+
+    model        a model module (pymht_amd.models.pv / .ca: Phi, Q, C_RADAR, R_RADAR); `transition == "ct"` raises NotImplementedError
+    tracks       list of (x_init [nx], P_init [nx, nx], measurements): one entry of `measurements` per node of the track -- a 2-vector, or
+                 None / a NaN row for a node without a radar measurement.  Entry 0 belongs to the node x_init is the state of and is
+                 not used (what `Target.backtrackMeasurement()` returns can be handed in as it is).
+    device, ctx  the GPU ordinal, or an existing pymht_amd.device.Context (a Tracker's) to run on
+    Returns per track (xs [L, nx], Ps [L, nx, nx]) float64, Ps None with covariances=False (means only: the cheaper kernel)."""
+    nx = _check_model(model)
+    n = len(tracks)
+    if n == 0:
+        return []
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _smooth(ctx, model, period, tracks, nx, covariances):
+    n, ns = len(tracks), nx * (nx + 1) // 2
+    zs = [_measurement_array(t[2]) for t in tracks]
+    lens = np.array([len(z) for z in zs], dtype=np.int32)
+    if lens.min() < 1:
+        raise ValueError("smoothing: a track without nodes")
+    # tracks of similar length side by side: a wavefront runs as long as the longest of its 64 tracks (stable: equal lengths keep their order)
+    order = np.argsort(-lens, kind="stable")
+    L_max = int(lens.max())
+    zp = np.zeros((n, L_max, 2))
+    hp = np.zeros((n, L_max), dtype=np.uint8)
+    x0 = np.empty((n, nx))
+    P0 = np.empty((n, nx * nx))
+    for j, t in enumerate(order):
+        z = zs[t]
+        has = ~np.isnan(z).any(axis=1)
+        has[0] = False
+        zp[j, :len(z)] = np.where(has[:, None], z, 0.0)
+        hp[j, :len(z)] = has
+        x0[j] = np.asarray(tracks[t][0], dtype=np.float64).reshape(nx)
+        P0[j] = np.asarray(tracks[t][1], dtype=np.float64).reshape(nx * nx)
+    dev = ctx.device
+    up = lambda a: torch.from_numpy(a).to(dev)
+    # track-minor on the device: [node][element][track]
+    z_d = up(zp).permute(1, 2, 0).contiguous()
+    h_d = up(hp).permute(1, 0).contiguous()
+    x_d = up(x0).permute(1, 0).contiguous()
+    P_d = up(P0).permute(1, 0).contiguous()
+    xs_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
+    Ps_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev) if covariances else None
+    lib = ctx.lib
+    need = int(lib.mht_smooth_work_bytes(nx, n, L_max))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in (model.Phi(period), model.Q(period), model.C_RADAR, model.R_RADAR())]
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    mx = _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 0, period)
+    lens_sorted = np.ascontiguousarray(lens[order])
+    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
+    _lib.check(lib.mht_smooth_tracks(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
+                                     z_d.data_ptr(), h_d.data_ptr(), xs_d.data_ptr(), Ps_d.data_ptr() if covariances else None,
+                                     work.data_ptr(), need), lib)
+    xs = xs_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
+    Ps = None
+    if covariances:      # packed upper triangle -> full matrices, still on the device
+        idx = torch.tensor([min(i, j) * nx - min(i, j) * (min(i, j) - 1) // 2 + abs(i - j) for i in range(nx) for j in range(nx)], device=dev)
+        Ps = Ps_d.index_select(1, idx).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
+    out = [None] * n
+    for j, t in enumerate(order):
+        L = int(lens[t])
+        out[t] = (xs[j, :L], Ps[j, :L] if covariances else None)
+    return out
+
+
+def chain_inputs(node, default_P0):
+    """What the reference hands to its smoother for the track that ends in `node`: the initial state of the chain and
+    backtrackMeasurement().  P_init is the first node's own covariance (the birth's), `default_P0` where it has none."""
+    chain = node.backtrackNodes()
+    first = chain[0]
+    P = first.P_0
+    return chain, (np.asarray(first.x_0, dtype=np.float64), np.asarray(default_P0 if P is None else P, dtype=np.float64),
+                   [c.measurement for c in chain])
+
+
+def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None):
+    """`Target.getSmoothTrack` for many track nodes in one device call: per node (positions [L, 2], velocities [L, 2], ok) as the
+    reference returns them.  A chain of fewer than two nodes has nothing to smooth: its measurements, NaN velocities and False."""
+    _check_model(model)
+    out, batch, where = [None] * len(nodes), [], []
+    for i, node in enumerate(nodes):
+        chain, inputs = chain_inputs(node, model.P0)
+        if len(chain) < 2:
+            pos = _measurement_array(inputs[2])
+            out[i] = (pos, np.full_like(pos, np.nan), False)
+        else:
+            batch.append(inputs)
+            where.append(i)
+    for i, (xs, _) in zip(where, smooth_tracks(model, radarPeriod, batch, device=device, ctx=ctx, covariances=False)):
+        out[i] = (xs[:, 0:2], xs[:, 2:4], True)
+    return out

@@ -970,6 +970,20 @@ class Tracker():
     def getTrackNodes(self):
         return self.__trackNodes__
 
+    def _smooth_nodes(self, nodes):
+        from . import smoothing
+        return smoothing.smooth_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx)
+
+    def getSmoothTracks(self, terminated=False):
+        """tracker.py: [track.getSmoothTrack(radarPeriod) for track in __trackNodes__] -- (positions, velocities, ok) per live track, with
+        terminated=True followed by the terminated ones (__terminatedTargets__) -- smoothed in ONE batched device call
+        (pymht_amd/smoothing.py: a Rauch-Tung-Striebel smoother with the tracker's own model, not pykalman).  A constant-turn tracker
+        raises NotImplementedError: its transition depends on the state."""
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        return self._smooth_nodes(nodes)
+
     def synchronize(self):
         """Wait for everything queued on the device and fold it (reports are folded lazily otherwise)."""
         self._drain()
@@ -1039,9 +1053,11 @@ class Tracker():
                             ("targetSizeLimit", self.targetSizeLimit), ("maxSpeedMS", self.maxSpeedMS)):
             ET.SubElement(settings, name).text = str(value)
 
-    def _storeRun(self, scenarioElement, preInitialized=True, **kwargs):
+    def _storeRun(self, scenarioElement, preInitialized=True, smooth=False, **kwargs):
         """One <Run>: the per-stage run times of every scan and one <Track> per live and per terminated target -- all states of
-        the selected hypothesis' chain (preInitialized=True; without the reference's pykalman-smoothed copy) or its first and last."""
+        the selected hypothesis' chain (preInitialized=True) or its first and last.  smooth=True also fills every track's
+        <SmoothedStates> (one <S> per node), all tracks of the run smoothed in ONE device call (getSmoothTracks); by default the
+        element stays empty."""
         import xml.etree.ElementTree as ET
         run = ET.SubElement(scenarioElement, xmltags.runTag)
         run.attrib[xmltags.iterationTag] = str(kwargs[xmltags.iterationTag] if xmltags.iterationTag in kwargs
@@ -1057,10 +1073,12 @@ class Tracker():
             ET.SubElement(runtime, str(stage), attrib={xmltags.meanTag: str(round(np.mean(v), prec)), xmltags.minTag: str(round(np.min(v), prec)),
                                                        xmltags.maxTag: str(round(np.max(v), prec))}
                           ).text = np.array_str(v, precision=prec, max_line_width=999999)
-        for nodes, extra in ((self.__trackNodes__, {}), (self.__terminatedTargets__, {xmltags.terminatedTag: True})):
+        groups = ((list(self.__trackNodes__), {}), (self.__terminatedTargets__, {xmltags.terminatedTag: True}))
+        smoothed = iter(self._smooth_nodes([node for nodes, _ in groups for node in nodes])) if (smooth and preInitialized) else None
+        for nodes, extra in groups:
             for node in nodes:
                 if preInitialized:
-                    node._storeNode(run, self.radarPeriod, **extra)
+                    node._storeNode(run, self.radarPeriod, smooth=(next(smoothed) if smoothed is not None else False), **extra)
                 else:
                     node._storeNodeSparse(run, **extra)
         return run

@@ -1,0 +1,200 @@
+"""What the device smoother (pymht_amd/smoothing.py, `mht_smooth_tracks`) costs next to the float64 NumPy recursion (tests/smooth_ref.py).
+
+  python tools/smooth_cost.py [--out FILE] [--reference-tracks N]
+      for 500 tracks x 200 nodes (models/pv) and 2 000 x 400 (models/ca), 80 % detections:
+        (a) smooth_tracks() end to end -- host packing, upload, kernel, copy back, unpacking -- with and without covariances (median of 5 behind a warm-up)
+        (b) the float64 NumPy reference, a loop over tracks and nodes; it is linear in the tracks, so it is timed on the first N (default 50) and scaled
+            (--reference-tracks 0: all of them, minutes)
+        accuracy of the 40-track batch of tests/test_smooth_gpu.py: e_dev / e_np against the np.longdouble truth
+        kernel time from ONE `rocprofv3 --kernel-trace --stats` run (a run of its own) next to the bytes the kernel has to move
+      Every step that touches the GPU is a child process under its own timeout; the first that fails ends the run.
+  (children: `time NAME`, `accuracy`, `trace`)"""
+import glob
+import json
+import os
+import re
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+
+PERIOD = 2.5
+SIZES = {"pv": (500, 200), "ca": (2000, 400)}
+HBM_PEAK = 8.0e12      # bytes / s, MI355X (HBM3E)
+
+
+def model_of(name):
+    from pymht_amd.models import pv, ca
+    return {"pv": pv, "ca": ca}[name]
+
+
+def batch(name):
+    import smooth_ref as sr
+    n, L = SIZES[name]
+    return sr.make_batch(model_of(name), PERIOD, [L] * n, seed=99, p_detect=0.8)
+
+
+def kernel_bytes(nx, n, L, cov=True):
+    """What one launch has to move: forward writes and backward reads the filtered state of every node but the last (nx + nx (nx + 1) / 2
+    doubles each way), reads z (2 doubles) and has_z (1 byte) per node, writes xs (nx) and Ps (nx (nx + 1) / 2) per node."""
+    ns = nx * (nx + 1) // 2
+    per_node = 2 * (nx + ns) * 8 + 2 * 8 + 1 + nx * 8 + (ns * 8 if cov else 0)
+    return n * L * per_node
+
+
+def child_time(name):
+    import torch
+    from pymht_amd.device import Context
+    from pymht_amd.smoothing import smooth_tracks
+    model, tracks = model_of(name), batch(name)
+    nx = int(np.asarray(model.C_RADAR).shape[1])
+    ctx = Context(0, nx=nx)
+    res = {}
+    for cov in (True, False):
+        smooth_tracks(model, PERIOD, tracks, ctx=ctx, covariances=cov)      # warm-up: code object load, allocator
+        ts = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            smooth_tracks(model, PERIOD, tracks, ctx=ctx, covariances=cov)      # (ends in a device-to-host copy: synchronous)
+            ts.append(time.perf_counter() - t0)
+        res["cov" if cov else "means"] = ts
+    ctx.close()
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def child_accuracy():
+    import smooth_ref as sr
+    from pymht_amd.smoothing import smooth_tracks
+    assert np.finfo(np.longdouble).eps < 1e-18
+    res = {}
+    for name in ("pv", "ca"):
+        model = model_of(name)
+        rng = np.random.default_rng(20240)
+        tracks = sr.make_batch(model, PERIOD, [int(v) for v in rng.integers(2, 401, 40)], seed=17, p_detect=0.8)      # (the batch of tests/test_smooth_gpu.py)
+        dev = smooth_tracks(model, PERIOD, tracks)
+        mats = sr.model_matrices(model, PERIOD)
+        e = np.zeros(4)
+        for (x0, P0, z), (xs, Ps) in zip(tracks, dev):
+            t, f = sr.rts(*mats, x0, P0, z, dtype=np.longdouble), sr.rts(*mats, x0, P0, z, dtype=np.float64)
+            e = np.maximum(e, [sr.err(xs, t["xs"]), sr.err(f["xs"], t["xs"]), sr.err(Ps, t["Ps"]), sr.err(f["Ps"], t["Ps"])])
+        res[name] = e.tolist()
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def child_trace():
+    from pymht_amd.smoothing import smooth_tracks
+    for name in ("pv", "ca"):
+        tracks = batch(name)
+        for cov in (True, False):
+            for _ in range(3):
+                smooth_tracks(model_of(name), PERIOD, tracks, covariances=cov)
+
+
+def run_child(args, timeout, prefix=()):
+    cmd = list(prefix) + [sys.executable, os.path.abspath(__file__)] + list(args)
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    if out.returncode != 0:
+        sys.stderr.write(out.stdout[-3000:] + out.stderr[-3000:])
+        raise SystemExit("step %s failed with exit status %d: stopping" % (" ".join(args), out.returncode))
+    for line in out.stdout.splitlines():
+        if line.startswith("RESULT "):
+            return json.loads(line[7:])
+    return None
+
+
+def kernel_times(prof_dir):
+    """Durations (us) per smoother kernel instance from the profiler's output: the kernel-trace CSV, or the rocpd database."""
+    times = {}
+    for path in glob.glob(os.path.join(prof_dir, "**", "*kernel_trace.csv"), recursive=True):
+        import csv
+        for row in csv.DictReader(open(path)):
+            if "smooth_rts_kernel" in row["Kernel_Name"]:
+                times.setdefault(row["Kernel_Name"], []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
+    if times:
+        return times
+    for path in glob.glob(os.path.join(prof_dir, "**", "*.db"), recursive=True):
+        import sqlite3
+        c = sqlite3.connect(path)
+        tabs = [r[0] for r in c.execute("select name from sqlite_master where type='table'")]
+        disp = next(t for t in tabs if t.startswith("rocpd_kernel_dispatch"))
+        sym = next(t for t in tabs if t.startswith("rocpd_info_kernel_symbol"))
+        names = {r[0]: r[1] for r in c.execute('select id, kernel_name from "%s"' % sym)}
+        for kid, s, e in c.execute('select kernel_id, start, end from "%s" order by start' % disp):
+            if "smooth_rts_kernel" in names[kid]:
+                times.setdefault(names[kid], []).append((e - s) / 1e3)
+    return times
+
+
+def main():
+    import smooth_ref as sr
+    out_path = os.path.join(os.environ.get("OUT_DIR", os.path.join(ROOT, "out")), "smooth_cost.txt")
+    n_ref = 50
+    argv = sys.argv[1:]
+    while argv:
+        a = argv.pop(0)
+        if a == "--out":
+            out_path = argv.pop(0)
+        elif a == "--reference-tracks":
+            n_ref = int(argv.pop(0))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    lines = ["tools/smooth_cost.py: the device Rauch-Tung-Striebel smoother (mht_smooth_tracks, one track per lane) against the float64 NumPy recursion",
+             "80 % detections, T = 2.5; device times are smooth_tracks() end to end (host packing, upload, kernel, copy back, unpacking), median of 5", ""]
+    emit = lambda s: (lines.append(s), print(s, flush=True))
+    acc = run_child(["accuracy"], 300)
+    for name in ("pv", "ca"):
+        e = acc[name]
+        emit("accuracy models/%s (40 tracks of 2-400 nodes, truth = np.longdouble): means e_dev %.3g e_np %.3g ratio %.2f | covariances e_dev %.3g e_np %.3g ratio %.2f  (required: <= 8)"
+             % (name, e[0], e[1], e[0] / e[1], e[2], e[3], e[2] / e[3]))
+    emit("")
+    dev_cov = {}
+    for name in ("pv", "ca"):
+        n, L = SIZES[name]
+        res = run_child(["time", name], 420)
+        tracks = batch(name)
+        mats = sr.model_matrices(model_of(name), PERIOD)
+        k = n if n_ref <= 0 else min(n_ref, n)
+        t0 = time.perf_counter()
+        for x0, P0, z in tracks[:k]:
+            sr.rts(*mats, x0, P0, z, dtype=np.float64)
+        t_np = (time.perf_counter() - t0) * n / k
+        dev_cov[name] = float(np.median(res["cov"]))
+        emit("%s  %5d tracks x %3d nodes: device with covariances %8.1f ms (%s), means only %8.1f ms | NumPy float64 %9.1f ms (%d tracks timed%s) | NumPy / device %.0f x"
+             % (name, n, L, 1e3 * np.median(res["cov"]), " ".join("%.1f" % (1e3 * t) for t in res["cov"]), 1e3 * np.median(res["means"]), 1e3 * t_np, k,
+                "" if k == n else ", scaled by %d / %d" % (n, k), t_np / np.median(res["cov"])))
+        if not np.median(res["cov"]) < t_np:
+            emit("  !! the device path is NOT faster than the NumPy loop at this size")
+    emit("")
+    prof_dir = os.path.join(os.path.dirname(os.path.abspath(out_path)), "smooth_prof")
+    run_child(["trace"], 600, prefix=["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", prof_dir, "-o", "smooth", "--"])
+    times = kernel_times(prof_dir)
+    if not times:
+        emit("kernel times: no smooth_rts_kernel in the profiler's output under %s" % os.path.relpath(prof_dir, ROOT))
+    for kname, v in sorted(times.items()):
+        inst = re.search(r"smooth_rts_kernel(?:<(\d), (true|false)>|ILi(\d)ELb([01])E)", kname)      # demangled or mangled
+        nx = int(inst.group(1) or inst.group(3))
+        cov = inst.group(2) == "true" or inst.group(4) == "1"
+        n, L = SIZES["pv" if nx == 4 else "ca"]
+        b = kernel_bytes(nx, n, L, cov)
+        t = float(np.median(v))
+        emit("kernel smooth_rts_kernel<%d, %s> %5d x %3d: %d launches, median %9.1f us (min %.1f, max %.1f); %.1f MB to move -> %.1f GB/s = %.2f %% of %.0f TB/s HBM peak"
+             % (nx, "covariances" if cov else "means only", n, L, len(v), t, min(v), max(v), b / 1e6, b / t / 1e3, 100 * b / (t * 1e-6) / HBM_PEAK, HBM_PEAK / 1e12))
+    emit("(a batch is n / 64 wavefronts of one serial chain per lane -- 8 wavefronts at 500 tracks, 32 at 2 000, on a device with 1 024 SIMDs: the kernel is bound by the")
+    emit(" latency of the chain, not by bandwidth; the rest of the end-to-end time is host packing, the copies and the unpacking)")
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "time":
+        child_time(sys.argv[2])
+    elif len(sys.argv) > 1 and sys.argv[1] == "accuracy":
+        child_accuracy()
+    elif len(sys.argv) > 1 and sys.argv[1] == "trace":
+        child_trace()
+    else:
+        main()
