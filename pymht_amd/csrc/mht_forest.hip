@@ -28,8 +28,49 @@
 #include <new>
 #include <stdlib.h>
 
-static void hp_print();      // (development, see forest_step_impl)
+// development: where the host time of a streamed scan goes (MHT_HOST_PROF=1, process-wide: per-section means on stderr when a forest is destroyed)
+struct HostProf { bool on = false; bool asked = false; double acc[16] = {}; long n = 0; double t_last = 0.0; };
+static HostProf g_hp;
+static inline double hp_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
+static inline void hp_begin() { if (!g_hp.asked) { g_hp.asked = true; const char* e = getenv("MHT_HOST_PROF"); g_hp.on = e && e[0] == '1'; } if (g_hp.on) { g_hp.t_last = hp_now(); g_hp.n += 1; } }
+static inline void hp_mark(int i) { if (g_hp.on) { const double t = hp_now(); g_hp.acc[i] += t - g_hp.t_last; g_hp.t_last = t; } }
+static void hp_print() {
+    if (!g_hp.on || !g_hp.n) return;
+    static const char* nm[16] = {"checks", "stage (memcpy, kernel, events)", "begin_step + deferred init", "fill grow args", "grow launch", "events behind grow", "fill blp", "blp launch", "initiator args / defer", "end_step", "initiate_impl (ride)", "", "", "", "", ""};
+    fprintf(stderr, "[mht host prof] %ld scans, us per scan:", g_hp.n);
+    for (int i = 0; i < 11; ++i) fprintf(stderr, " %s %.2f |", nm[i], g_hp.acc[i] / g_hp.n);
+    fprintf(stderr, "\n");
+    g_hp = HostProf();
+}
+
+// Development switches (environment; INTEGRATION.md lists them): "1" switches on, "0" switches off, anything else leaves the default.
+static bool env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : dflt; }
+static long long env_int(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
+
 namespace mht {
+
+// The forest's development switches, read from the environment when the forest is created (Forest::sw).  None of them changes a result.
+struct Switches {
+    bool debug = getenv("MHT_GROW_DEBUG") != nullptr;             // set (to anything, as mht_gate.hip reads it): phase stamps (with -DMHT_GROW_STAMPS), forced storage policies
+    bool ct_spill = env_flag("MHT_CT_SPILL", false);              // testing: fgrow_ct_kernel keeps every target's hit masks in the global spill block
+    bool grid_by_hint = env_flag("MHT_BLP_GRID_HINT", true);      // 0: the ILP launch sized by the target count alone, as until round 5
+    bool force_hbm = env_flag("MHT_BLP_FORCE_HBM", false);        // testing: every ILP through the HBM storage policy
+    bool no_enum = env_flag("MHT_BLP_NO_ENUM", false);            // testing: no exact search for small clusters (branch and bound instead)
+    bool no_reduce = env_flag("MHT_BLP_NO_REDUCE", false);        // (BlpArgs::no_reduce)
+    bool teams = !env_flag("MHT_BLP_NO_TEAMS", false);            // branch-and-bound teams (mht_blp.hip); 1: giant ILP clusters by one workgroup
+    bool adm_fuse = env_flag("MHT_ADM_FUSE", true);               // 0: admission in a launch of its own behind every scan
+    bool no_uf = env_flag("MHT_NO_UF", false);                    // 1: the clustering kernel on every scan (Forest::uf_ok)
+    bool no_overlap = env_flag("MHT_NO_OVERLAP", false);          // 1: no any-order grow launches (Forest::ovl_ok)
+    // (rocprofv3 --pmc runs ONE kernel at a time across all queues, in the order the queues happen to be served: a launch that waits for a
+    // launch on another queue never sees it start.  Under counter collection the initiator stays on the ctx stream.)
+    bool serial_prof = env_flag("ROCPROF_COUNTER_COLLECTION", false);      // no launch may wait for a launch on another queue (the staging goes by event too)
+    bool init_side_q = env_flag("MHT_INIT_QUEUE", true) && !serial_prof;   // 0: the streamed scans' initiator any-order on the ctx stream instead of the side stream
+    bool rep_flag_ok = env_flag("MHT_REPORT_FLAG", true);         // 0: the streamed report handed over by an event instead of the words in its pinned block
+    bool stage_stream = env_flag("MHT_STAGE_STREAM", true);       // 0: scan staging on the ctx stream
+    bool blp_stamps = env_flag("MHT_BLP_STAMPS", false);          // with debug: the ILP launch's phase stamps
+    bool ovl_stamps = env_flag("MHT_OVL_STAMPS", false);          // (FDyn::stamp_end)
+    bool ovl_force = env_flag("MHT_OVL_FORCE", false);            // any-order launches with the debug stamps on
+};
 
 constexpr int MAXR = 16;
 // Layers of the node ring beyond the N-scan window.  A leaf's chain back to its root spans N + 2 layers; the streaming drop-in path folds
@@ -41,8 +82,6 @@ constexpr int EV_POOL = 64;
 constexpr int Z_RING = 8;           // pinned staging buffers of mht_forest_step_host (a consumer guard every Z_GUARD scans, see step_host_impl)
 constexpr int Z_GUARD = 4;
 constexpr int BIRTH_CAP = 256;      // candidates of the device initiator per scan that the report can hold
-
-struct LayerView { const double* x; const double* cnllr; const int32_t* parent; const int32_t* meas; const uint8_t* flags; const int32_t* cov; const float* P; };
 
 // The scan report goes to the host from inside the kernel that completes it: the workgroup copies header, used-measurement
 // mask, birth records and the target rows from the device block into pinned, device-mapped host memory with 16-byte stores
@@ -297,6 +336,7 @@ struct Arena {
 struct Forest {
     mht_forest_config cfg;
     mht_model model;
+    Switches sw;                      // as the environment had them when the forest was created (forest_create_impl)
     int Tcap, Ncap, Mpad, R, PD, AW, n_mnodes, Ecap, SegCap;
     VTab vt = {};                     // covariances by value, shared by all targets and scans (mht_vtab.h): the CURRENT generation
     // Value ids are never recycled within a generation.  When the table is three quarters full the live leaves are re-keyed into the
@@ -330,7 +370,7 @@ struct Forest {
     int32_t *edge_t, *edge_m, *t_label, *t_cluster, *cl_ptr, *cl_members, *multi_list, *single_list, *cl_counts, *big_list;
     int32_t* cl_owner;      // [Tcap] cluster-sharded step: device of every multi-target cluster (LPT by column count)
     // clustering inside the grow launch (mht_kernels.h: FDyn::uf_epoch): owner word per measurement node, parent word per target; uf_ok:
-    // the ILP launch's workgroups can derive the cluster tables themselves (MHT_NO_UF=1: the clustering kernel on every scan, as before)
+    // the ILP launch's workgroups can derive the cluster tables themselves (Switches::no_uf: the clustering kernel on every scan, as before)
     unsigned long long* uf_owner = nullptr; unsigned long long* uf_parent2[2] = {nullptr, nullptr}; bool uf_ok = false; int uf_scans = 0;
     // overlap of a scan's ILP launch with the next scan's grow launch (mht_kernels.h: TGT_REC_*, FDyn::ovl): the per-target records, the
     // scan whose ILP launch published them, the total its workgroups will have counted off (FCounts::blp_done), launches made any-order
@@ -339,14 +379,14 @@ struct Forest {
     int init_flag_scan = 0;      // last scan whose initiator posts FCounts::init_flag
     unsigned long long* rec0 = nullptr; int pub_scan = 0; unsigned long long blp_done_total = 0; bool ovl_ok = true; int ovl_launches = 0;
     int32_t* cl_gtab = nullptr; bool cluster_big = false;      // the clustering tables in HBM when they do not fit LDS (mht_cluster.hip: cluster_big_kernel)
-    int32_t* team_list; TeamState* team_state2[2]; TeamResult* team_res; bool teams = true;      // (team_state2: by scan parity)      // branch-and-bound teams (mht_blp.hip); MHT_BLP_NO_TEAMS=1: off
+    int32_t* team_list; TeamState* team_state2[2]; TeamResult* team_res;      // (team_state2: by scan parity)      // branch-and-bound teams (mht_blp.hip; Switches::teams)
     double* u; int32_t* usage; int32_t* mark;
     int32_t *best_h, *bb_ch, *bb_best, *bb_last_idx; double *best_rc, *bb_cost, *bb_uused, *bb_last_rc, *bb_rest, *bb_min;
     int32_t *sel, *cl_status, *cl_iters, *cl_nodes, *cl_time; unsigned long long* grow_dbg; int32_t* commit_log; double* bb_snap; int32_t* bb_busy; int bb_snap_rows = 0;
     int32_t *t_status, *t_jdrop, *t_count, *t_firstsurv, *new_index, *near; double* t_score;
     int32_t *w_root_scan, *w_root_node; double* w_root_cnllr; uint8_t* w_root_f32;
     FCounts* cnt;
-    bool rep_by_flag[2] = {false, false}; unsigned long long rep_tag[2] = {0, 0}; bool rep_flag_ok = true;      // the host block's report is complete when its done words carry rep_tag (no event)
+    bool rep_by_flag[2] = {false, false}; unsigned long long rep_tag[2] = {0, 0};      // the host block's report is complete when its done words carry rep_tag (no event)
     char* report_dev2[2]; char* report_host; size_t report_bytes, rec_off, used_off, birth_off, done_off;      // device report blocks by scan parity
     // no copy engine on the scan's path: a small kernel pulls the scan out of the pinned ring, the kernel that completes the report
     // pushes it into pinned host memory (publish_report)
@@ -361,10 +401,10 @@ struct Forest {
     int host_block_scan[2] = {0, 0};      // scan whose report the host block holds (or is receiving: rep_ev of the block), 0 = none
     hipStream_t stage_stream = nullptr; bool stage_stream_tried = false;
     // the streamed scans' initiator launches go onto the SIDE stream, each one behind the staging kernel of the scan after its own (it is
-    // queued by the next call, or by whoever needs its births first: launch_deferred_init): see forest_step_impl
-    bool init_ev_lazy = false; bool init_deferred = false; bool init_side_q = true; bool serial_prof = false;      // serial_prof: no launch may wait for a launch on another queue (the staging goes by event too)
+    // queued by the next call, or by whoever needs its births first: launch_deferred_init): see step_initiator
+    bool init_ev_lazy = false; bool init_deferred = false;
     InitArgs init_def_args; const DevStatus* init_def_status = nullptr; unsigned long long init_def_ztag = 0;
-    hipEvent_t grow_ev = nullptr, init_ev = nullptr; bool init_ev_pending = false; bool init_side = false;      // MHT_INIT_SIDE=1: the initiator as a launch of its own on the side stream (default: inside the cluster launch)
+    hipEvent_t init_ev = nullptr; bool init_ev_pending = false;
     float* z_dev; float* z_host; hipEvent_t z_ev[Z_RING] = {}; bool z_used[Z_RING] = {}; int z_slot = 0;
     hipEvent_t z_guard_ev[2] = {nullptr, nullptr}; long long z_count = 0; int z_guard_due = -1;      // consumer guard of the staging ring (step_host_impl)
     // small staging for add_targets / leaves / chain
@@ -381,18 +421,14 @@ struct Forest {
     // the target-side commit of the last launched scan has not run yet: it rides in the next grow_kernel, or is launched
     // on its own by whoever needs the committed state first (report, births, exports)
     bool commit_pending = false; CommitArgs pending = {}; CommitDyn pending_dyn = {};
-    bool ct_spill = false;         // testing: MHT_CT_SPILL=1 at creation -- fgrow_ct_kernel keeps every target's hit masks in the global spill block
-    bool grid_by_hint = true;      // MHT_BLP_GRID_HINT=0 at creation: the ILP launch sized by the target count alone, as until round 5
     // streaming drop-in path: the admission of what the scan's initiator gave birth to is pending WITH the commit -- both ride in
     // workgroup 0 of the next scan's grow launch (fgrow_adm_kernel), or run as post_scan_kernel when somebody needs the state first
-    bool adm_pending = false; AddArgs adm = {}; bool adm_fuse = true;      // MHT_ADM_FUSE=0: admission in a launch of its own behind every scan
+    bool adm_pending = false; AddArgs adm = {};
     bool shard_open = false; int shard_plan_s = 0, shard_plan_W = 0, shard_M = 0, shard_xn = 0;      // cluster-sharded step between _begin and _end
     long long blp_time_limit = 0;   // wall-clock budget per ILP in 10 ns ticks, 0 = none (mht_forest_set_blp_time_limit)
     float prune_thr = 0.f;       // similar-state pruning (mht_similar.hip): threshold in metres, 0 = off (mht_forest_set_prune_similar)
     int in_groups = 0;           // mht_group_create snapshots the ILP argument blocks of its members: settings behind them are frozen while > 0
     int similar_ran_scan = -100; // last scan prune_similar_kernel ran on: its children may carry F_DEAD when they are leaves (FDyn::maybe_dead)
-    bool force_hbm = false;      // testing: MHT_BLP_FORCE_HBM=1 at creation runs every ILP through the HBM storage policy
-    bool no_enum = false;        // testing: MHT_BLP_NO_ENUM=1 at creation: no exact search for small clusters (branch and bound instead)
     // grid sizing without reports: the commit publishes {scan, targets alive} in a host-mapped word; with the births the host issued
     // since that scan this bounds the current target count (targets only disappear otherwise)
     unsigned long long* hint_host = nullptr; unsigned long long* hint_dev = nullptr;
@@ -434,7 +470,6 @@ struct Forest {
         }
         return ub;
     }
-    bool debug = false;      // MHT_GROW_DEBUG set at creation: phase stamps (with -DMHT_GROW_STAMPS), forced storage policies
     bool timing = false; int timed_steps = 0; int ev_slot = 0; hipEvent_t (*evp)[5] = nullptr;   // pool of EV_POOL event sets
 
     void layout(Arena& ar) {
@@ -528,7 +563,6 @@ void forest_destroy(mht_ctx* ctx) {
     for (auto& cs : f->chain_slots) { if (cs.ev) (void)hipEventDestroy(cs.ev); if (cs.host) (void)hipHostFree(cs.host); }
     f->stage_dev.release();
     if (f->stage_stream) (void)hipStreamDestroy(f->stage_stream);
-    if (f->grow_ev) (void)hipEventDestroy(f->grow_ev);
     if (f->init_ev) (void)hipEventDestroy(f->init_ev);
     if (f->evp) {
         for (int k = 0; k < EV_POOL; ++k) for (int i = 0; i < 5; ++i) (void)hipEventDestroy(f->evp[k][i]);
@@ -624,8 +658,6 @@ static int flush_publish(mht_ctx* ctx, Forest* f) {
     return MHT_OK;
 }
 
-static LayerView view_of(const mht_nodes& l) { return LayerView{l.x, l.cnllr, l.parent, l.meas, l.flags, l.cov, l.P}; }
-
 }  // namespace mht
 
 using namespace mht;
@@ -667,7 +699,7 @@ static int forest_create_impl(mht_ctx* ctx, const mht_model* model, const mht_fo
         // the headline size with half of the ships reporting, and a generation must last R + 2 scans.  1.9 GB per generation at 8 M ids:
         // sized for the 288 GB part)
         if (flags & MHT_FOREST_AIS) { vc = 16ll * f->Ncap; if (vc < (1 << 20)) vc = 1 << 20; if (vc > (1 << 23)) vc = 1 << 23; }
-        if (const char* e = getenv("MHT_VTAB_CAP")) vc = atoll(e);
+        vc = env_int("MHT_VTAB_CAP", vc);
         f->vt.vcap = (int)vc;
         unsigned hs = 1;
         while (hs < 4u * (unsigned)vc) hs <<= 1;
@@ -680,31 +712,17 @@ static int forest_create_impl(mht_ctx* ctx, const mht_model* model, const mht_fo
         long long bc = usable * 3 / 4 / f->Tcap;
         if (bc > 256) bc = 256;
         if (bc < 16) bc = 0;          // (tiny pools: everything through the overflow counters)
-        if (const char* e = getenv("MHT_BLOCK_CAP")) bc = atoi(e) < bc ? atoi(e) : bc;      // development: 0 = no static blocks
+        { const long long e = env_int("MHT_BLOCK_CAP", bc); if (e < bc) bc = e; }      // development: 0 = no static blocks
         f->block_cap = (int)bc;
         f->over_base = f->Tcap * f->block_cap;
         f->region_cap = (int)((usable - f->over_base) / FG_REGIONS);
         f->root_base = f->over_base + FG_REGIONS * f->region_cap;
     }
-    f->debug = getenv("MHT_GROW_DEBUG") != nullptr;
-    { const char* e = getenv("MHT_CT_SPILL"); f->ct_spill = e && e[0] == '1'; }
-    { const char* e = getenv("MHT_BLP_GRID_HINT"); f->grid_by_hint = !(e && e[0] == '0'); }
-    { const char* e = getenv("MHT_BLP_FORCE_HBM"); f->force_hbm = e && e[0] == '1'; }
-    { const char* e = getenv("MHT_BLP_NO_ENUM"); f->no_enum = e && e[0] == '1'; }
-    { const char* e = getenv("MHT_BLP_NO_TEAMS"); f->teams = !(e && e[0] == '1'); }
-    { const char* e = getenv("MHT_ADM_FUSE"); f->adm_fuse = !(e && e[0] == '0'); }
-    { const char* e = getenv("MHT_INIT_SIDE"); f->init_side = (e && e[0] == '1'); }      // (measured: the two event operations per scan cost the host more than the 6 us save the device -- 91 against 76 us per streamed scan)
-    MHT_HIP_CHECK(hipEventCreateWithFlags(&f->grow_ev, hipEventDisableTiming));
     MHT_HIP_CHECK(hipEventCreateWithFlags(&f->init_ev, hipEventDisableTiming));
     f->pds = f->PD <= 8 ? 8 : 16;
     f->cluster_big = !cluster_fits_lds(f->Tcap, f->n_mnodes);
-    { const char* e = getenv("MHT_NO_UF"); f->uf_ok = !(e && e[0] == '1') && blp_uf_fits(f->Tcap, f->n_mnodes); }
-    { const char* e = getenv("MHT_NO_OVERLAP"); f->ovl_ok = !(e && e[0] == '1'); }
-    { const char* e = getenv("MHT_INIT_QUEUE"); f->init_side_q = !(e && e[0] == '0'); }
-    { const char* e = getenv("MHT_REPORT_FLAG"); f->rep_flag_ok = !(e && e[0] == '0'); }
-    // (rocprofv3 --pmc runs ONE kernel at a time across all queues, in the order the queues happen to be served: a launch that waits for a
-    // launch on another queue never sees it start.  Under counter collection the initiator stays on the ctx stream.)
-    { const char* e = getenv("ROCPROF_COUNTER_COLLECTION"); if (e && e[0] == '1') { f->init_side_q = false; f->serial_prof = true; } }
+    f->uf_ok = !f->sw.no_uf && blp_uf_fits(f->Tcap, f->n_mnodes);
+    f->ovl_ok = !f->sw.no_overlap;
     if (flags & MHT_FOREST_CT) {       // the transition is rebuilt per hypothesis from its turn rate (pymht_amd/models/ct.py): T = A[4][5]
         if (NX != 6 || (flags & MHT_FOREST_AIS)) { delete f; set_error("mht_forest_create_ex: MHT_FOREST_CT needs the six-state build of the library and no MHT_FOREST_AIS"); return MHT_E_INVALID; }
         f->ct = true;
@@ -869,6 +887,19 @@ extern "C" int mht_forest_read_mmsi_nodes(mht_ctx* ctx, int32_t scan, int32_t n,
     return MHT_OK;
 }
 
+// where an admission behind the last launched scan puts its roots: that scan's layer, the table the next scan runs on
+static void fill_add(const Forest* f, AddArgs& a) {
+    a.thr = f->cfg.merge_threshold;
+    const int nb = (f->scan + 1) & 1;
+    a.layer = f->layer[f->scan % f->R];
+    a.tab = f->tab[nb]; a.vidx = nb;
+    a.path = f->path[f->scan & 1]; a.apath = f->apath[f->scan & 1]; a.PD = f->pds;
+    a.cnt = f->cnt; a.scan = f->scan; a.Nwin = f->cfg.n_scan; a.Tcap = f->Tcap;
+    a.near = f->near;
+    fill_model_only(a.model, &f->model); a.vt = f->vt; a.root_base = f->root_base; a.ct_Proot = f->ct ? f->ct_Proot[f->scan % f->R] : nullptr;
+    if (f->ais) { a.mmsi = f->l_mmsi[f->scan % f->R]; a.hmmsi = f->l_hmmsi[f->scan % f->R]; }
+}
+
 extern "C" int mht_forest_add_targets_dev(mht_ctx* ctx, int32_t n, const double* x0, const float* P0, const uint8_t* flags,
                                           const double* pd, const int32_t* meas, int32_t check_neighbours,
                                           uint8_t* accepted, int32_t* ids) {
@@ -883,15 +914,8 @@ extern "C" int mht_forest_add_targets_dev(mht_ctx* ctx, int32_t n, const double*
     if (!fuse) { const int rc = flush_commit(ctx, f); if (rc) return rc; }
     AddArgs a = {};
     a.n = n; a.x0 = x0; a.pd = pd; a.P0 = P0; a.meas = meas; a.flags = flags; a.ids = ids; a.accepted = accepted;
-    a.check = check_neighbours; a.thr = f->cfg.merge_threshold;
-    const int nb = (f->scan + 1) & 1;
-    a.layer = f->layer[f->scan % f->R];
-    a.tab = f->tab[nb]; a.vidx = nb;
-    a.path = f->path[f->scan & 1]; a.apath = f->apath[f->scan & 1]; a.PD = f->pds;
-    a.cnt = f->cnt; a.scan = f->scan; a.Nwin = f->cfg.n_scan; a.Tcap = f->Tcap;
-    a.near = f->near;
-    fill_model_only(a.model, &f->model); a.vt = f->vt; a.root_base = f->root_base; a.ct_Proot = f->ct ? f->ct_Proot[f->scan % f->R] : nullptr;
-    if (f->ais) { a.mmsi = f->l_mmsi[f->scan % f->R]; a.hmmsi = f->l_hmmsi[f->scan % f->R]; }
+    a.check = check_neighbours;
+    fill_add(f, a);
     MHT_REQUIRE(n <= f->Tcap, "mht_forest_add_targets: %d candidates exceed max_targets", n);
     if (fuse) { f->adm = a; f->adm_pending = true; const int rc = flush_commit(ctx, f); if (rc) return rc; }
     else
@@ -988,7 +1012,7 @@ static void fill_fgrow(const Forest* f, int s, bool fused, FGrowArgs& g) {
     g.status = f->status2 + (s & 1); g.prev_status = f->status2 + ((s - 1) & 1); g.sticky_overflow = &f->cnt->overflow;
     g.rec0 = f->rec0; g.new_index = f->new_index; g.ni_flag = &f->cnt->ni_flag;
     g.uf_owner = f->uf_owner; g.uf_parent = f->uf_parent2[s & 1];      // (by scan parity: the grow launch of scan s + 1 links while the ILP launch of scan s still reads)
-     g.uf_team_state = f->teams ? f->team_state2[s & 1] : nullptr;
+     g.uf_team_state = f->sw.teams ? f->team_state2[s & 1] : nullptr;
     if (f->ct) { g.ct.on = 1; g.ct.gains = f->ct_gains; g.ct.xbar = f->ct_xbar; g.ct.zhat = f->ct_zhat; g.ct.hw_spill = f->ct_hw_spill; }
     if (f->ais) {
         g.ais.nf = f->ais_nf; g.ais.off = f->ais_off; g.ais.rec = f->ais_rec; g.ais.half = f->ais_half;
@@ -1004,10 +1028,10 @@ static void fill_cluster(const Forest* f, int s, ClusterArgs& c) {
     c.alloc_reset = f->alloc2[s & 1];
     c.edges_in = f->edges; c.edge_count = f->edge_count; c.ticket_reset = nullptr; c.seg_cap = f->SegCap;
     c.status = f->status2 + (s & 1); c.status_other = f->status2 + ((s - 1) & 1);
-    c.dbg = f->debug ? reinterpret_cast<int32_t*>(f->grow_dbg) + 16 : nullptr;
+    c.dbg = f->sw.debug ? reinterpret_cast<int32_t*>(f->grow_dbg) + 16 : nullptr;
     c.t_label = f->t_label; c.t_cluster = f->t_cluster; c.cl_ptr = f->cl_ptr; c.cl_members = f->cl_members;
     c.multi_list = f->multi_list; c.single_list = f->single_list; c.counts = f->cl_counts;
-    c.team_list = f->teams ? f->team_list : nullptr; c.team_state = f->teams ? f->team_state2[s & 1] : nullptr;
+    c.team_list = f->sw.teams ? f->team_list : nullptr; c.team_state = f->sw.teams ? f->team_state2[s & 1] : nullptr;
     c.gtab = f->cl_gtab;
     cluster_prepare(c);
 }
@@ -1017,21 +1041,21 @@ static void fill_blp(const Forest* f, int s, BlpArgs& b) {
     const int cb = s & 1;
     const mht_nodes& out = f->layer[s % f->R];
     b.cl_ptr = f->cl_ptr; b.cl_members = f->cl_members; b.multi_list = f->multi_list; b.single_list = f->single_list;
-    b.team_list = f->teams ? f->team_list : nullptr; b.team_state = f->team_state2[s & 1]; b.team_res = f->team_res;
+    b.team_list = f->sw.teams ? f->team_list : nullptr; b.team_state = f->team_state2[s & 1]; b.team_res = f->team_res;
     b.counts = f->cl_counts; b.big_count = f->cl_counts + 4; b.big_list = f->big_list; b.tchild = f->tchild; b.tcend = f->tcend; b.cost = f->cost2[s & 1]; b.cnllr = out.cnllr;
     b.path = f->path[s & 1]; b.cap = f->Ncap; b.PD = f->ais ? f->pds : f->PD; b.pds = f->pds;      // (AIS forest: every entry of a record can be a row)
     b.u = f->u; b.usage = f->usage; b.mark = f->mark; b.n_mnodes = f->n_mnodes;
-    if (f->teams) { b.tm_sm = (size_t)f->n_mnodes; b.tm_ss = (size_t)2 * f->Tcap + 2; }
+    if (f->sw.teams) { b.tm_sm = (size_t)f->n_mnodes; b.tm_ss = (size_t)2 * f->Tcap + 2; }
     b.bb_snap = f->bb_snap; b.bb_busy = f->bb_busy; b.bb_snap_rows = f->bb_snap_rows;
     b.best_h = f->best_h; b.best_rc = f->best_rc; b.bb_ch = f->bb_ch; b.bb_best = f->bb_best; b.bb_cost = f->bb_cost;
     b.bb_uused = f->bb_uused; b.bb_last_rc = f->bb_last_rc; b.bb_last_idx = f->bb_last_idx; b.bb_rest = f->bb_rest; b.bb_min = f->bb_min;
     b.sel = f->sel; b.cl_status = f->cl_status; b.cl_iters = f->cl_iters; b.cl_nodes = f->cl_nodes; b.cl_time = f->cl_time;
     b.max_iter = f->cfg.blp_max_iter; b.node_limit = f->cfg.blp_node_limit; b.status = f->status2 + (s & 1);
-    b.force_hbm = f->force_hbm ? 1 : 0;
-    b.no_enum = f->no_enum ? 1 : 0;
+    b.force_hbm = f->sw.force_hbm ? 1 : 0;
+    b.no_enum = f->sw.no_enum ? 1 : 0;
     b.skip_dead = f->prune_thr > 0.f ? 1 : 0;
     b.time_limit = f->blp_time_limit;
-    { static int nr = -1; if (nr < 0) { const char* e = getenv("MHT_BLP_NO_REDUCE"); nr = (e && e[0] == '1') ? 1 : 0; } b.no_reduce = nr; }
+    b.no_reduce = f->sw.no_reduce ? 1 : 0;
     b.x = out.x; b.flags = out.flags; b.t_root_cnllr = f->tab[cb].root_cnllr; b.t_root_f32 = f->tab[cb].root_f32;
     b.t_depth = f->tab[cb].depth; b.t_window = f->tab[cb].window;
     b.apath = f->apath[s & 1]; b.R = f->R; b.kc = s % f->R;
@@ -1046,7 +1070,7 @@ static void fill_blp(const Forest* f, int s, BlpArgs& b) {
     // (clusters from the grow launch's union-find: switched on per scan by the caller, b.uf_epoch = scan number)
     b.uf_parent = f->uf_parent2[s & 1]; b.nT_dev = &f->cnt->nT; b.uf_cap = f->Tcap; b.status_other = f->status2 + ((s - 1) & 1); b.alloc_reset = f->alloc2[s & 1];
     b.t_cluster = f->t_cluster;
-    { static int bs = -1; if (bs < 0) { const char* e = getenv("MHT_BLP_STAMPS"); bs = (e && e[0] == '1') ? 1 : 0; } b.dbg = (bs && f->debug) ? f->grow_dbg : nullptr; }
+    b.dbg = (f->sw.blp_stamps && f->sw.debug) ? f->grow_dbg : nullptr;
 }
 
 // similar-state pruning of scan s's children (between the cluster and the ILP kernel; tracker.py:230-231)
@@ -1122,7 +1146,13 @@ __global__ __launch_bounds__(256) void vt_rebuild_kernel(const RebuildArgs a) {
     }
 }
 
-struct StepPlan { int s; bool fused; int n_ub; int W; bool rebuilt; };
+struct StepPlan {                 // what the host knows about the scan being stepped: forest_begin_step fills the first row, the entry points the rest
+    int s; bool fused; int n_ub; int W; bool rebuilt;
+    bool ais = false;             // the scan carries AIS messages (step_begin)
+    bool use_uf = false;          // clusters from the grow launch's union-find, no clustering launch (forest_streams_uf)
+    bool grow_ovl = false;        // this scan's grow launch took the previous scan's results target by target (FDyn::ovl)
+    hipEvent_t* ev = nullptr;     // per-stage timing: this scan's row of the event pool
+};
 // Switches the forest to the other generation of its value table in front of scan s (the newest layer is s - 1).
 static int vt_switch_generation(mht_ctx* ctx, Forest* f, int s) {
     { const int rc = flush_commit(ctx, f); if (rc) return rc; }      // (the leaf ranges of the committed table are what is re-keyed)
@@ -1198,9 +1228,7 @@ static void forest_end_step(Forest* f, const StepPlan& pl, int M) {
     f->L_ub = f->Ncap;        // unknown until the report is fetched
 }
 
-}  // namespace mht
 
-namespace mht {
 void initiator_scan_args(mht_initiator* in, const float* z, int M, const unsigned long long* used, double now, InitArgs& a);
 void initiator_born_ptrs(const mht_initiator* in, const double** x, const float** P, const uint8_t** fl, const double** pd, const int32_t** meas,
                          const int32_t** n, int* cap, mht_ctx** ctx);
@@ -1210,9 +1238,15 @@ bool initiator_lift(const mht_initiator* in, double* x, float* P);
 void initiator_ais_ptrs(mht_initiator* in, const AisInitMsg** msgs, unsigned char** used);
 }
 
-// will a step with this initiator take the union-find path with the initiator as a launch of its own (forest_step_impl: use_uf)?
+// ---- the stages of a scan: mht_forest_step / mht_forest_scan, the cluster-sharded step and mht_group_step are made of these ------------
+// A failure behind forest_begin_step kills the forest (the scan counter has moved: the ring and the parities the later steps derive their
+// buffers from are no longer what the device holds).
+#define MHT_STEP_CHECK(expr) do { const int rc_ = (expr); if (rc_) { f->dead = true; return rc_; } } while (0)
+#define MHT_STEP_HIP(expr) do { if ((expr) != hipSuccess) { f->dead = true; set_error("mht_forest_step: %s failed", #expr); return MHT_E_HIP; } } while (0)
+
+// will a step with this initiator take the union-find path with the initiator as a launch of its own (StepPlan::use_uf)?
 static bool forest_streams_uf(const Forest* f, const mht_initiator* init) {
-    return f->uf_ok && !(f->prune_thr > 0.f) && (!init || (f->adm_fuse && !f->ais && !f->timing && !f->init_side));
+    return f->uf_ok && !(f->prune_thr > 0.f) && (!init || (f->sw.adm_fuse && !f->ais && !f->timing));
 }
 // a reader of the staged scan other than the grow launch / the initiator's launch is about to be queued on the ctx stream: the event wait
 // the step skipped (step_host_impl)
@@ -1224,19 +1258,29 @@ static int flush_z_wait(mht_ctx* ctx, Forest* f) {
     }
     return MHT_OK;
 }
-// development: where the host time of a streamed scan goes (MHT_HOST_PROF=1: per-section means on stderr when the forest is destroyed)
-struct HostProf { bool on = false; bool asked = false; double acc[16] = {}; long n = 0; double t_last = 0.0; };
-static HostProf g_hp;
-static inline double hp_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
-static inline void hp_begin() { if (!g_hp.asked) { g_hp.asked = true; const char* e = getenv("MHT_HOST_PROF"); g_hp.on = e && e[0] == '1'; } if (g_hp.on) { g_hp.t_last = hp_now(); g_hp.n += 1; } }
-static inline void hp_mark(int i) { if (g_hp.on) { const double t = hp_now(); g_hp.acc[i] += t - g_hp.t_last; g_hp.t_last = t; } }
-static void hp_print() {
-    if (!g_hp.on || !g_hp.n) return;
-    static const char* nm[16] = {"checks", "stage (memcpy, kernel, events)", "begin_step + deferred init", "fill grow args", "grow launch", "events behind grow", "fill blp", "blp launch", "initiator args / defer", "end_step", "initiate_impl (ride)", "", "", "", "", ""};
-    fprintf(stderr, "[mht host prof] %ld scans, us per scan:", g_hp.n);
-    for (int i = 0; i < 11; ++i) fprintf(stderr, " %s %.2f |", nm[i], g_hp.acc[i] / g_hp.n);
-    fprintf(stderr, "\n");
-    g_hp = HostProf();
+// Opens scan s = pl.s.  AIS arming: the scan carries the armed messages, as measurement nodes M .. M + nA - 1 (pl.W counts them); their fused
+// children are made from the leaves of the COMMITTED table, so the pending commit runs first, as a launch of its own (flush_ct: the same for
+// a constant-turn forest's prepass).  A refused step must not leave the messages armed: the tracker stays alive after MHT_E_INVALID, and the
+// next accepted scan -- maybe one without messages -- would consume them with this scan's time steps.
+static int step_begin(mht_ctx* ctx, Forest* f, const float* z, int M, const char* who, bool flush_ct, bool carries_admission, StepPlan& pl) {
+    const bool ais = f->ais && f->ais_armed;
+    int rc = MHT_OK;
+    if (ais && M + f->ais_nA > f->Mpad) {
+        set_error("%s: %d radar measurements + %d AIS messages exceed max_meas=%d (rounded up to %d measurement nodes per scan)", who, M, f->ais_nA, f->cfg.max_meas, f->Mpad);
+        rc = MHT_E_INVALID;
+    }
+    if (!rc && (ais || flush_ct)) rc = flush_commit(ctx, f);
+    if (!rc) rc = forest_begin_step(ctx, f, z, M, who, pl, carries_admission && !ais);
+    if (rc) { f->ais_armed = false; return rc; }
+    pl.ais = ais;
+    if (ais) pl.W = (M + f->ais_nA + 63) / 64;
+    return MHT_OK;
+}
+// what every grow launch is told about its scan (the one-sector launch adds its overlap, flag and debug fields)
+static void fdyn_base(const Forest* f, const float* z, int M, const StepPlan& pl, FDyn& d) {
+    d.z = z; d.M = M; d.W = pl.W; d.c_scan = f->pending_dyn.scan; d.c_M = f->pending_dyn.M; d.c_W = f->pending_dyn.W;
+    d.ais_on = pl.ais ? 1 : 0;
+    d.maybe_dead = (f->similar_ran_scan == pl.s - 1);
 }
 // AIS forest: forest_ais_kernel (mht_ais.hip) over the leaves of the committed table, in front of scan s's grow launch; disarms the messages
 static int forest_ais_prepass(mht_ctx* ctx, Forest* f, int s, int n_ub, const float* z, int M) {
@@ -1255,8 +1299,10 @@ static int forest_ais_prepass(mht_ctx* ctx, Forest* f, int s, int n_ub, const fl
     f->ais_armed = false;
     return rc;
 }
-// constant-turn forest: forest_ct_kernel (mht_ais.hip) over the leaves of the committed table, in front of scan s's grow launch
-static int forest_ct_prepass(mht_ctx* ctx, Forest* f, int s, int n_ub, bool fused = false) {
+// constant-turn forest: forest_ct_kernel (mht_ais.hip) over the leaves in front of scan s's grow launch -- of the uncommitted table when the
+// previous scan's commit is still pending (fused: it then rides in the grow launch like everywhere else: one launch and two boundaries less
+// per scan), else of the committed one
+static int forest_ct_prepass(mht_ctx* ctx, Forest* f, int s, int n_ub, bool fused) {
     CtForestArgs ca = {};
     const int li = (s - 1) % f->R, lp = (s - 2 + f->R) % f->R;
     const mht_nodes& in = f->layer[li];
@@ -1269,202 +1315,201 @@ static int forest_ct_prepass(mht_ctx* ctx, Forest* f, int s, int n_ub, bool fuse
     ca.gains = f->ct_gains; ca.xbar = f->ct_xbar; ca.zhat = f->ct_zhat;
     return launch_forest_ct(ctx, ca, n_ub);
 }
-// init != null (mht_forest_scan): the scan's step 7 rides in the cluster launch (cluster_init_kernel)
+// ---- 0: AIS-aided children of every leaf (tracker.py:394-396, :417-552), only on scans that carry messages; 0': a constant-turn forest's
+// leaves' own transitions, predictions, gains and children covariances
+static int step_prepasses(mht_ctx* ctx, Forest* f, const StepPlan& pl, const float* z, int M, bool ct_fused) {
+    if (pl.ais) { const int rc = forest_ais_prepass(ctx, f, pl.s, pl.n_ub, z, M); if (rc) return rc; }
+    return f->ct ? forest_ct_prepass(ctx, f, pl.s, pl.n_ub, ct_fused) : MHT_OK;
+}
+// similar-state pruning of scan s's children, between clustering and the ILPs (tracker.py:230-231); the launch goes to ctx's stream
+static int step_prune_similar(mht_ctx* ctx, Forest* f, int s) {
+    if (!(f->prune_thr > 0.f)) return MHT_OK;
+    SimilarArgs sa;
+    fill_similar(f, s, sa);
+    const int rc = launch_prune_similar(ctx, sa, f->nT_ub_step);
+    f->similar_ran_scan = s;
+    return rc;
+}
+// workgroups of an ILP launch sized by the scan's target bound alone: one per `div` targets and a few to spare
+static int blp_full_grid(const Forest* f, int div) {
+    const int grid = f->nT_ub_step / div + 8;
+    return grid > 1024 ? 1024 : grid;
+}
+// Clusters from the union-find: a workgroup per multi-target cluster and a wavefront per single-target one is all the launch needs
+// (the loops of blp_body take more of either) -- every further workgroup runs the prologue for nothing and loads the fabric the
+// others work through: at the headline size 160-192 workgroups instead of 258 are 1 us per scan (profiles/r05_merge_ab.txt, "ILP grid").
+// The commit leaves the last scan's counts in the host-mapped hint block; a scan with a team-sized cluster keeps the workgroups
+// without a cluster (they are the teams).
+// (a wall-clock budget per cluster is set: the width of a team -- and with it which non-proven incumbent a budget-limited search returns -- follows
+// the grid, so the grid stays the full one and does not depend on when the host happened to read the hint word)
+static int blp_hint_grid(const Forest* f, int s, bool use_uf, int grid) {
+    if (!(use_uf && f->hint_host && f->sw.grid_by_hint && !(f->blp_time_limit > 0 && f->nT_ub_step >= TEAM_MIN_K))) return grid;
+    const unsigned long long hh = reinterpret_cast<volatile unsigned long long*>(f->hint_host)[2];
+    const int h_scan = (int)(hh >> 48), h_multi = (int)((hh >> 32) & 0xffffu), h_single = (int)((hh >> 8) & 0xffffffu), h_team = (int)(hh & 0xffu);
+    const int age = (s - h_scan) & 0xffff;
+    // (a host that queues scans far ahead of the device -- the replay -- sees counts that are hundreds of scans old: a stationary
+    // stream's statistics; what the launch is too small for, it loops over)
+    if (hh != 0ull && age >= 1 && age <= 8192 && h_team == 0) {
+        int gh = h_multi + h_multi / 8 + (h_single + 3) / 4 + 8;      // (an eighth more multi-target clusters than last time; the rest loops)
+        if (gh < 32) gh = 32;
+        // (the hint may be thousands of scans old and targets may have been added since: a workgroup's tables hold 4 multi-target
+        // clusters and 32 single-target ones -- UfPersist::own / single -- so THIS scan's target bound keeps the grid from below)
+        const int g_min = f->nT_ub_step / 8 + 1;
+        if (gh < g_min) gh = g_min;
+        if (gh < grid) grid = gh;
+    }
+    return grid;
+}
+// The initiator's arguments for scan s.  used_words: the scan's committed used-measurement mask (the initiator runs behind the commit:
+// post_scan_kernel); null: it reads the bytes scan s's grow launch wrote (packed and cleared by that scan's commit later).
+static void scan_init_args(const Forest* f, mht_initiator* in, const float* z, int M, const unsigned long long* used_words, double now, int s, InitArgs& ia) {
+    initiator_scan_args(in, z, M, used_words, now, ia);
+    if (!used_words) ia.used_b = f->used_bytes[s & 1];
+    ia.bhint = f->bhint_dev; ia.forest_overflow = &f->cnt->overflow; ia.scan_no = s;
+}
+// what the device initiator of a scan gives birth to (its arrays on the device, their capacity)
+struct BornPtrs { const double* x; const float* P; const uint8_t* fl; const double* pd; const int32_t* meas; const int32_t* n; int cap; };
+// can this initiator start tracks in ctx's forest?  (the six-state build takes the 4-state initiator's births only lifted into its state space)
+static int initiator_check(const mht_ctx* ctx, const mht_initiator* in, const char* who, BornPtrs& b) {
+    double lx[2]; float lP[4];
+    MHT_REQUIRE(NX == 4 || initiator_lift(in, lx, lP), "%s: the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv); "
+                "this is the %d-state build: call mht_initiator_set_lift first", who, NX);
+    mht_ctx* ictx;
+    initiator_born_ptrs(in, &b.x, &b.P, &b.fl, &b.pd, &b.meas, &b.n, &b.cap, &ictx);
+    MHT_REQUIRE(ictx == ctx, "%s: the initiator belongs to another context", who);
+    MHT_REQUIRE(b.cap <= BIRTH_CAP, "%s: the initiator's max_born=%d exceeds the report's %d", who, b.cap, BIRTH_CAP);
+    return MHT_OK;
+}
+
+// ---- 1: grow every leaf (tracker.py:207-209) ---------------------------------------------------------------
+// No memsets between scans: the used-measurement bytes are cleared by the commit, the other parity's status word, the edge
+// and child counters and the cluster counters by the cluster kernel.
+static int step_grow(mht_ctx* ctx, Forest* f, StepPlan& pl, const float* z, int M) {
+    hp_mark(2);
+    hipStream_t st = ctx->stream;
+    FGrowArgs g;
+    fill_fgrow(f, pl.s, pl.fused, g);
+    FDyn d = {};
+    fdyn_base(f, z, M, pl, d);
+    d.dbg = f->sw.debug ? f->grow_dbg : nullptr;
+    d.uf_epoch = pl.use_uf ? 2u * (unsigned)pl.s : 0u;      // (2 x scan: the odd value in between is the epoch of a union-find that had to be redone, mht_fgrow.hip)
+    // the previous scan's ILP launch published per-target records and its commit rides here: this launch takes what it needs of that
+    // launch target by target -- and may start while it is still running
+    d.ovl = (pl.fused && f->pub_scan == pl.s - 1 && f->pending_dyn.scan == pl.s - 1) ? 1 : 0;
+    d.c_wait = f->blp_done_total;
+    pl.grow_ovl = d.ovl != 0;
+    d.ct_spill = f->sw.ct_spill ? 1 : 0;
+    d.z_flag = &f->cnt->z_flag; d.z_tag = f->z_tag_step;
+    d.stamp_end = f->sw.ovl_stamps ? 1 : 0;
+    const bool adm = f->adm_pending && pl.fused;      // (flush_commit clears both)
+    // (the streamed path's launch -- commit, admission of the initiator's births, report push -- overlaps too when that initiator posts its flag)
+    const bool adm_ovl = adm && f->init_flag_scan == pl.s - 1;
+    d.adm_wait = adm_ovl ? 1 : 0;
+    const bool any_order = d.ovl && f->ovl_ok && (!adm || adm_ovl) && (!f->pub_deferred || adm_ovl) && !pl.ais && !f->timing && (!f->sw.debug || f->sw.ovl_force);
+    if (any_order) f->ovl_launches += 1;
+    hp_mark(3);
+    MHT_STEP_CHECK(launch_deferred_init(ctx, f));      // (the previous scan's initiator: behind this scan's staging kernel, in front of this launch)
+    if (adm && f->init_ev_pending) {
+        if (adm_ovl && f->init_ev_lazy) { f->init_ev_pending = false; f->init_ev_lazy = false; }      // (the admission waits for the initiator's flag itself)
+        else MHT_STEP_CHECK(wait_init_ev(ctx, f));
+    }
+    const bool pub_flag = f->pub_deferred && adm && f->pub_args.dst && f->sw.rep_flag_ok && !f->sw.serial_prof;      // (fgrow_adm_kernel pushes it: the host polls the pushing workgroups' words)
+    if (pub_flag) {
+        f->pub_args.done = reinterpret_cast<unsigned long long*>(f->report_host_dev[f->pub_slot] + f->done_off);
+        f->pub_args.tag = (unsigned long long)(pl.s - 1) | (1ull << 40);
+    } else { f->pub_args.done = nullptr; f->pub_args.tag = 0; }
+    MHT_STEP_CHECK(launch_fgrow(ctx, g, d, pl.n_ub, pl.fused ? &f->pending : nullptr, f->pub_deferred ? &f->pub_args : nullptr, adm ? &f->adm : nullptr, any_order));
+    hp_mark(4);
+    f->adm_pending = false;
+    if (f->z_guard_due >= 0) { MHT_STEP_HIP(hipEventRecord(f->z_guard_ev[f->z_guard_due], st)); f->z_guard_due = -1; }      // (step_host_impl: consumer guard of the staging ring)
+    if (f->pub_deferred) {      // the previous scan's report went along: the host waits for this launch
+        if (pub_flag) { f->rep_by_flag[f->pub_slot] = true; f->rep_tag[f->pub_slot] = f->pub_args.tag; }
+        else { MHT_STEP_HIP(hipEventRecord(f->rep_ev[f->pub_slot], st)); f->rep_by_flag[f->pub_slot] = false; }
+        f->rep_started[f->pub_slot] = true;
+        f->host_block_scan[f->pub_slot] = pl.s - 1;
+        f->pub_deferred = false;
+    }
+    f->commit_pending = false;
+    hp_mark(5);
+    return MHT_OK;
+}
+// ---- 2: cluster (tracker.py:218-221) ---------------------------------------------------------------------------
+// Clusters without a clustering launch (mht_kernels.h: FDyn::uf_epoch): the target workgroups of the grow launch hook their targets
+// into a union-find, the workgroups of the ILP launch derive the cluster tables from it.  Similar-state pruning works on the
+// clustering kernel's list of lone targets between the two launches; the streamed path's initiator rides in the cluster launch
+// (init != null: the scan's step 7 as cluster_init_kernel).
+static int step_cluster(mht_ctx* ctx, Forest* f, const StepPlan& pl, const float* z, int M, mht_initiator* init, double now) {
+    if (pl.use_uf) { f->uf_scans += 1; return MHT_OK; }
+    ClusterArgs c;
+    fill_cluster(f, pl.s, c);
+    if (!init || f->cluster_big) return launch_cluster(ctx, c);      // (no initiator, or the HBM-table clustering kernel: the initiator then runs behind the scan, in post_scan_kernel)
+    InitArgs ia;
+    scan_init_args(f, init, z, M, nullptr, now, pl.s, ia);
+    MHT_STEP_CHECK(launch_cluster(ctx, c, &ia, &f->cnt->overflow));
+    f->init_ran_scan = pl.s;
+    return MHT_OK;
+}
+// step 7 (tracker.py:264-278) of a scan clustered by the union-find needs the scan and the used-measurement bytes of the grow launch, nothing
+// of the ILPs: one workgroup, launched any-order behind the ILP launch -- it runs next to the ILPs' tail -- or deferred onto the side stream
+// (launch_deferred_init); what it gives birth to is admitted in the next scan's grow launch (which waits for both)
+static int step_initiator(mht_ctx* ctx, Forest* f, const StepPlan& pl, const float* z, int M, mht_initiator* init, double now) {
+    InitArgs ia;
+    scan_init_args(f, init, z, M, nullptr, now, pl.s, ia);
+    if (f->sw.init_side_q && f->stage_stream && f->z_tag_step) {
+        f->init_deferred = true; f->init_def_args = ia; f->init_def_status = f->status2 + (pl.s & 1); f->init_def_ztag = f->z_tag_step;
+        f->init_ev_pending = true; f->init_ev_lazy = true;      // (whoever needs the births without the flag: init_ev, recorded then)
+    } else
+    hipExtLaunchKernelGGL(initiator_side_kernel, dim3(1), dim3(INIT_THREADS), 0, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, ia,
+                          static_cast<const DevStatus*>(f->status2 + (pl.s & 1)), static_cast<const int32_t*>(&f->cnt->overflow), &f->cnt->init_flag,
+                          static_cast<const unsigned long long*>(f->z_tag_step ? &f->cnt->z_flag : nullptr), f->z_tag_step,
+                          static_cast<unsigned long long*>(nullptr), static_cast<const unsigned long long*>(nullptr), static_cast<unsigned long long*>(nullptr));      // (no ticket: one workgroup)
+    MHT_STEP_HIP(hipGetLastError());
+    f->init_ran_scan = pl.s; f->init_flag_scan = pl.s;
+    return MHT_OK;
+}
+// ---- 3: global hypothesis per cluster (tracker.py:225-237) + per-target termination / prune decision ---------------
+static int step_solve(mht_ctx* ctx, Forest* f, const StepPlan& pl, const float* z, int M, mht_initiator* init, double now) {
+    BlpArgs b;
+    fill_blp(f, pl.s, b);
+    b.uf_epoch = pl.use_uf ? 2u * (unsigned)pl.s : 0u;
+    b.ni_flag = &f->cnt->ni_flag; b.uf_ovl = pl.grow_ovl ? 1 : 0;
+    const int grid = blp_hint_grid(f, pl.s, pl.use_uf, blp_full_grid(f, 2));
+    if (pl.use_uf) {
+        b.rec0 = f->rec0; b.blp_done = &f->cnt->blp_done; b.pub_scan = (unsigned)pl.s; b.begun = &f->cnt->ilp_begun;
+        b.pub_ub = f->nT_ub_step < 1 ? 1 : (f->nT_ub_step < f->Tcap ? f->nT_ub_step : f->Tcap);      // (the next grow launch has one target workgroup at least)
+    }
+    hp_mark(6);
+    MHT_STEP_CHECK(launch_blp(ctx, b, grid));
+    hp_mark(7);
+    if (pl.use_uf) { f->pub_scan = pl.s; f->blp_done_total += (unsigned long long)grid; }
+    if (pl.use_uf && init) MHT_STEP_CHECK(step_initiator(ctx, f, pl, z, M, init, now));
+    hp_mark(8);
+    return MHT_OK;
+}
+// One scan of one forest on its own stream.  init != null (mht_forest_scan): the scan's step 7 rides along (step_cluster, step_initiator).
 static int forest_step_impl(mht_ctx* ctx, const float* z, int32_t M, mht_initiator* init, double now) {
     MHT_REQUIRE(ctx && ctx->forest, "mht_forest_step: no forest");
     Forest* f = ctx->forest;
     MHT_HIP_CHECK(hipSetDevice(ctx->device));
-    const bool ais = f->ais && f->ais_armed;
-    // (a refused step must not leave the messages armed: the tracker stays alive after MHT_E_INVALID, and the next accepted scan -- maybe
-    // one without messages -- would consume them with this scan's time steps)
-    if (ais && !(M + f->ais_nA <= f->Mpad)) f->ais_armed = false;
-    if (ais) {      // the fused children are made from the leaves of the COMMITTED table, in front of the grow launch
-        MHT_REQUIRE(M + f->ais_nA <= f->Mpad, "mht_forest_step: %d radar measurements + %d AIS messages exceed max_meas=%d (rounded up to %d measurement nodes per scan)",
-                    M, f->ais_nA, f->cfg.max_meas, f->Mpad);
-        const int rc = flush_commit(ctx, f);
-        if (rc) return rc;
-    }
-    // (constant-turn forest: forest_ct_kernel walks the leaves in front of the grow launch -- of the uncommitted table when the previous scan's
-    // commit is still pending (it then rides in the grow launch like everywhere else: one launch and two boundaries less per scan), MHT_CT_FLUSH=1:
-    // of the committed table, as until the end of round 5)
-    static int ct_flush = -1; if (ct_flush < 0) { const char* e = getenv("MHT_CT_FLUSH"); ct_flush = (e && e[0] == '1') ? 1 : 0; }
-    if (f->ct && ct_flush) {
-        const int rc = flush_commit(ctx, f);
-        if (rc) return rc;
-    }
     StepPlan pl;
-    { const int rc = forest_begin_step(ctx, f, z, M, "mht_forest_step", pl, !ais); if (rc) { f->ais_armed = false; return rc; } }
-    if (ais) pl.W = (M + f->ais_nA + 63) / 64;      // (the messages are measurement nodes M .. M + nA - 1 of this scan)
+    { const int rc = step_begin(ctx, f, z, M, "mht_forest_step", false, true, pl); if (rc) return rc; }
+    pl.use_uf = forest_streams_uf(f, init);
     hipStream_t st = ctx->stream;
-    hipEvent_t* ev = nullptr;
-    if (f->timing) {
-        ev = f->evp[f->ev_slot];
-        f->ev_slot = (f->ev_slot + 1) % EV_POOL;
-    }
-    // No memsets between scans: the used-measurement bytes are cleared by the commit, the other parity's status word, the edge
-    // and child counters and the cluster counters by the cluster kernel.
-#define MHT_STEP_CHECK(expr) do { const int rc_ = (expr); if (rc_) { f->dead = true; return rc_; } } while (0)
-#define MHT_STEP_HIP(expr) do { if ((expr) != hipSuccess) { f->dead = true; set_error("mht_forest_step: %s failed", #expr); return MHT_E_HIP; } } while (0)
-    if (f->timing) MHT_STEP_HIP(hipEventRecord(ev[0], st));
-    // ---- 0: AIS-aided children of every leaf (tracker.py:394-396, :417-552), only on scans that carry messages ----------------
-    if (ais) MHT_STEP_CHECK(forest_ais_prepass(ctx, f, pl.s, pl.n_ub, z, M));
-    if (f->ct) MHT_STEP_CHECK(forest_ct_prepass(ctx, f, pl.s, pl.n_ub, pl.fused));      // ---- 0': the leaves' own transitions, predictions, gains and children covariances
-    // Clusters without a clustering launch (mht_kernels.h: FDyn::uf_epoch): the target workgroups of the grow launch hook their targets
-    // into a union-find, the workgroups of the ILP launch derive the cluster tables from it.  Similar-state pruning works on the
-    // clustering kernel's list of lone targets between the two launches; the streamed path's initiator rides in the cluster launch.
-    // (streamed path: the scan's initiator then runs as a launch of its own NEXT to the ILP launch -- launched any-order behind it)
-    const bool use_uf = forest_streams_uf(f, init);
-    bool grow_ovl = false;      // this scan's grow launch took the previous scan's results target by target (FDyn::ovl)
-    // ---- 1: grow every leaf (tracker.py:207-209) ---------------------------------------------------------------
-    {
-        hp_mark(2);
-        FGrowArgs g;
-        fill_fgrow(f, pl.s, pl.fused, g);
-        FDyn d = {};
-        d.z = z; d.M = M; d.W = pl.W; d.c_scan = f->pending_dyn.scan; d.c_M = f->pending_dyn.M; d.c_W = f->pending_dyn.W;
-        d.ais_on = ais ? 1 : 0;
-        d.maybe_dead = (f->similar_ran_scan == pl.s - 1);
-        d.dbg = f->debug ? f->grow_dbg : nullptr;
-        d.uf_epoch = use_uf ? 2u * (unsigned)pl.s : 0u;      // (2 x scan: the odd value in between is the epoch of a union-find that had to be redone, mht_fgrow.hip)
-        // the previous scan's ILP launch published per-target records and its commit rides here: this launch takes what it needs of that
-        // launch target by target -- and may start while it is still running
-        d.ovl = (pl.fused && f->pub_scan == pl.s - 1 && f->pending_dyn.scan == pl.s - 1) ? 1 : 0;
-        d.c_wait = f->blp_done_total;
-        grow_ovl = d.ovl != 0;
-        d.ct_spill = f->ct_spill ? 1 : 0;
-        d.z_flag = &f->cnt->z_flag; d.z_tag = f->z_tag_step;
-        { static int os = -1; if (os < 0) { const char* e = getenv("MHT_OVL_STAMPS"); os = (e && e[0] == '1') ? 1 : 0; } d.stamp_end = os; }
-        const bool adm = f->adm_pending && pl.fused;      // (flush_commit clears both)
-        static int ovl_force = -1; if (ovl_force < 0) { const char* e = getenv("MHT_OVL_FORCE"); ovl_force = (e && e[0] == '1') ? 1 : 0; }      // (development: any-order launches with the debug stamps on)
-        // (the streamed path's launch -- commit, admission of the initiator's births, report push -- overlaps too when that initiator posts its flag)
-        const bool adm_ovl = adm && f->init_flag_scan == pl.s - 1;
-        d.adm_wait = adm_ovl ? 1 : 0;
-        const bool any_order = d.ovl && f->ovl_ok && (!adm || adm_ovl) && (!f->pub_deferred || adm_ovl) && !ais && !f->timing && (!f->debug || ovl_force);
-        if (any_order) f->ovl_launches += 1;
-        hp_mark(3);
-        MHT_STEP_CHECK(launch_deferred_init(ctx, f));      // (the previous scan's initiator: behind this scan's staging kernel, in front of this launch)
-        if (adm && f->init_ev_pending) {
-            if (adm_ovl && f->init_ev_lazy) { f->init_ev_pending = false; f->init_ev_lazy = false; }      // (the admission waits for the initiator's flag itself)
-            else MHT_STEP_CHECK(wait_init_ev(ctx, f));
-        }
-        const bool pub_flag = f->pub_deferred && adm && f->pub_args.dst && f->rep_flag_ok && !f->serial_prof;      // (fgrow_adm_kernel pushes it: the host polls the pushing workgroups' words)
-        if (pub_flag) {
-            f->pub_args.done = reinterpret_cast<unsigned long long*>(f->report_host_dev[f->pub_slot] + f->done_off);
-            f->pub_args.tag = (unsigned long long)(pl.s - 1) | (1ull << 40);
-        } else { f->pub_args.done = nullptr; f->pub_args.tag = 0; }
-        MHT_STEP_CHECK(launch_fgrow(ctx, g, d, pl.n_ub, pl.fused ? &f->pending : nullptr, f->pub_deferred ? &f->pub_args : nullptr, adm ? &f->adm : nullptr, any_order));
-        hp_mark(4);
-        f->adm_pending = false;
-        if (f->z_guard_due >= 0) { MHT_STEP_HIP(hipEventRecord(f->z_guard_ev[f->z_guard_due], st)); f->z_guard_due = -1; }      // (step_host_impl: consumer guard of the staging ring)
-        if (f->pub_deferred) {      // the previous scan's report went along: the host waits for this launch
-            if (pub_flag) { f->rep_by_flag[f->pub_slot] = true; f->rep_tag[f->pub_slot] = f->pub_args.tag; }
-            else { MHT_STEP_HIP(hipEventRecord(f->rep_ev[f->pub_slot], st)); f->rep_by_flag[f->pub_slot] = false; }
-            f->rep_started[f->pub_slot] = true;
-            f->host_block_scan[f->pub_slot] = pl.s - 1;
-            f->pub_deferred = false;
-        }
-    }
-    f->commit_pending = false;
-    hp_mark(5);
-    if (f->timing) MHT_STEP_HIP(hipEventRecord(ev[1], st));
-    // ---- 2: cluster (tracker.py:218-221) ---------------------------------------------------------------------------
-    if (use_uf) f->uf_scans += 1;
-    else {
-        ClusterArgs c;
-        fill_cluster(f, pl.s, c);
-        if (init && !f->cluster_big) {
-            InitArgs ia;
-            initiator_scan_args(init, z, M, nullptr, now, ia);
-            ia.used_b = f->used_bytes[pl.s & 1];      // (written by this scan's grow launch, packed and cleared by its commit later)
-            ia.bhint = f->bhint_dev; ia.forest_overflow = &f->cnt->overflow; ia.scan_no = pl.s;
-            if (f->init_side && f->stage_stream && f->adm_fuse && !f->ais && !f->timing) {
-                MHT_STEP_HIP(hipEventRecord(f->grow_ev, st));                       // behind the grow launch
-                MHT_STEP_HIP(hipStreamWaitEvent(f->stage_stream, f->grow_ev, 0));
-                hipLaunchKernelGGL(initiator_side_kernel, dim3(1), dim3(INIT_THREADS), 0, f->stage_stream, ia, static_cast<const DevStatus*>(c.status), static_cast<const int32_t*>(&f->cnt->overflow));
-                MHT_STEP_HIP(hipGetLastError());
-                MHT_STEP_HIP(hipEventRecord(f->init_ev, f->stage_stream));
-                f->init_ev_pending = true;
-                MHT_STEP_CHECK(launch_cluster(ctx, c));
-            } else {
-                MHT_STEP_CHECK(launch_cluster(ctx, c, &ia, &f->cnt->overflow));
-            }
-            f->init_ran_scan = pl.s;
-        } else {      // (no initiator, or the HBM-table clustering kernel: the initiator then runs behind the scan, in post_scan_kernel)
-            MHT_STEP_CHECK(launch_cluster(ctx, c));
-        }
-    }
-    if (f->timing) MHT_STEP_HIP(hipEventRecord(ev[2], st));
-    // ---- 3: global hypothesis per cluster (tracker.py:225-237) + per-target termination / prune decision ---------------
-    if (f->prune_thr > 0.f) {
-        SimilarArgs sa;
-        fill_similar(f, pl.s, sa);
-        MHT_STEP_CHECK(launch_prune_similar(ctx, sa, f->nT_ub_step));
-        f->similar_ran_scan = pl.s;
-    }
-    {
-        BlpArgs b;
-        fill_blp(f, pl.s, b);
-        b.uf_epoch = use_uf ? 2u * (unsigned)pl.s : 0u;
-        b.ni_flag = &f->cnt->ni_flag; b.uf_ovl = grow_ovl ? 1 : 0;
-        int grid = f->nT_ub_step / 2 + 8;
-        if (grid > 1024) grid = 1024;
-        // Clusters from the union-find: a workgroup per multi-target cluster and a wavefront per single-target one is all the launch needs
-        // (the loops of blp_body take more of either) -- every further workgroup runs the prologue for nothing and loads the fabric the
-        // others work through: at the headline size 160-192 workgroups instead of 258 are 1 us per scan (profiles/r05_merge_ab.txt, "ILP grid").
-        // The commit leaves the last scan's counts in the host-mapped hint block; a scan with a team-sized cluster keeps the workgroups
-        // without a cluster (they are the teams).
-        // (a wall-clock budget per cluster is set: the width of a team -- and with it which non-proven incumbent a budget-limited search returns -- follows
-        // the grid, so the grid stays the full one and does not depend on when the host happened to read the hint word)
-        if (use_uf && f->hint_host && f->grid_by_hint && !(f->blp_time_limit > 0 && f->nT_ub_step >= TEAM_MIN_K)) {
-            const unsigned long long hh = reinterpret_cast<volatile unsigned long long*>(f->hint_host)[2];
-            const int h_scan = (int)(hh >> 48), h_multi = (int)((hh >> 32) & 0xffffu), h_single = (int)((hh >> 8) & 0xffffffu), h_team = (int)(hh & 0xffu);
-            const int age = (pl.s - h_scan) & 0xffff;
-            // (a host that queues scans far ahead of the device -- the replay -- sees counts that are hundreds of scans old: a stationary
-            // stream's statistics; what the launch is too small for, it loops over)
-            if (hh != 0ull && age >= 1 && age <= 8192 && h_team == 0) {
-                int gh = h_multi + h_multi / 8 + (h_single + 3) / 4 + 8;      // (an eighth more multi-target clusters than last time; the rest loops)
-                if (gh < 32) gh = 32;
-                // (the hint may be thousands of scans old and targets may have been added since: a workgroup's tables hold 4 multi-target
-                // clusters and 32 single-target ones -- UfPersist::own / single -- so THIS scan's target bound keeps the grid from below)
-                const int g_min = f->nT_ub_step / 8 + 1;
-                if (gh < g_min) gh = g_min;
-                if (gh < grid) grid = gh;
-            }
-        }
-        if (use_uf) {
-            b.rec0 = f->rec0; b.blp_done = &f->cnt->blp_done; b.pub_scan = (unsigned)pl.s; b.begun = &f->cnt->ilp_begun;
-            b.pub_ub = f->nT_ub_step < 1 ? 1 : (f->nT_ub_step < f->Tcap ? f->nT_ub_step : f->Tcap);      // (the next grow launch has one target workgroup at least)
-        }
-        hp_mark(6);
-        MHT_STEP_CHECK(launch_blp(ctx, b, grid));
-        hp_mark(7);
-        if (use_uf) { f->pub_scan = pl.s; f->blp_done_total += (unsigned long long)grid; }
-        if (use_uf && init) {
-            // step 7 (tracker.py:264-278) needs the scan and the used-measurement bytes of the grow launch, nothing of the ILPs: one
-            // workgroup, launched any-order behind the ILP launch -- it runs next to the ILPs' tail; what it gives birth to is admitted in
-            // the next scan's grow launch (which waits for both)
-            InitArgs ia;
-            initiator_scan_args(init, z, M, nullptr, now, ia);
-            ia.used_b = f->used_bytes[pl.s & 1];
-            ia.bhint = f->bhint_dev; ia.forest_overflow = &f->cnt->overflow; ia.scan_no = pl.s;
-            if (f->init_side_q && f->stage_stream && f->z_tag_step) {      // (launch_deferred_init)
-                f->init_deferred = true; f->init_def_args = ia; f->init_def_status = f->status2 + (pl.s & 1); f->init_def_ztag = f->z_tag_step;
-                f->init_ev_pending = true; f->init_ev_lazy = true;      // (whoever needs the births without the flag: init_ev, recorded then)
-            } else
-            hipExtLaunchKernelGGL(initiator_side_kernel, dim3(1), dim3(INIT_THREADS), 0, st, nullptr, nullptr, hipExtAnyOrderLaunch, ia,
-                                  static_cast<const DevStatus*>(f->status2 + (pl.s & 1)), static_cast<const int32_t*>(&f->cnt->overflow), &f->cnt->init_flag,
-                                  static_cast<const unsigned long long*>(f->z_tag_step ? &f->cnt->z_flag : nullptr), f->z_tag_step,
-                                  static_cast<unsigned long long*>(nullptr), static_cast<const unsigned long long*>(nullptr), static_cast<unsigned long long*>(nullptr));      // (no ticket: one workgroup)
-            MHT_STEP_HIP(hipGetLastError());
-            f->init_ran_scan = pl.s; f->init_flag_scan = pl.s;
-        }
-    }
-    hp_mark(8);
-    if (f->timing) MHT_STEP_HIP(hipEventRecord(ev[3], st));
+    if (f->timing) { pl.ev = f->evp[f->ev_slot]; f->ev_slot = (f->ev_slot + 1) % EV_POOL; }
+    hipEvent_t* const ev = pl.ev;
+    if (ev) MHT_STEP_HIP(hipEventRecord(ev[0], st));
+    MHT_STEP_CHECK(step_prepasses(ctx, f, pl, z, M, pl.fused));
+    MHT_STEP_CHECK(step_grow(ctx, f, pl, z, M));
+    if (ev) MHT_STEP_HIP(hipEventRecord(ev[1], st));
+    MHT_STEP_CHECK(step_cluster(ctx, f, pl, z, M, init, now));
+    if (ev) MHT_STEP_HIP(hipEventRecord(ev[2], st));
+    MHT_STEP_CHECK(step_prune_similar(ctx, f, pl.s));
+    MHT_STEP_CHECK(step_solve(ctx, f, pl, z, M, init, now));
+    if (ev) MHT_STEP_HIP(hipEventRecord(ev[3], st));
     // ---- 4: N-scan prune (tracker.py:256-259), target side: deferred ------------------------------------------------------
     forest_end_step(f, pl, M);
     hp_mark(9);
-    if (f->timing) { MHT_STEP_HIP(hipEventRecord(ev[4], st)); f->timed_steps += 1; }
+    if (ev) { MHT_STEP_HIP(hipEventRecord(ev[4], st)); f->timed_steps += 1; }
     return MHT_OK;
 }
 extern "C" int mht_forest_step(mht_ctx* ctx, const float* z, int32_t M) { return forest_step_impl(ctx, z, M, nullptr, 0.0); }
@@ -1489,15 +1534,6 @@ extern "C" int mht_forest_sharded_words(mht_ctx* ctx, int32_t shard_n, int32_t* 
     return MHT_OK;
 }
 
-static int sharded_begin_impl(mht_ctx* ctx, const float* z, int32_t M, int32_t shard_n, int32_t shard_i, int32_t* sel_rel, int32_t n_words);
-extern "C" int mht_forest_step_sharded_begin(mht_ctx* ctx, const float* z, int32_t M, int32_t shard_n, int32_t shard_i, int32_t* sel_rel) {
-    return sharded_begin_impl(ctx, z, M, shard_n, shard_i, sel_rel, 0);
-}
-extern "C" int mht_forest_step_sharded_begin2(mht_ctx* ctx, const float* z, int32_t M, int32_t shard_n, int32_t shard_i, int32_t* xch, int32_t n_words) {
-    MHT_REQUIRE(ctx && ctx->forest && n_words >= ctx->forest->Tcap + shard_n * TEAM_MAX * XT_WORDS,
-                "mht_forest_step_sharded_begin2: the exchange block needs mht_forest_sharded_words() words");
-    return sharded_begin_impl(ctx, z, M, shard_n, shard_i, xch, n_words);
-}
 static int sharded_begin_impl(mht_ctx* ctx, const float* z, int32_t M, int32_t shard_n, int32_t shard_i, int32_t* sel_rel, int32_t n_words) {
     MHT_REQUIRE(ctx && ctx->forest && sel_rel, "mht_forest_step_sharded_begin: null argument");
     MHT_REQUIRE(shard_n >= 1 && shard_i >= 0 && shard_i < shard_n, "mht_forest_step_sharded_begin: bad shard %d of %d", shard_i, shard_n);
@@ -1506,60 +1542,48 @@ static int sharded_begin_impl(mht_ctx* ctx, const float* z, int32_t M, int32_t s
     MHT_REQUIRE(!f->shard_open, "mht_forest_step_sharded_begin: the previous sharded step has not been ended");
     MHT_HIP_CHECK(hipSetDevice(ctx->device));
     { const int rc = flush_publish(ctx, f); if (rc) return rc; }
-    StepPlan pl;
     // (AIS messages: the fused children are made on every shard, like grow and clustering -- forest_ais_kernel walks the leaves of the COMMITTED
-    // table, as forest_ct_kernel does)
-    const bool ais = f->ais && f->ais_armed;
-    if (ais && !(M + f->ais_nA <= f->Mpad)) {
-        f->ais_armed = false;
-        set_error("mht_forest_step_sharded_begin: %d radar measurements + %d AIS messages exceed max_meas=%d", M, f->ais_nA, f->cfg.max_meas);
-        return MHT_E_INVALID;
-    }
-    if (f->ct || ais) { const int rcf = flush_commit(ctx, f); if (rcf) return rcf; }
-    { const int rc = forest_begin_step(ctx, f, z, M, "mht_forest_step_sharded_begin", pl); if (rc) { f->ais_armed = false; return rc; } }
-    if (ais) pl.W = (M + f->ais_nA + 63) / 64;
-    int rc;
-    if (ais) { rc = forest_ais_prepass(ctx, f, pl.s, pl.n_ub, z, M); if (rc) { f->dead = true; return rc; } }
-    if (f->ct) { rc = forest_ct_prepass(ctx, f, pl.s, pl.n_ub); if (rc) { f->dead = true; return rc; } }
+    // table, as forest_ct_kernel does here)
+    StepPlan pl;
+    { const int rc = step_begin(ctx, f, z, M, "mht_forest_step_sharded_begin", f->ct, false, pl); if (rc) return rc; }
+    MHT_STEP_CHECK(step_prepasses(ctx, f, pl, z, M, false));
     {
         FGrowArgs g;
         fill_fgrow(f, pl.s, pl.fused, g);
         FDyn d = {};
-        d.z = z; d.M = M; d.W = pl.W; d.c_scan = f->pending_dyn.scan; d.c_M = f->pending_dyn.M; d.c_W = f->pending_dyn.W;
-        d.ais_on = ais ? 1 : 0;
-        d.maybe_dead = (f->similar_ran_scan == pl.s - 1);
-        rc = launch_fgrow(ctx, g, d, pl.n_ub, pl.fused ? &f->pending : nullptr);
+        fdyn_base(f, z, M, pl, d);
+        MHT_STEP_CHECK(launch_fgrow(ctx, g, d, pl.n_ub, pl.fused ? &f->pending : nullptr));
     }
     f->commit_pending = false;
-    if (!rc) {
+    {
         ClusterArgs c;
         fill_cluster(f, pl.s, c);
         c.sel_rel_reset = sel_rel;
         c.shard_n = shard_n; c.tchild = f->tchild; c.tcend = f->tcend; c.cl_owner = f->cl_owner;
-        rc = launch_cluster(ctx, c);
+        MHT_STEP_CHECK(launch_cluster(ctx, c));
     }
-    if (!rc && f->prune_thr > 0.f) {      // (replicated, like grow and clustering: every device prunes every lone target)
-        SimilarArgs sa;
-        fill_similar(f, pl.s, sa);
-        rc = launch_prune_similar(ctx, sa, f->nT_ub_step);
-        f->similar_ran_scan = pl.s;
-    }
-    if (!rc) {
+    MHT_STEP_CHECK(step_prune_similar(ctx, f, pl.s));      // (replicated, like grow and clustering: every device prunes every lone target)
+    {
         BlpArgs b;
         fill_blp(f, pl.s, b);
         b.shard_n = shard_n; b.shard_i = shard_i; b.sel_rel = sel_rel; b.cl_owner = f->cl_owner;
         b.t_alive = nullptr;      // solve only: the per-target end of the scan follows the exchange (mht_forest_step_sharded_end)
         if (n_words > 0 && shard_n > 1) {      // teams across the devices: the files' slots start empty
             b.shard_team = sel_rel + f->Tcap;
-            MHT_HIP_CHECK(hipMemsetAsync(b.shard_team, 0xff, (size_t)shard_n * TEAM_MAX * XT_WORDS * sizeof(int32_t), ctx->stream));
+            MHT_STEP_HIP(hipMemsetAsync(b.shard_team, 0xff, (size_t)shard_n * TEAM_MAX * XT_WORDS * sizeof(int32_t), ctx->stream));
         }
-        int grid = f->nT_ub_step / 2 + 8;
-        if (grid > 1024) grid = 1024;
-        rc = launch_blp(ctx, b, grid);
+        MHT_STEP_CHECK(launch_blp(ctx, b, blp_full_grid(f, 2)));
     }
-    if (rc) { f->dead = true; return rc; }
     f->shard_open = true; f->shard_plan_s = pl.s; f->shard_plan_W = pl.W; f->shard_M = M; f->shard_xn = (n_words > 0 && shard_n > 1) ? shard_n : 0;
     return MHT_OK;
+}
+extern "C" int mht_forest_step_sharded_begin(mht_ctx* ctx, const float* z, int32_t M, int32_t shard_n, int32_t shard_i, int32_t* sel_rel) {
+    return sharded_begin_impl(ctx, z, M, shard_n, shard_i, sel_rel, 0);
+}
+extern "C" int mht_forest_step_sharded_begin2(mht_ctx* ctx, const float* z, int32_t M, int32_t shard_n, int32_t shard_i, int32_t* xch, int32_t n_words) {
+    MHT_REQUIRE(ctx && ctx->forest && n_words >= ctx->forest->Tcap + shard_n * TEAM_MAX * XT_WORDS,
+                "mht_forest_step_sharded_begin2: the exchange block needs mht_forest_sharded_words() words");
+    return sharded_begin_impl(ctx, z, M, shard_n, shard_i, xch, n_words);
 }
 
 extern "C" int mht_forest_step_sharded_end(mht_ctx* ctx, const int32_t* sel_rel) {
@@ -1601,6 +1625,7 @@ struct mht_group {
     bool light = false;           // ILPs of a group: wavefront-per-cluster round-0 pass first (mht_blp.hip: blp_light), the full solver for what it leaves
     bool counted = false;         // the members' in_groups counters include this group
     bool wave = true;             // grow launch: wavefront per target (MHT_FG_WAVE=0: the workgroup-per-target kernel of the one-sector launch)
+    int blp_div = 4;              // ILP launch: targets per workgroup (MHT_GROUP_BLP_DIV)
 };
 
 extern "C" int mht_group_destroy(mht_group* g) {
@@ -1645,13 +1670,16 @@ extern "C" int mht_group_create(mht_group** out, int32_t n, mht_ctx* const* ctxs
     ClusterArgs* hcl = new ClusterArgs[(size_t)n * 2];
     BlpArgs* hbl = new BlpArgs[(size_t)n * P * 2];
     BlpArgs* hbl0 = new BlpArgs[(size_t)n * P];
-    { const char* e = getenv("MHT_BLP_TWO_TIER"); g->two_tier = e && e[0] == '1'; }
+    g->two_tier = env_flag("MHT_BLP_TWO_TIER", false);
     // (measured, headline config, two groups: 16 sectors 56.7 k -> 72.2 k scans/s with the light pass, 4 sectors 40.6 k -> 36.1 k: the second
     // launch costs more than the narrow one saves while the full solver's workgroups still fit the machine in two rounds)
-    { const char* e = getenv("MHT_BLP_LIGHT"); g->light = e ? (e[0] != '0') : (n >= 6); }
+    g->light = env_flag("MHT_BLP_LIGHT", n >= 6);
     // grow launch of the group: wavefront per target from eight sectors on (measured, headline config: 4 sectors 49 us workgroup-
     // per-target vs 54 us; 16 sectors 136 vs 121 us -- the wavefront variant costs 5.6 us per further sector, the other 7.2)
-    { const char* e = getenv("MHT_FG_WAVE"); g->wave = e ? (e[0] != '0') : (n >= 8); }
+    g->wave = env_flag("MHT_FG_WAVE", n >= 8);
+    // ILP launch of the group: a workgroup per blp_div targets (mht_group_step)
+    g->blp_div = (int)env_int("MHT_GROUP_BLP_DIV", 4);
+    if (g->blp_div < 1) g->blp_div = 4;
     for (int i = 0; i < n; ++i) {
         const Forest* f = ctxs[i]->forest;
         for (int v = 0; v < P; ++v) {
@@ -1741,10 +1769,7 @@ extern "C" int mht_group_step(mht_group* g, const float* const* z, const int32_t
         if (pl[i].rebuilt) { const int rc = group_refresh_member(g, i); if (rc) { f->dead = true; return rc; } }
         const int s = pl[i].s, v = s % P;
         FDyn& d = fb.d[i];
-        d.z = z[i]; d.M = M[i]; d.W = pl[i].W;
-        d.c_scan = f->pending_dyn.scan; d.c_M = f->pending_dyn.M; d.c_W = f->pending_dyn.W;
-        d.maybe_dead = (f->similar_ran_scan == pl[i].s - 1);
-        d.dbg = nullptr;
+        fdyn_base(f, z[i], M[i], pl[i], d);
         fgrow_plan(d, pl[i].n_ub, f->Tcap, pl[i].fused, g->wave);
         fb.ga[i] = g->ga + ((size_t)i * P + v) * 2 + (pl[i].fused ? 1 : 0);
         fb.ca[i] = g->ca + (size_t)i * P + (s - 1 + P) % P;      // the commit of the scan before rides along (if fused)
@@ -1757,9 +1782,7 @@ extern "C" int mht_group_step(mht_group* g, const float* const* z, const int32_t
         // (a quarter of the targets, not half as in the one-sector launch: the 155 KB workgroups of S sectors share the CUs one at a time, and one
         // without a multi-target cluster still costs its entry; measured, headline config, two groups: S = 4 39.1 -> 42.3 k scans/s, S = 16 74.1 -> 75.2 k;
         // an eighth: 39.7 / 74.8 k.  MHT_GROUP_BLP_DIV overrides)
-        static int gdiv = -1; if (gdiv < 0) { const char* e = getenv("MHT_GROUP_BLP_DIV"); gdiv = e ? atoi(e) : 4; if (gdiv < 1) gdiv = 4; }
-        int gbl = f->nT_ub_step / gdiv + 8;
-        if (gbl > 1024) gbl = 1024;
+        const int gbl = blp_full_grid(f, g->blp_div);
         if (gbl > grid_b) grid_b = gbl;
         const size_t l = g->wave ? fgrow_wave_lds_bytes(d.W, f->pds, f->AW) : fgrow_lds_bytes(d.W, f->pds, f->AW);
         if (l > lds) lds = l;
@@ -1769,15 +1792,7 @@ extern "C" int mht_group_step(mht_group* g, const float* const* z, const int32_t
     int rc = launch_fgrow_batch(c0, fb, n, grid_g, lds, g->ctx[0]->forest->pds, g->wave);
     if (!rc) rc = launch_cluster_batch(c0, cb, n, f0->Tcap, f0->n_mnodes);
     // similar-state pruning of the members that ask for it: a launch of their own each, between clustering and the ILPs
-    for (int i = 0; i < n && !rc; ++i) {
-        const Forest* f = g->ctx[i]->forest;
-        if (f->prune_thr > 0.f) {
-            SimilarArgs sa;
-            fill_similar(f, pl[i].s, sa);
-            rc = launch_prune_similar(c0, sa, f->nT_ub_step);
-            g->ctx[i]->forest->similar_ran_scan = pl[i].s;
-        }
-    }
+    for (int i = 0; i < n && !rc; ++i) rc = step_prune_similar(c0, g->ctx[i]->forest, pl[i].s);
     // ILPs in two LDS tiers: the small footprint (several workgroups per CU) takes the clusters that fit it and the single-target
     // clusters, a narrow launch with the default footprint takes the few that do not
     if (g->light && !g->two_tier) {
@@ -1803,10 +1818,9 @@ static int forest_initiate_impl(mht_ctx* ctx, mht_initiator* in, const float* z,
     MHT_REQUIRE(f->scan > 0, "mht_forest_initiate: no scan processed yet");
     MHT_REQUIRE(M == f->last_M, "mht_forest_initiate: M=%d is not the scan just stepped (M=%d)", M, f->last_M);
     if (!z) z = f->z_cur;      // (the scan mht_forest_step_host staged)
-    const double* bx; const float* bP; const uint8_t* bfl; const double* bpd; const int32_t* bme; const int32_t* bn; int cap; mht_ctx* ictx;
-    initiator_born_ptrs(in, &bx, &bP, &bfl, &bpd, &bme, &bn, &cap, &ictx);
-    MHT_REQUIRE(ictx == ctx, "mht_forest_initiate: the initiator belongs to another context");
-    MHT_REQUIRE(cap <= BIRTH_CAP, "mht_forest_initiate: the initiator's max_born=%d exceeds the report's %d", cap, BIRTH_CAP);
+    BornPtrs born;
+    { const int rc = initiator_check(ctx, in, "mht_forest_initiate", born); if (rc) return rc; }
+    const int cap = born.cap;
     MHT_HIP_CHECK(hipSetDevice(ctx->device));
     InitArgs ia = {};
     char* report_dev = f->report_dev2[f->scan & 1];
@@ -1818,22 +1832,15 @@ static int forest_initiate_impl(mht_ctx* ctx, mht_initiator* in, const float* z,
         initiator_ais_ptrs(in, &au.msgs, &au.used);
         au.mmsi = f->l_mmsi[f->scan % f->R]; au.first = f->tab[nb_].first; au.leaf_off = f->tab[nb_].leaf_off; au.cnt = f->cnt;
     }
-    if (!init_done) { initiator_scan_args(in, z, M, reinterpret_cast<const unsigned long long*>(report_dev + f->used_off), now, ia); ia.bhint = f->bhint_dev; ia.forest_overflow = &f->cnt->overflow; ia.scan_no = f->scan; }
+    if (!init_done) scan_init_args(f, in, z, M, reinterpret_cast<const unsigned long long*>(report_dev + f->used_off), now, f->scan, ia);
     AddArgs a = {};
-    a.n = cap; a.n_dev = bn; a.x0 = bx; a.pd = bpd; a.P0 = bP; a.meas = bme; a.flags = bfl; a.ids = nullptr; a.accepted = nullptr;
-    a.check = 1; a.thr = f->cfg.merge_threshold;
-    const int nb = (f->scan + 1) & 1;
-    a.layer = f->layer[f->scan % f->R];
-    a.tab = f->tab[nb]; a.vidx = nb;
-    a.path = f->path[f->scan & 1]; a.apath = f->apath[f->scan & 1]; a.PD = f->pds;
-    a.cnt = f->cnt; a.scan = f->scan; a.Nwin = f->cfg.n_scan; a.Tcap = f->Tcap;
-    a.near = f->near;
-    fill_model_only(a.model, &f->model); a.vt = f->vt; a.root_base = f->root_base; a.ct_Proot = f->ct ? f->ct_Proot[f->scan % f->R] : nullptr;
-    if (f->ais) { a.mmsi = f->l_mmsi[f->scan % f->R]; a.hmmsi = f->l_hmmsi[f->scan % f->R]; }
+    a.n = cap; a.n_dev = born.n; a.x0 = born.x; a.pd = born.pd; a.P0 = born.P; a.meas = born.meas; a.flags = born.fl; a.ids = nullptr; a.accepted = nullptr;
+    a.check = 1;
+    fill_add(f, a);
     a.hdr = reinterpret_cast<ReportHeader*>(report_dev);
     a.births = reinterpret_cast<mht_birth_report*>(report_dev + f->birth_off);
 #if MHT_NX == 6
-    {   // the initiator's births are 4-state: lifted into the forest's state space on admission (checked by the callers: the lift is set)
+    {   // the initiator's births are 4-state: lifted into the forest's state space on admission (initiator_check: the lift is set)
         double lx[2]; float lP[4];
         a.lift = initiator_lift(in, lx, lP) ? 1 : 0;
         for (int k = 0; k < 2; ++k) a.lift_x[k] = lx[k];
@@ -1848,7 +1855,7 @@ static int forest_initiate_impl(mht_ctx* ctx, mht_initiator* in, const float* z,
     // streaming (mht_forest_scan) and nothing left to do here but the commit and the admission: both ride in the next scan's grow launch
     // (fgrow_adm_kernel, whose grow is the shared-transition one: a constant-turn forest's grow kernel carries no admission -- its commit and
     // admission run as post_scan_kernel here)
-    const bool ride = defer_publish && init_done && f->adm_fuse && f->commit_pending && !f->ais && !f->ct && au.nA == 0 && ia.nA == 0;
+    const bool ride = defer_publish && init_done && f->sw.adm_fuse && f->commit_pending && !f->ais && !f->ct && au.nA == 0 && ia.nA == 0;
     if (!ride) { const int rc = wait_init_ev(ctx, f); if (rc) return rc; }
     if (!ride) { const int rc = flush_z_wait(ctx, f); if (rc) return rc; }      // (post_scan_kernel may read the scan)
     if (ride) { f->adm = a; f->adm_pending = true; }
@@ -1871,19 +1878,9 @@ static int forest_initiate_impl(mht_ctx* ctx, mht_initiator* in, const float* z,
     return MHT_OK;
 }
 
-// the six-state build takes the 4-state initiator's births only lifted into its state space (mht_initiator_set_lift)
-static bool initiator_fits(const mht_initiator* in) {
-    double x[2]; float P[4];
-    return NX == 4 || initiator_lift(in, x, P);
-}
+extern "C" int mht_forest_initiate(mht_ctx* ctx, mht_initiator* in, const float* z, int32_t M, double now) { return forest_initiate_impl(ctx, in, z, M, now, false); }
 
-extern "C" int mht_forest_initiate(mht_ctx* ctx, mht_initiator* in, const float* z, int32_t M, double now) {
-    MHT_REQUIRE(!in || initiator_fits(in), "mht_forest_initiate: the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv); "
-                "this is the %d-state build: call mht_initiator_set_lift first", NX);
-    return forest_initiate_impl(ctx, in, z, M, now, false);
-}
-
-static int step_host_impl(mht_ctx* ctx, const float* z_host, int32_t M, bool mark_done, mht_initiator* init = nullptr, double now = 0.0) {
+static int step_host_impl(mht_ctx* ctx, const float* z_host, int32_t M, mht_initiator* init = nullptr, double now = 0.0) {
     MHT_REQUIRE(ctx && ctx->forest, "mht_forest_step_host: no forest");
     Forest* f = ctx->forest;
     MHT_REQUIRE(M >= 0 && M <= f->cfg.max_meas, "mht_forest_step_host: M=%d exceeds max_meas=%d", M, f->cfg.max_meas);
@@ -1903,8 +1900,7 @@ static int step_host_impl(mht_ctx* ctx, const float* z_host, int32_t M, bool mar
         // grow launch (4 us + a launch gap per scan); the ctx stream waits for the event (already signalled by then).
         if (!f->stage_stream_tried) {
             f->stage_stream_tried = true;
-            const char* e = getenv("MHT_STAGE_STREAM");
-            if (!(e && e[0] == '0') && hipStreamCreateWithFlags(&f->stage_stream, hipStreamNonBlocking) != hipSuccess) f->stage_stream = nullptr;
+            if (f->sw.stage_stream && hipStreamCreateWithFlags(&f->stage_stream, hipStreamNonBlocking) != hipSuccess) f->stage_stream = nullptr;
         }
         hipStream_t sst = f->stage_stream ? f->stage_stream : ctx->stream;
         // The slot's previous tenant (Z_RING scans ago) must have been CONSUMED -- grow, initiator, post-scan launches on the ctx stream --
@@ -1912,9 +1908,9 @@ static int step_host_impl(mht_ctx* ctx, const float* z_host, int32_t M, bool mar
         // reading a report can get that far ahead of the device.  Every Z_GUARD scans an event goes onto the ctx stream (behind everything
         // queued for the scans so far) and the side stream waits for the one recorded Z_GUARD scans earlier: that covers the tenants of the
         // next Z_GUARD slots (Z_RING = 2 x Z_GUARD), at one event operation per two scans.
-        const bool by_flag = f->stage_stream && init && forest_streams_uf(f, init) && !(f->ais && f->ais_armed) && !f->serial_prof;
+        const bool by_flag = f->stage_stream && init && forest_streams_uf(f, init) && !(f->ais && f->ais_armed) && !f->sw.serial_prof;
         // (streamed scans: the HOST waits for that event -- long signalled -- instead of the side stream: it then also knows that the pinned slots
-        // were pulled, and no per-scan event is needed; and the new event is recorded BEHIND this scan's grow launch (forest_step_impl,
+        // were pulled, and no per-scan event is needed; and the new event is recorded BEHIND this scan's grow launch (step_grow,
         // z_guard_due), not in front of it: a marker packet in front of an any-order grow launch would end its overlap with the previous
         // scan's ILP launch on every fourth scan)
         if (f->stage_stream && f->z_count % Z_GUARD == 0) {
@@ -1942,7 +1938,6 @@ static int step_host_impl(mht_ctx* ctx, const float* z_host, int32_t M, bool mar
         f->z_wait_slot = by_flag ? slot : -1;
         f->z_used[slot] = !by_flag;
         f->z_cur = zd;
-        (void)mark_done;
         hp_mark(1);
         const int rc = forest_step_impl(ctx, zd, M, init, now);
         f->z_tag_step = 0;
@@ -1952,26 +1947,23 @@ static int step_host_impl(mht_ctx* ctx, const float* z_host, int32_t M, bool mar
     f->z_tag_step = 0; f->z_wait_slot = -1;
     return forest_step_impl(ctx, f->z_dev, M, init, now);
 }
-extern "C" int mht_forest_step_host(mht_ctx* ctx, const float* z_host, int32_t M) { return step_host_impl(ctx, z_host, M, true); }
+extern "C" int mht_forest_step_host(mht_ctx* ctx, const float* z_host, int32_t M) { return step_host_impl(ctx, z_host, M); }
 
 // One radar scan of the drop-in API path in one call: steps 1-6 (mht_forest_step_host), step 7 (mht_forest_initiate, if an
 // initiator is given) and the start of the report's way to the host (mht_forest_report_begin).  Nothing here waits for the device.
 extern "C" int mht_forest_scan(mht_ctx* ctx, mht_initiator* in, const float* z_host, int32_t M, double now) {
     hp_begin();
     if (in) {      // (checked before the scan is stepped: nothing may fail between the initiator's run and the admission of its births)
-        MHT_REQUIRE(initiator_fits(in), "mht_forest_scan: the M-of-N initiator is the reference's 4-state one (m_of_n.py imports models/pv); "
-                    "this is the %d-state build: call mht_initiator_set_lift first", NX);
         MHT_REQUIRE(ctx && ctx->forest, "mht_forest_scan: no forest");
-        const double* bx; const float* bP; const uint8_t* bfl; const double* bpd; const int32_t* bme; const int32_t* bn; int cap; mht_ctx* ictx;
-        initiator_born_ptrs(in, &bx, &bP, &bfl, &bpd, &bme, &bn, &cap, &ictx);
-        MHT_REQUIRE(ictx == ctx, "mht_forest_scan: the initiator belongs to another context");
-        MHT_REQUIRE(cap <= BIRTH_CAP, "mht_forest_scan: the initiator's max_born=%d exceeds the report's %d", cap, BIRTH_CAP);
+        BornPtrs born;
+        const int rc = initiator_check(ctx, in, "mht_forest_scan", born);
+        if (rc) return rc;
     }
     // (messages waiting for the initiator: which of them a track took is known behind the scan's pruning only -- the initiator then runs in
     // post_scan_kernel, not next to the clustering)
     const bool ais_init = in && initiator_ais_pending(in) > 0;
     hp_mark(0);
-    int rc = step_host_impl(ctx, z_host, M, false, ais_init ? nullptr : in, now);
+    int rc = step_host_impl(ctx, z_host, M, ais_init ? nullptr : in, now);
     if (rc) return rc;
     if (!in) return mht_forest_report_begin(ctx);
     rc = forest_initiate_impl(ctx, in, nullptr, M, now, true);
