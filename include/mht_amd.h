@@ -31,7 +31,7 @@ extern "C" {
 /* State dimension of the library build the header is used with: 4 (libmht_amd.so: the reference's CV model, models/pv.py) or 6
  * (libmht_amd6.so: the same sources compiled with -DMHT_NX=6 for BASELINE config 5's six-state model).  It sizes the model matrices
  * and the state vectors / covariances of the forest's reports; the stateless seams mht_gate_scan (4 states), mht_gate_scan_x and
- * mht_smooth_tracks (4 or 6 at run time) do not depend on it. */
+ * mht_smooth_tracks (4 or 6 at run time) and mht_smooth_tracks_ct (6) do not depend on it. */
 #ifndef MHT_NX
 #define MHT_NX 4
 #endif
@@ -206,6 +206,25 @@ size_t mht_smooth_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max);
 int mht_smooth_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                       const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* xs, double* Ps,
                       void* work, size_t work_bytes);
+
+/* ---- seam (v), constant turn: the same smoother for histories of the constant-turn model (pymht_amd/models/ct.py) -- OPT-IN: nothing
+ * routes here unless the caller asks (constantTurn=True in the Python API); mht_smooth_tracks keeps rejecting transition != 0 -------
+ * The forest's filter predicts such a track with x+ = Phi(T, w) x, P+ = Phi P Phi' + Q, Phi taken at the hypothesis's FILTERED turn
+ * rate w = x[4] and without a Jacobian with respect to w (not an EKF).  Along one track that is a linear model with a known A_k per
+ * step, and this is the recursion above with A_k = Phi(T, xf_k[4]) in place of A, in the forward pass and -- rebuilt from the same
+ * stored xf_k[4] -- in G_k = Pf_k A_k' Pp_{k+1}^-1:
+ *   s = sin(w T), c = cos(w T), sw = s / w, cw = (1 - c) / w (|w| < 1e-9: sw = T, cw = 0);  A_k = I + the nine entries
+ *   (0,2) sw (0,3) -cw (1,2) cw (1,3) sw (2,2) c (2,3) -s (3,2) s (3,3) c (4,5) T, in float64 and NOT rounded to float32 as the
+ *   forest's own Phi is -- a rounded A_k would make the result a discontinuous function of w; the forward pass here therefore differs
+ *   from the forest's filtered states by that rounding, of order 1e-7 relative.
+ * model: nx == 6 and transition == 1 are required (anything else, transition == 0 included: MHT_E_INVALID); Q, C, R are read and
+ * widened, T is `period` (> 0), A is ignored and may be NULL.  Every other argument, every layout and the error behaviour are those of
+ * mht_smooth_tracks with nx = 6; work_bytes >= mht_smooth_ct_work_bytes(n_tracks, L_max) = mht_smooth_work_bytes(6, n_tracks, L_max)
+ * (sin / cos are recomputed in the backward pass, not stored; 0 for a negative size). */
+size_t mht_smooth_ct_work_bytes(int32_t n_tracks, int32_t L_max);
+int mht_smooth_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                         const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* xs, double* Ps,
+                         void* work, size_t work_bytes);
 
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in

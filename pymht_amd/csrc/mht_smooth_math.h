@@ -57,9 +57,9 @@ MHT_HD void smooth_predict(const SmoothModel<N>& m, const double* xf, const doub
 }
 
 // Measurement update of (x, P) in place with z:  S = C P C' + R (2 x 2, inverted in closed form), K = P C' S^-1,
-// x += K (z - C x), P -= K (C P)
-template <int N>
-MHT_HD void smooth_update(const SmoothModel<N>& m, double z0, double z1, double* x, double* P) {
+// x += K (z - C x), P -= K (C P).  M: anything with C [2 N] and R [3] (SmoothModel<N>, or the constant-turn smoother's SmoothCtModel)
+template <int N, typename M>
+MHT_HD void smooth_update(const M& m, double z0, double z1, double* x, double* P) {
     double CP[2 * N];      // C P, 2 x N; (P C')' by symmetry
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -122,15 +122,14 @@ MHT_HD void smooth_cholesky(double* P, double* inv_d) {
     }
 }
 
-// One backward step.  In: the filtered (xf, Pf) of node k, the smoothed (xs, Ps) of node k + 1.  Out, in place: (xs, Ps) of node k.
-//   G = Pf A' Pp^-1 with Pp = A Pf A' + Q recomputed here (the forward pass keeps xf and Pf only), applied through Pp = U' U:
-//   row i of G solves g U' U = row i of Pf A' = column i of A Pf.
+// The part of a backward step behind the prediction, whatever made it.  In: the filtered (xf, Pf) of node k, the prediction of node
+// k + 1 from it (xp, AP = A Pf, U = Pp: destroyed), the smoothed (xs, Ps) of node k + 1.  Out, in place: (xs, Ps) of node k.
+//   G = Pf A' Pp^-1 applied through Pp = U' U: row i of G solves g U' U = row i of Pf A' = column i of A Pf.
 //   xs_k = xf + G (xs_{k+1} - xp),  Ps_k = Pf + G (Ps_{k+1} - Pp) G'.   COV = false: means only, Ps is not touched.
 template <int N, bool COV>
-MHT_HD void smooth_backward(const SmoothModel<N>& m, const double* xf, const double* Pf, double* xs, double* Ps) {
+MHT_HD void smooth_backward_gain(const double* xf, const double* Pf, const double* xp, const double* AP, double* U, double* xs, double* Ps) {
     constexpr int NS = N * (N + 1) / 2;
-    double xp[N], AP[N * N], U[NS], inv_d[N];
-    smooth_predict<N>(m, xf, Pf, xp, AP, U);
+    double inv_d[N];
     double D[COV ? NS : 1];      // Ps_{k+1} - Pp
     if (COV) {
 #pragma unroll
@@ -186,6 +185,14 @@ MHT_HD void smooth_backward(const SmoothModel<N>& m, const double* xf, const dou
             }
         }
     }
+}
+
+// One backward step of the linear model: Pp = A Pf A' + Q is recomputed here (the forward pass keeps xf and Pf only).
+template <int N, bool COV>
+MHT_HD void smooth_backward(const SmoothModel<N>& m, const double* xf, const double* Pf, double* xs, double* Ps) {
+    double xp[N], AP[N * N], U[N * (N + 1) / 2];
+    smooth_predict<N>(m, xf, Pf, xp, AP, U);
+    smooth_backward_gain<N, COV>(xf, Pf, xp, AP, U, xs, Ps);
 }
 
 }  // namespace mht

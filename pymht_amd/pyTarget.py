@@ -225,12 +225,13 @@ class Target:
             el.attrib[stateTag] = node.status
         return el
 
-    def getSmoothTrack(self, radarPeriod, model=None, device=0):
+    def getSmoothTrack(self, radarPeriod, model=None, device=0, constantTurn=False):
         """pyTarget.py:580-609: (smoothed positions [L, 2], smoothed velocities [L, 2], ok) of the chain that ends in this node, from its
         initial state and backtrackMeasurement().  A chain of fewer than two nodes returns its measurements, NaN velocities and False, as
         the reference does.  The smoother is pymht_amd.smoothing (device, fixed model, no EM) -- not pykalman.  The model is the
         tracker's for a node that came from one, else `model`, else models/pv as in the reference; many nodes at once:
-        Tracker.getSmoothTracks()."""
+        Tracker.getSmoothTracks().  constantTurn=True: the node of a constant-turn tracker (models/ct), smoothed with that model's own
+        transition (refused by default; ValueError for a linear model)."""
         from . import smoothing
         tracker = getattr(self, "_tracker", None)
         if model is None:
@@ -238,7 +239,8 @@ class Target:
                 model = tracker._model_mod
             else:
                 from .models import pv as model
-        return smoothing.smooth_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx)[0]
+        return smoothing.smooth_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
+                                      constantTurn=constantTurn)[0]
 
     @staticmethod
     def _smoothed_state_element(states, node, position, velocity, precision=2):

@@ -6,7 +6,11 @@ the smoother below runs with the tracker's OWN model -- A = Phi(T), Q = Q(T), C_
 difference from the reference.  The inputs are the reference's: the initial state of the chain and
 `backtrackMeasurement()` with None for a missed detection.
 
-All tracks of a call go to the device in ONE launch, one track per lane; there is no host fallback."""
+All tracks of a call go to the device in ONE launch, one track per lane; there is no host fallback.
+
+Constant-turn models (models/ct.py) are smoothed only on request: `smooth_tracks_ct`, or `constantTurn=True` further up.  Their transition
+Phi(T, w) is taken at each node's FILTERED turn rate, without a Jacobian with respect to w -- the model the forest itself filters with --
+which makes a track a linear model with a known A_k per step (`mht_smooth_tracks_ct`); `smooth_tracks` keeps refusing such a model."""
 import ctypes as C
 
 import numpy as np
@@ -38,6 +42,15 @@ def _measurement_array(measurements):
     return z
 
 
+def _check_ct_model(model):
+    if getattr(model, "transition", None) != "ct":
+        raise ValueError("smoothing: constant-turn smoothing needs a model whose transition is \"ct\" (models/ct.py); model %r has no turn "
+                         "rate to read" % getattr(model, "__name__", model))
+    if np.asarray(model.C_RADAR).shape[1] != 6:
+        raise ValueError("smoothing: the constant-turn model has 6 states (got %d)" % np.asarray(model.C_RADAR).shape[1])
+    return 6
+
+
 def smooth_tracks(model, radarPeriod, tracks, device=0, ctx=None, covariances=True):
     """Smooth a batch of track histories.
 
@@ -47,21 +60,30 @@ def smooth_tracks(model, radarPeriod, tracks, device=0, ctx=None, covariances=Tr
                  not used (what `Target.backtrackMeasurement()` returns can be handed in as it is).
     device, ctx  the GPU ordinal, or an existing pymht_amd.device.Context (a Tracker's) to run on
     Returns per track (xs [L, nx], Ps [L, nx, nx]) float64, Ps None with covariances=False (means only: the cheaper kernel)."""
-    nx = _check_model(model)
-    n = len(tracks)
-    if n == 0:
+    return _smooth_on(ctx, device, model, radarPeriod, tracks, _check_model(model), covariances, False)
+
+
+def smooth_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None, covariances=True):
+    """`smooth_tracks` for a constant-turn model (`model.transition == "ct"`: pymht_amd.models.ct; anything else raises ValueError): same
+    arguments, same outputs with nx = 6.  A_k = Phi(T, w) at the filtered turn rate of node k, in float64 and not rounded to float32 as
+    `model.Phi` returns it, no Jacobian with respect to w."""
+    return _smooth_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), covariances, True)
+
+
+def _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, constant_turn):
+    if len(tracks) == 0:
         return []
     own = ctx is None
     if own:
         ctx = Context(device, nx=nx)
     try:
-        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances)
+        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances, constant_turn)
     finally:
         if own:
             ctx.close()
 
 
-def _smooth(ctx, model, period, tracks, nx, covariances):
+def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn):
     n, ns = len(tracks), nx * (nx + 1) // 2
     zs = [_measurement_array(t[2]) for t in tracks]
     lens = np.array([len(z) for z in zs], dtype=np.int32)
@@ -92,16 +114,17 @@ def _smooth(ctx, model, period, tracks, nx, covariances):
     xs_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
     Ps_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev) if covariances else None
     lib = ctx.lib
-    need = int(lib.mht_smooth_work_bytes(nx, n, L_max))
+    need = int(lib.mht_smooth_ct_work_bytes(n, L_max) if constant_turn else lib.mht_smooth_work_bytes(nx, n, L_max))
     work = torch.empty(need, dtype=torch.uint8, device=dev)
+    # (the constant-turn seam builds its own transition per node: Phi(T, 0) stands in the struct and is not read)
     keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in (model.Phi(period), model.Q(period), model.C_RADAR, model.R_RADAR())]
     fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-    mx = _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 0, period)
+    mx = _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 1 if constant_turn else 0, period)
     lens_sorted = np.ascontiguousarray(lens[order])
     torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    _lib.check(lib.mht_smooth_tracks(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                                     z_d.data_ptr(), h_d.data_ptr(), xs_d.data_ptr(), Ps_d.data_ptr() if covariances else None,
-                                     work.data_ptr(), need), lib)
+    seam = lib.mht_smooth_tracks_ct if constant_turn else lib.mht_smooth_tracks
+    _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
+                    z_d.data_ptr(), h_d.data_ptr(), xs_d.data_ptr(), Ps_d.data_ptr() if covariances else None, work.data_ptr(), need), lib)
     xs = xs_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
     Ps = None
     if covariances:      # packed upper triangle -> full matrices, still on the device
@@ -124,10 +147,13 @@ def chain_inputs(node, default_P0):
                    [c.measurement for c in chain])
 
 
-def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None):
+def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False):
     """`Target.getSmoothTrack` for many track nodes in one device call: per node (positions [L, 2], velocities [L, 2], ok) as the
-    reference returns them.  A chain of fewer than two nodes has nothing to smooth: its measurements, NaN velocities and False."""
-    _check_model(model)
+    reference returns them.  A chain of fewer than two nodes has nothing to smooth: its measurements, NaN velocities and False.
+    constantTurn=True: the nodes are a constant-turn tracker's and go through `smooth_tracks_ct` (ValueError for any other model); by
+    default such a model is refused (NotImplementedError)."""
+    smooth = smooth_tracks_ct if constantTurn else smooth_tracks
+    (_check_ct_model if constantTurn else _check_model)(model)
     out, batch, where = [None] * len(nodes), [], []
     for i, node in enumerate(nodes):
         chain, inputs = chain_inputs(node, model.P0)
@@ -137,6 +163,6 @@ def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None):
         else:
             batch.append(inputs)
             where.append(i)
-    for i, (xs, _) in zip(where, smooth_tracks(model, radarPeriod, batch, device=device, ctx=ctx, covariances=False)):
+    for i, (xs, _) in zip(where, smooth(model, radarPeriod, batch, device=device, ctx=ctx, covariances=False)):
         out[i] = (xs[:, 0:2], xs[:, 2:4], True)
     return out

@@ -970,19 +970,21 @@ class Tracker():
     def getTrackNodes(self):
         return self.__trackNodes__
 
-    def _smooth_nodes(self, nodes):
+    def _smooth_nodes(self, nodes, constantTurn=False):
         from . import smoothing
-        return smoothing.smooth_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx)
+        return smoothing.smooth_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn)
 
-    def getSmoothTracks(self, terminated=False):
+    def getSmoothTracks(self, terminated=False, constantTurn=False):
         """tracker.py: [track.getSmoothTrack(radarPeriod) for track in __trackNodes__] -- (positions, velocities, ok) per live track, with
         terminated=True followed by the terminated ones (__terminatedTargets__) -- smoothed in ONE batched device call
         (pymht_amd/smoothing.py: a Rauch-Tung-Striebel smoother with the tracker's own model, not pykalman).  A constant-turn tracker
-        raises NotImplementedError: its transition depends on the state."""
+        raises NotImplementedError: its transition depends on the state -- unless constantTurn=True asks for the smoother of that model
+        (Phi(T, w) at each node's filtered turn rate, no Jacobian: smoothing.smooth_tracks_ct), which in turn raises ValueError for a
+        tracker on a linear model."""
         nodes = list(self.__trackNodes__)
         if terminated:
             nodes += list(self.__terminatedTargets__)
-        return self._smooth_nodes(nodes)
+        return self._smooth_nodes(nodes, constantTurn=constantTurn)
 
     def synchronize(self):
         """Wait for everything queued on the device and fold it (reports are folded lazily otherwise)."""
@@ -1053,11 +1055,11 @@ class Tracker():
                             ("targetSizeLimit", self.targetSizeLimit), ("maxSpeedMS", self.maxSpeedMS)):
             ET.SubElement(settings, name).text = str(value)
 
-    def _storeRun(self, scenarioElement, preInitialized=True, smooth=False, **kwargs):
+    def _storeRun(self, scenarioElement, preInitialized=True, smooth=False, constantTurn=False, **kwargs):
         """One <Run>: the per-stage run times of every scan and one <Track> per live and per terminated target -- all states of
         the selected hypothesis' chain (preInitialized=True) or its first and last.  smooth=True also fills every track's
-        <SmoothedStates> (one <S> per node), all tracks of the run smoothed in ONE device call (getSmoothTracks); by default the
-        element stays empty."""
+        <SmoothedStates> (one <S> per node), all tracks of the run smoothed in ONE device call (getSmoothTracks, which constantTurn is
+        handed to: a constant-turn tracker smooths with constantTurn=True only); by default the element stays empty."""
         import xml.etree.ElementTree as ET
         run = ET.SubElement(scenarioElement, xmltags.runTag)
         run.attrib[xmltags.iterationTag] = str(kwargs[xmltags.iterationTag] if xmltags.iterationTag in kwargs
@@ -1074,7 +1076,8 @@ class Tracker():
                                                        xmltags.maxTag: str(round(np.max(v), prec))}
                           ).text = np.array_str(v, precision=prec, max_line_width=999999)
         groups = ((list(self.__trackNodes__), {}), (self.__terminatedTargets__, {xmltags.terminatedTag: True}))
-        smoothed = iter(self._smooth_nodes([node for nodes, _ in groups for node in nodes])) if (smooth and preInitialized) else None
+        smoothed = (iter(self._smooth_nodes([node for nodes, _ in groups for node in nodes], constantTurn=constantTurn))
+                    if (smooth and preInitialized) else None)
         for nodes, extra in groups:
             for node in nodes:
                 if preInitialized:

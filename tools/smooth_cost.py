@@ -8,7 +8,12 @@
         accuracy of the 40-track batch of tests/test_smooth_gpu.py: e_dev / e_np against the np.longdouble truth
         kernel time from ONE `rocprofv3 --kernel-trace --stats` run (a run of its own) next to the bytes the kernel has to move
       Every step that touches the GPU is a child process under its own timeout; the first that fails ends the run.
-  (children: `time NAME`, `accuracy`, `trace`)"""
+  python tools/smooth_cost.py --ct [--out FILE]
+      the constant-turn smoother (smooth_tracks_ct, `mht_smooth_tracks_ct`; default FILE: smooth_ct_cost.txt): the accuracy ratios of the
+      40-track batch of tests/test_smooth_ct_gpu.py on both library builds, then 2 000 tracks x 400 nodes of models/ct with and without
+      covariances -- end to end and, from one profiler run, per kernel -- and IN THE SAME RUN the linear six-state smoother (models/ca) on
+      a batch of the same shape: the thing to compare with.
+  (children: `time NAME`, `accuracy`, `trace`, `time-ct`, `accuracy-ct`, `trace-ct`)"""
 import glob
 import json
 import os
@@ -95,6 +100,114 @@ def child_trace():
                 smooth_tracks(model_of(name), PERIOD, tracks, covariances=cov)
 
 
+CT_SIZE = (2000, 400)
+
+
+def ct_batches():
+    """(models/ct, its batch), (models/ca, a batch of the same shape)."""
+    import smooth_ct_ref as cr
+    import smooth_ref as sr
+    from pymht_amd.models import ca, ct
+    n, L = CT_SIZE
+    return (ct, cr.make_batch(ct, PERIOD, [L] * n, seed=99, p_detect=0.8)), (ca, sr.make_batch(ca, PERIOD, [L] * n, seed=99, p_detect=0.8))
+
+
+def child_time_ct():
+    import torch
+    from pymht_amd.device import Context
+    from pymht_amd.smoothing import smooth_tracks, smooth_tracks_ct
+    (ct, ct_tracks), (ca, ca_tracks) = ct_batches()
+    ctx = Context(0, nx=6)
+    res = {}
+    for key, fn, model, tracks in (("ct", smooth_tracks_ct, ct, ct_tracks), ("ca", smooth_tracks, ca, ca_tracks)):
+        for cov in (True, False):
+            fn(model, PERIOD, tracks, ctx=ctx, covariances=cov)      # warm-up: code object load, allocator
+            ts = []
+            for _ in range(5):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(model, PERIOD, tracks, ctx=ctx, covariances=cov)      # (ends in a device-to-host copy: synchronous)
+                ts.append(time.perf_counter() - t0)
+            res[key + ("_cov" if cov else "_means")] = ts
+    ctx.close()
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def child_accuracy_ct():
+    import smooth_ct_ref as cr
+    import smooth_ref as sr
+    from pymht_amd.device import Context
+    from pymht_amd.models import ct
+    from pymht_amd.smoothing import smooth_tracks_ct
+    assert np.finfo(np.longdouble).eps < 1e-18
+    rng = np.random.default_rng(20240)
+    tracks = cr.make_batch(ct, PERIOD, [int(v) for v in rng.integers(2, 401, 40)], seed=17, p_detect=0.8)      # (the batch of tests/test_smooth_ct_gpu.py)
+    mats = cr.model_matrices(ct, PERIOD)
+    refs = [(cr.rts_ct(*mats, x0, P0, z, dtype=np.longdouble), cr.rts_ct(*mats, x0, P0, z, dtype=np.float64)) for x0, P0, z in tracks]
+    res = {}
+    for nx in (4, 6):
+        ctx = Context(0, nx=nx)
+        dev = smooth_tracks_ct(ct, PERIOD, tracks, ctx=ctx)
+        ctx.close()
+        e = np.zeros(4)
+        for (xs, Ps), (t, f) in zip(dev, refs):
+            e = np.maximum(e, [sr.err(xs, t["xs"]), sr.err(f["xs"], t["xs"]), sr.err(Ps, t["Ps"]), sr.err(f["Ps"], t["Ps"])])
+        res[str(nx)] = e.tolist()
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def child_trace_ct():
+    from pymht_amd.smoothing import smooth_tracks, smooth_tracks_ct
+    (ct, ct_tracks), (ca, ca_tracks) = ct_batches()
+    for fn, model, tracks in ((smooth_tracks_ct, ct, ct_tracks), (smooth_tracks, ca, ca_tracks)):
+        for cov in (True, False):
+            for _ in range(3):
+                fn(model, PERIOD, tracks, covariances=cov)
+
+
+def main_ct(out_path):
+    n, L = CT_SIZE
+    lines = ["tools/smooth_cost.py --ct: the constant-turn Rauch-Tung-Striebel smoother (mht_smooth_tracks_ct: A_k = Phi(T, w) rebuilt per lane and per node from the",
+             "filtered turn rate, float64 sin / cos recomputed in the backward pass) next to the linear six-state smoother (mht_smooth_tracks, models/ca) IN THE SAME RUN",
+             "80 % detections, T = 2.5; end-to-end times are smooth_tracks_ct() / smooth_tracks() (host packing, upload, kernel, copy back, unpacking), median of 5", ""]
+    emit = lambda s: (lines.append(s), print(s, flush=True))
+    acc = run_child(["accuracy-ct"], 420)
+    for nx in ("4", "6"):
+        e = acc[nx]
+        emit("accuracy models/ct, %s-state build (40 tracks of 2-400 nodes, turn rates 0 .. 0.6 rad/s, half with a coupled P_init; truth = np.longdouble): "
+             "means e_dev %.3g e_np %.3g ratio %.2f | covariances e_dev %.3g e_np %.3g ratio %.2f  (required: <= 8)"
+             % (nx, e[0], e[1], e[0] / e[1], e[2], e[3], e[2] / e[3]))
+    emit("")
+    res = run_child(["time-ct"], 900)
+    for key, label in (("ct", "models/ct  constant turn   "), ("ca", "models/ca  linear six-state")):
+        emit("%s %5d tracks x %3d nodes: with covariances %8.1f ms (%s), means only %8.1f ms (%s)"
+             % (label, n, L, 1e3 * np.median(res[key + "_cov"]), " ".join("%.1f" % (1e3 * t) for t in res[key + "_cov"]),
+                1e3 * np.median(res[key + "_means"]), " ".join("%.1f" % (1e3 * t) for t in res[key + "_means"])))
+    emit("")
+    prof_dir = os.path.join(os.path.dirname(os.path.abspath(out_path)), "smooth_ct_prof")
+    run_child(["trace-ct"], 900, prefix=["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", prof_dir, "-o", "smooth_ct", "--"])
+    times = kernel_times(prof_dir)
+    if not times:
+        emit("kernel times: no smoother kernel in the profiler's output under %s" % os.path.relpath(prof_dir, ROOT))
+    med = {}
+    for kname, v in sorted(times.items()):
+        inst = re.search(r"smooth_rts_(ct_)?kernel(?:<(?:6, )?(true|false)>|(?:ILi6E)?I?Lb([01])E)", kname)      # demangled or mangled
+        cov = inst.group(2) == "true" or inst.group(3) == "1"
+        b = kernel_bytes(6, n, L, cov)
+        t = float(np.median(v))
+        med[(bool(inst.group(1)), cov)] = t
+        emit("kernel %-24s %s %5d x %3d: %d launches, median %9.1f us (min %.1f, max %.1f); %.1f MB to move -> %.1f GB/s = %.2f %% of %.0f TB/s HBM peak"
+             % ("smooth_rts_ct_kernel" if inst.group(1) else "smooth_rts_kernel<6>", "covariances" if cov else "means only ", n, L, len(v), t, min(v), max(v),
+                b / 1e6, b / t / 1e3, 100 * b / (t * 1e-6) / HBM_PEAK, HBM_PEAK / 1e12))
+    for cov in (True, False):
+        if (True, cov) in med and (False, cov) in med:
+            emit("constant turn / linear six-state, kernel time, %s: %.2f" % ("covariances" if cov else "means only", med[(True, cov)] / med[(False, cov)]))
+    emit("(both kernels move the same bytes and walk the same chain; the difference is the transition: nine multiply-adds per six-vector and a sin / cos pair per step")
+    emit(" in the forward AND in the backward pass against a dense 6 x 6 product with a wave-uniform matrix)")
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
 def run_child(args, timeout, prefix=()):
     cmd = list(prefix) + [sys.executable, os.path.abspath(__file__)] + list(args)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
@@ -113,7 +226,7 @@ def kernel_times(prof_dir):
     for path in glob.glob(os.path.join(prof_dir, "**", "*kernel_trace.csv"), recursive=True):
         import csv
         for row in csv.DictReader(open(path)):
-            if "smooth_rts_kernel" in row["Kernel_Name"]:
+            if "smooth_rts_" in row["Kernel_Name"]:
                 times.setdefault(row["Kernel_Name"], []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3)
     if times:
         return times
@@ -125,15 +238,14 @@ def kernel_times(prof_dir):
         sym = next(t for t in tabs if t.startswith("rocpd_info_kernel_symbol"))
         names = {r[0]: r[1] for r in c.execute('select id, kernel_name from "%s"' % sym)}
         for kid, s, e in c.execute('select kernel_id, start, end from "%s" order by start' % disp):
-            if "smooth_rts_kernel" in names[kid]:
+            if "smooth_rts_" in names[kid]:
                 times.setdefault(names[kid], []).append((e - s) / 1e3)
     return times
 
 
 def main():
     import smooth_ref as sr
-    out_path = os.path.join(os.environ.get("OUT_DIR", os.path.join(ROOT, "out")), "smooth_cost.txt")
-    n_ref = 50
+    out_path, n_ref, ct_mode = None, 50, False
     argv = sys.argv[1:]
     while argv:
         a = argv.pop(0)
@@ -141,7 +253,13 @@ def main():
             out_path = argv.pop(0)
         elif a == "--reference-tracks":
             n_ref = int(argv.pop(0))
+        elif a == "--ct":
+            ct_mode = True
+    if out_path is None:
+        out_path = os.path.join(os.environ.get("OUT_DIR", os.path.join(ROOT, "out")), "smooth_ct_cost.txt" if ct_mode else "smooth_cost.txt")
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    if ct_mode:
+        return main_ct(out_path)
     lines = ["tools/smooth_cost.py: the device Rauch-Tung-Striebel smoother (mht_smooth_tracks, one track per lane) against the float64 NumPy recursion",
              "80 % detections, T = 2.5; device times are smooth_tracks() end to end (host packing, upload, kernel, copy back, unpacking), median of 5", ""]
     emit = lambda s: (lines.append(s), print(s, flush=True))
@@ -196,5 +314,11 @@ if __name__ == "__main__":
         child_accuracy()
     elif len(sys.argv) > 1 and sys.argv[1] == "trace":
         child_trace()
+    elif len(sys.argv) > 1 and sys.argv[1] == "time-ct":
+        child_time_ct()
+    elif len(sys.argv) > 1 and sys.argv[1] == "accuracy-ct":
+        child_accuracy_ct()
+    elif len(sys.argv) > 1 and sys.argv[1] == "trace-ct":
+        child_trace_ct()
     else:
         main()
