@@ -31,7 +31,7 @@ extern "C" {
 /* State dimension of the library build the header is used with: 4 (libmht_amd.so: the reference's CV model, models/pv.py) or 6
  * (libmht_amd6.so: the same sources compiled with -DMHT_NX=6 for BASELINE config 5's six-state model).  It sizes the model matrices
  * and the state vectors / covariances of the forest's reports; the stateless seams mht_gate_scan (4 states), mht_gate_scan_x and
- * mht_smooth_tracks (4 or 6 at run time) and mht_smooth_tracks_ct (6) do not depend on it. */
+ * mht_smooth_tracks (4 or 6 at run time), mht_smooth_tracks_ct (6) and mht_smooth_tracks_ais (4) do not depend on it. */
 #ifndef MHT_NX
 #define MHT_NX 4
 #endif
@@ -225,6 +225,33 @@ size_t mht_smooth_ct_work_bytes(int32_t n_tracks, int32_t L_max);
 int mht_smooth_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                          const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* xs, double* Ps,
                          void* work, size_t work_bytes);
+
+/* ---- seam (v), AIS: the same smoother for histories of an AIS-aided forest, with the AIS updates the forest applied -- OPT-IN: nothing
+ * routes here unless the caller asks (ais=True in the Python API); mht_smooth_tracks smooths such a history as radar-only ------------
+ * A node of an AIS-aided track that took a message did not step one radar period (Tracker.__fuseRadarAndAis, csrc/mht_ais_math.h):
+ *   leg 1   xp = A1 x, Pp = A1 P A1' + Q1 to the message's time        AIS   S = Pp + r I4, K = Pp S^-1 (through a Cholesky factor of
+ *   S), x = xp + K (m - xp), P = Pp - K Pp        leg 2   predict with A2, Q2 to the scan's time        radar   update, with a plot
+ * and the backward pass takes two Rauch-Tung-Striebel steps over such a node: over leg 2 to the smoothed state at the message's time
+ * (from the filtered state there, behind the AIS update; an intermediate, not output), then over leg 1 to the node in front.  A node
+ * without a message is mht_smooth_tracks' step, operation for operation: a batch without any gives that seam's bits.
+ * model: nx == 4 and transition == 0 are required (MHT_E_INVALID); A, Q, C, R as for mht_smooth_tracks.  len, x_init, P_init, z, has_z,
+ * xs, Ps, the error behaviour and the layouts are mht_smooth_tracks' with nx = 4.  Next to them, per node and track:
+ *   kind     dev [L_max][n_tracks] uint8: 0 plain step, no plot; 1 plain step, radar update; 2 AIS legs only; 3 AIS legs, then radar
+ *            update.  The device takes the radar update from has_z and the legs from kind >= 2: the caller keeps has_z == kind & 1.
+ *   ais_z    dev [L_max][4][n_tracks] f64: the message's state [x, y, vx, vy]      ais_r  dev [L_max][n_tracks] f64: its sigma^2 (> 0)
+ *   leg      dev [L_max][n_tracks] int32: the node's entry of the leg table     (all three read where kind >= 2 only)
+ *   legs     dev [n_legs][52] f64: one entry per distinct (dT1, dT2) of the batch -- A1 [16] row-major, Q1 [10] upper triangle row
+ *            by row, A2 [16], Q2 [10]: Phi and Q of the two time steps as the forest used them (float32, widened).  NULL with n_legs == 0.
+ *   work     dev, work_bytes >= mht_smooth_ais_work_bytes(n_tracks, L_max) (two filtered states per node: at the scan's and at the
+ *            message's time; 0 for a negative size): MHT_E_CAPACITY if it is smaller.
+ * kind, ais_r, leg and legs are device arrays the host cannot see: THE CALLER OWNS THEIR CONTRACT -- 0 <= leg < n_legs wherever
+ * kind >= 2, and r > 0 (pymht_amd.smoothing checks both before it uploads).  Row 0 of every per-node array is ignored; rows >= len[t]
+ * of track t are not read.  Exported by both builds. */
+size_t mht_smooth_ais_work_bytes(int32_t n_tracks, int32_t L_max);
+int mht_smooth_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                          const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, const uint8_t* kind,
+                          const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
+                          double* xs, double* Ps, void* work, size_t work_bytes);
 
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in

@@ -225,22 +225,28 @@ class Target:
             el.attrib[stateTag] = node.status
         return el
 
-    def getSmoothTrack(self, radarPeriod, model=None, device=0, constantTurn=False):
+    def getSmoothTrack(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False):
         """pyTarget.py:580-609: (smoothed positions [L, 2], smoothed velocities [L, 2], ok) of the chain that ends in this node, from its
         initial state and backtrackMeasurement().  A chain of fewer than two nodes returns its measurements, NaN velocities and False, as
         the reference does.  The smoother is pymht_amd.smoothing (device, fixed model, no EM) -- not pykalman.  The model is the
         tracker's for a node that came from one, else `model`, else models/pv as in the reference; many nodes at once:
         Tracker.getSmoothTracks().  constantTurn=True: the node of a constant-turn tracker (models/ct), smoothed with that model's own
-        transition (refused by default; ValueError for a linear model)."""
+        transition (refused by default; ValueError for a linear model).  ais=True: the node of an AIS-aided tracker, smoothed with the
+        AIS updates of its chain, which that tracker's AIS history supplies (ValueError for a node without such a tracker)."""
         from . import smoothing
         tracker = getattr(self, "_tracker", None)
+        lookup = None
+        if ais:
+            if tracker is None:
+                raise ValueError("ais=True needs the node of an AIS-aided Tracker: the messages are in the tracker's history")
+            lookup = tracker._ais_lookup(constantTurn)
         if model is None:
             if tracker is not None:
                 model = tracker._model_mod
             else:
                 from .models import pv as model
         return smoothing.smooth_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
-                                      constantTurn=constantTurn)[0]
+                                      constantTurn=constantTurn, ais=lookup)[0]
 
     @staticmethod
     def _smoothed_state_element(states, node, position, velocity, precision=2):

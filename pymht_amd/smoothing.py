@@ -10,7 +10,12 @@ All tracks of a call go to the device in ONE launch, one track per lane; there i
 
 Constant-turn models (models/ct.py) are smoothed only on request: `smooth_tracks_ct`, or `constantTurn=True` further up.  Their transition
 Phi(T, w) is taken at each node's FILTERED turn rate, without a Jacobian with respect to w -- the model the forest itself filters with --
-which makes a track a linear model with a known A_k per step (`mht_smooth_tracks_ct`); `smooth_tracks` keeps refusing such a model."""
+which makes a track a linear model with a known A_k per step (`mht_smooth_tracks_ct`); `smooth_tracks` keeps refusing such a model.
+
+AIS-aided tracks are smoothed with their AIS updates only on request as well: `smooth_tracks_ais`, or `ais=True` further up.  A node that
+took a message went through two legs -- predict by dT1 to the message's time, update with the message (C = I4, R = sigma^2 I4), predict by
+dT2 to the scan's time -- before its radar update (Tracker.__fuseRadarAndAis, csrc/mht_ais_math.h), and `mht_smooth_tracks_ais` walks
+that model forward and back.  Without the request such a track is smoothed from its radar plots alone, as before."""
 import ctypes as C
 
 import numpy as np
@@ -51,6 +56,47 @@ def _check_ct_model(model):
     return 6
 
 
+def _check_ais_model(model):
+    if getattr(model, "transition", None) == "ct" or np.asarray(model.C_RADAR).shape[1] != 4:
+        raise ValueError("smoothing: AIS messages report four states [x, y, vx, vy]: AIS-aware smoothing needs a 4-state linear model "
+                         "(model %r is not one)" % getattr(model, "__name__", model))
+    return 4
+
+
+def _ais_inputs(model, tracks):
+    """Host side of `smooth_tracks_ais`, checked before any device is needed: per track (has_message [L] bool, message [L, 4],
+    r [L], leg [L] int32), and the leg table [n_legs, 52] -- per distinct (dT1, dT2): Phi(dT1) [16], the upper triangle of Q(dT1) [10],
+    Phi(dT2), Q(dT2), as the model returns them (float32: the matrices the forest filtered with, ais.py::group_messages), widened."""
+    from .ais import SIGMA_HIGH, SIGMA_LOW
+    iu = np.triu_indices(4)
+    widen = lambda m: np.asarray(m, dtype=np.float32).astype(np.float64).reshape(4, 4)
+    index, table, per_track = {}, [], []
+    for t, track in enumerate(tracks):
+        if len(track) != 4:
+            raise ValueError("smoothing: an AIS-aware track is (x_init, P_init, measurements, ais) (track %d has %d entries)" % (t, len(track)))
+        L, ais = len(track[2]), track[3]
+        if len(ais) != L:
+            raise ValueError("smoothing: track %d has %d nodes and %d AIS entries" % (t, L, len(ais)))
+        has, msg, r, leg = np.zeros(L, dtype=bool), np.zeros((L, 4)), np.ones(L), np.zeros(L, dtype=np.int32)
+        for k in range(1, L):      # (entry 0 belongs to the node x_init is the state of and is not used)
+            if ais[k] is None:
+                continue
+            dT1, dT2, state, high = ais[k]
+            dT1, dT2 = float(dT1), float(dT2)
+            if not (dT1 > 0.0 and dT2 > 0.0):
+                raise ValueError("smoothing: track %d node %d: an AIS message lies strictly inside the step to its node "
+                                 "(dT1 = %r, dT2 = %r must be positive)" % (t, k, dT1, dT2))
+            if (dT1, dT2) not in index:
+                index[(dT1, dT2)] = len(table)
+                A1, Q1, A2, Q2 = widen(model.Phi(dT1)), widen(model.Q(dT1)), widen(model.Phi(dT2)), widen(model.Q(dT2))
+                table.append(np.concatenate([A1.ravel(), Q1[iu], A2.ravel(), Q2[iu]]))
+            has[k], leg[k] = True, index[(dT1, dT2)]
+            msg[k] = np.asarray(state, dtype=np.float64).reshape(4)
+            r[k] = float(np.power(SIGMA_HIGH if high else SIGMA_LOW, 2))
+        per_track.append((has, msg, r, leg))
+    return per_track, np.array(table, dtype=np.float64).reshape(len(table), 52)
+
+
 def smooth_tracks(model, radarPeriod, tracks, device=0, ctx=None, covariances=True):
     """Smooth a batch of track histories.
 
@@ -70,20 +116,31 @@ def smooth_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None, covariances
     return _smooth_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), covariances, True)
 
 
-def _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, constant_turn):
+def smooth_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None, covariances=True):
+    """`smooth_tracks` for the histories of an AIS-aided tracker, with the AIS updates the forest applied (4-state linear models;
+    anything else raises ValueError).  tracks: list of (x_init, P_init, measurements, ais) -- the first three as for `smooth_tracks`, and
+    ais[k] None or (dT1, dT2, state [4], highAccuracy) for a node that took a message: made dT1 behind the node in front and dT2 in
+    front of the node itself (both positive, else ValueError), reporting [x, y, vx, vy] with sigma 1 (highAccuracy) or 3.  Entry 0 is
+    not used.  Same outputs as `smooth_tracks`; a batch without any message gives its numbers bit for bit."""
+    nx = _check_ais_model(model)
+    ais = _ais_inputs(model, tracks)
+    return _smooth_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, covariances, False, ais=ais)
+
+
+def _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, constant_turn, ais=None):
     if len(tracks) == 0:
         return []
     own = ctx is None
     if own:
         ctx = Context(device, nx=nx)
     try:
-        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances, constant_turn)
+        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances, constant_turn, ais)
     finally:
         if own:
             ctx.close()
 
 
-def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn):
+def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None):
     n, ns = len(tracks), nx * (nx + 1) // 2
     zs = [_measurement_array(t[2]) for t in tracks]
     lens = np.array([len(z) for z in zs], dtype=np.int32)
@@ -114,7 +171,26 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn):
     xs_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
     Ps_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev) if covariances else None
     lib = ctx.lib
-    need = int(lib.mht_smooth_ct_work_bytes(n, L_max) if constant_turn else lib.mht_smooth_work_bytes(nx, n, L_max))
+    if ais is not None:      # the per-node AIS inputs next to z / has_z, and the leg table
+        per_track, legs = ais
+        kp = hp.copy()
+        mp, rp, lp = np.zeros((n, L_max, 4)), np.ones((n, L_max)), np.zeros((n, L_max), dtype=np.int32)
+        for j, t in enumerate(order):
+            has_m, msg, r, leg = per_track[t]
+            kp[j, :len(has_m)] += 2 * has_m.astype(np.uint8)
+            mp[j, :len(has_m)], rp[j, :len(has_m)], lp[j, :len(has_m)] = msg, r, leg
+        # the seam cannot see these device arrays: its contract is checked here, before the upload
+        fused = kp >= 2
+        if not np.array_equal(kp & 1, hp) or (fused.any() and (lp[fused].min() < 0 or lp[fused].max() >= len(legs))) or not (rp > 0).all():
+            raise ValueError("smoothing: inconsistent AIS inputs (a leg index outside the table of %d entries, or a variance that is not positive)" % len(legs))
+        k_d = up(kp).permute(1, 0).contiguous()
+        m_d = up(mp).permute(1, 2, 0).contiguous()
+        r_d = up(rp).permute(1, 0).contiguous()
+        l_d = up(lp).permute(1, 0).contiguous()
+        legs_d = up(legs) if len(legs) else None
+        need = int(lib.mht_smooth_ais_work_bytes(n, L_max))
+    else:
+        need = int(lib.mht_smooth_ct_work_bytes(n, L_max) if constant_turn else lib.mht_smooth_work_bytes(nx, n, L_max))
     work = torch.empty(need, dtype=torch.uint8, device=dev)
     # (the constant-turn seam builds its own transition per node: Phi(T, 0) stands in the struct and is not read)
     keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in (model.Phi(period), model.Q(period), model.C_RADAR, model.R_RADAR())]
@@ -122,9 +198,15 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn):
     mx = _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 1 if constant_turn else 0, period)
     lens_sorted = np.ascontiguousarray(lens[order])
     torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    seam = lib.mht_smooth_tracks_ct if constant_turn else lib.mht_smooth_tracks
-    _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                    z_d.data_ptr(), h_d.data_ptr(), xs_d.data_ptr(), Ps_d.data_ptr() if covariances else None, work.data_ptr(), need), lib)
+    if ais is not None:
+        _lib.check(lib.mht_smooth_tracks_ais(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
+                                             z_d.data_ptr(), h_d.data_ptr(), k_d.data_ptr(), m_d.data_ptr(), r_d.data_ptr(), l_d.data_ptr(),
+                                             legs_d.data_ptr() if len(legs) else None, len(legs), xs_d.data_ptr(),
+                                             Ps_d.data_ptr() if covariances else None, work.data_ptr(), need), lib)
+    else:
+        seam = lib.mht_smooth_tracks_ct if constant_turn else lib.mht_smooth_tracks
+        _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
+                        z_d.data_ptr(), h_d.data_ptr(), xs_d.data_ptr(), Ps_d.data_ptr() if covariances else None, work.data_ptr(), need), lib)
     xs = xs_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
     Ps = None
     if covariances:      # packed upper triangle -> full matrices, still on the device
@@ -147,13 +229,34 @@ def chain_inputs(node, default_P0):
                    [c.measurement for c in chain])
 
 
-def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False):
+def chain_ais(chain, lookup):
+    """The AIS entries `smooth_tracks_ais` takes for a chain of an AIS-aided tracker: a node with `mmsi` set took the message
+    lookup(scanNumber, mmsi) -- made dT1 = message.time - parent.time behind its parent and dT2 = node.time - message.time in front of
+    itself.  A node whose message the look-up does not have raises RuntimeError: it is never smoothed as radar-only."""
+    ais = [None] * len(chain)
+    for k in range(1, len(chain)):      # (node 0 is the chain's initial state, however it came about)
+        node = chain[k]
+        if node.mmsi is None:
+            continue
+        msg = lookup(node.scanNumber, node.mmsi)
+        if msg is None:
+            raise RuntimeError("smoothing: the node of scan %r was updated by an AIS message of mmsi %r, and the AIS history of that "
+                               "scan has no such message" % (node.scanNumber, node.mmsi))
+        ais[k] = (float(msg.time) - float(chain[k - 1].time), float(node.time) - float(msg.time), msg.state, bool(msg.highAccuracy))
+    return ais
+
+
+def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None):
     """`Target.getSmoothTrack` for many track nodes in one device call: per node (positions [L, 2], velocities [L, 2], ok) as the
     reference returns them.  A chain of fewer than two nodes has nothing to smooth: its measurements, NaN velocities and False.
     constantTurn=True: the nodes are a constant-turn tracker's and go through `smooth_tracks_ct` (ValueError for any other model); by
-    default such a model is refused (NotImplementedError)."""
-    smooth = smooth_tracks_ct if constantTurn else smooth_tracks
-    (_check_ct_model if constantTurn else _check_model)(model)
+    default such a model is refused (NotImplementedError).
+    ais: None, or a callable (scanNumber, mmsi) -> message (time, state, highAccuracy) of an AIS-aided tracker: the chains go through
+    `smooth_tracks_ais` with the messages their nodes took (`chain_ais`).  Not together with constantTurn (ValueError)."""
+    if ais is not None and constantTurn:
+        raise ValueError("smoothing: AIS-aware smoothing is for 4-state linear models, not together with constantTurn")
+    smooth = smooth_tracks_ais if ais is not None else smooth_tracks_ct if constantTurn else smooth_tracks
+    (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
     out, batch, where = [None] * len(nodes), [], []
     for i, node in enumerate(nodes):
         chain, inputs = chain_inputs(node, model.P0)
@@ -161,7 +264,7 @@ def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fal
             pos = _measurement_array(inputs[2])
             out[i] = (pos, np.full_like(pos, np.nan), False)
         else:
-            batch.append(inputs)
+            batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
             where.append(i)
     for i, (xs, _) in zip(where, smooth(model, radarPeriod, batch, device=device, ctx=ctx, covariances=False)):
         out[i] = (xs[:, 0:2], xs[:, 2:4], True)

@@ -970,21 +970,45 @@ class Tracker():
     def getTrackNodes(self):
         return self.__trackNodes__
 
-    def _smooth_nodes(self, nodes, constantTurn=False):
-        from . import smoothing
-        return smoothing.smooth_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn)
+    def _ais_message(self, scanNumber, mmsi):
+        """The message of ship `mmsi` among those handed in with scan `scanNumber` (1-based: _finish_scan appends a scan's list to
+        __aisHistory__ as it appends the scan to __scanHistory__, so scan n is entry n - 1 of both), or None."""
+        hist = self.__aisHistory__
+        if scanNumber is None or not 1 <= scanNumber <= len(hist):
+            return None
+        for m in (hist[scanNumber - 1] or ()):
+            if m.mmsi == mmsi:
+                return m
+        return None
 
-    def getSmoothTracks(self, terminated=False, constantTurn=False):
+    def _ais_lookup(self, constantTurn=False):
+        """What ais=True hands to smoothing.smooth_nodes; ValueError where the switch does not apply."""
+        if constantTurn:
+            raise ValueError("ais=True and constantTurn=True exclude each other: AIS messages report four states of a linear model")
+        if not self._ais:
+            raise ValueError("ais=True needs a Tracker made with aisAided=True: this one has fused no AIS message")
+        self._drain()
+        return self._ais_message
+
+    def _smooth_nodes(self, nodes, constantTurn=False, ais=False):
+        from . import smoothing
+        return smoothing.smooth_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
+                                      ais=self._ais_lookup(constantTurn) if ais else None)
+
+    def getSmoothTracks(self, terminated=False, constantTurn=False, ais=False):
         """tracker.py: [track.getSmoothTrack(radarPeriod) for track in __trackNodes__] -- (positions, velocities, ok) per live track, with
         terminated=True followed by the terminated ones (__terminatedTargets__) -- smoothed in ONE batched device call
         (pymht_amd/smoothing.py: a Rauch-Tung-Striebel smoother with the tracker's own model, not pykalman).  A constant-turn tracker
         raises NotImplementedError: its transition depends on the state -- unless constantTurn=True asks for the smoother of that model
         (Phi(T, w) at each node's filtered turn rate, no Jacobian: smoothing.smooth_tracks_ct), which in turn raises ValueError for a
-        tracker on a linear model."""
+        tracker on a linear model.  ais=True (a tracker made with aisAided=True, else ValueError; not with constantTurn): the smoother
+        of the model the forest filtered with -- a node that took an AIS message is predicted to the message's time, updated with it
+        and predicted on to the scan (smoothing.smooth_tracks_ais), the messages looked up in __aisHistory__; a node whose message is
+        not there raises RuntimeError.  By default an AIS-aided tracker's histories are smoothed from their radar plots alone."""
         nodes = list(self.__trackNodes__)
         if terminated:
             nodes += list(self.__terminatedTargets__)
-        return self._smooth_nodes(nodes, constantTurn=constantTurn)
+        return self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais)
 
     def synchronize(self):
         """Wait for everything queued on the device and fold it (reports are folded lazily otherwise)."""
@@ -1055,11 +1079,12 @@ class Tracker():
                             ("targetSizeLimit", self.targetSizeLimit), ("maxSpeedMS", self.maxSpeedMS)):
             ET.SubElement(settings, name).text = str(value)
 
-    def _storeRun(self, scenarioElement, preInitialized=True, smooth=False, constantTurn=False, **kwargs):
+    def _storeRun(self, scenarioElement, preInitialized=True, smooth=False, constantTurn=False, ais=False, **kwargs):
         """One <Run>: the per-stage run times of every scan and one <Track> per live and per terminated target -- all states of
         the selected hypothesis' chain (preInitialized=True) or its first and last.  smooth=True also fills every track's
         <SmoothedStates> (one <S> per node), all tracks of the run smoothed in ONE device call (getSmoothTracks, which constantTurn is
-        handed to: a constant-turn tracker smooths with constantTurn=True only); by default the element stays empty."""
+        handed to: a constant-turn tracker smooths with constantTurn=True only; so is ais: an AIS-aided tracker's smoothed states hold
+        its AIS updates with ais=True only); by default the element stays empty."""
         import xml.etree.ElementTree as ET
         run = ET.SubElement(scenarioElement, xmltags.runTag)
         run.attrib[xmltags.iterationTag] = str(kwargs[xmltags.iterationTag] if xmltags.iterationTag in kwargs
@@ -1076,7 +1101,7 @@ class Tracker():
                                                        xmltags.maxTag: str(round(np.max(v), prec))}
                           ).text = np.array_str(v, precision=prec, max_line_width=999999)
         groups = ((list(self.__trackNodes__), {}), (self.__terminatedTargets__, {xmltags.terminatedTag: True}))
-        smoothed = (iter(self._smooth_nodes([node for nodes, _ in groups for node in nodes], constantTurn=constantTurn))
+        smoothed = (iter(self._smooth_nodes([node for nodes, _ in groups for node in nodes], constantTurn=constantTurn, ais=ais))
                     if (smooth and preInitialized) else None)
         for nodes, extra in groups:
             for node in nodes:

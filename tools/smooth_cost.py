@@ -208,6 +208,89 @@ def main_ct(out_path):
         fh.write("\n".join(lines) + "\n")
 
 
+AIS_SIZE = (2000, 100)      # --ais: tracks x nodes
+
+
+def child_time_ais():
+    """The seams themselves (length copy, kernel, wait), inputs packed and uploaded once: 3 warm-up calls, then 20 timed ones each of
+    mht_smooth_tracks (nx = 4), mht_smooth_tracks_ais on the same radar-only batch and mht_smooth_tracks_ais with 30 % AIS nodes."""
+    import ctypes as C
+    import torch
+    import smooth_ais_ref as sa
+    from pymht_amd import _lib
+    from pymht_amd.device import Context
+    from pymht_amd.models import pv
+    from pymht_amd.smoothing import _ais_inputs
+    n, L = AIS_SIZE
+    ctx = Context(0, nx=4)
+    lib, dev = ctx.lib, ctx.device
+    keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in (pv.Phi(PERIOD), pv.Q(PERIOD), pv.C_RADAR, pv.R_RADAR())]
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    mx = _lib.MhtModelX(4, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 0, PERIOD)
+    lens = np.full(n, L, dtype=np.int32)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    xs = torch.empty((L, 4, n), dtype=torch.float64, device=dev)
+    Ps = torch.empty((L, 10, n), dtype=torch.float64, device=dev)
+    need = int(lib.mht_smooth_ais_work_bytes(n, L))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    res = {}
+    for key, p_ais in (("radar", 0.0), ("ais", 0.3)):
+        tracks = sa.make_batch(pv, PERIOD, [L] * n, seed=41, p_detect=0.8, p_ais=p_ais)
+        per_track, legs = _ais_inputs(pv, tracks)
+        z = np.array([t[2] for t in tracks])
+        has = ~np.isnan(z).any(axis=2)
+        has[:, 0] = False
+        kind = has.astype(np.uint8) + 2 * np.array([p[0] for p in per_track], dtype=np.uint8)
+        d = dict(x=up(np.array([t[0] for t in tracks]).T), P=up(np.array([t[1].ravel() for t in tracks]).T),
+                 z=up(np.where(has[:, :, None], z, 0.0).transpose(1, 2, 0)), h=up(has.astype(np.uint8).T), k=up(kind.T),
+                 m=up(np.array([p[1] for p in per_track]).transpose(1, 2, 0)), r=up(np.array([p[2] for p in per_track]).T),
+                 l=up(np.array([p[3] for p in per_track]).T), legs=up(legs if len(legs) else np.zeros((1, 52))))
+        res[key + "_share"] = float((kind[:, 1:] >= 2).mean())
+        res[key + "_legs"] = len(legs)
+        torch.cuda.synchronize()
+        lp = lens.ctypes.data_as(C.c_void_p)
+        for cov in (True, False):
+            Pp = Ps.data_ptr() if cov else None
+            calls = {"ais": lambda: lib.mht_smooth_tracks_ais(ctx.handle, C.byref(mx), n, L, lp, d["x"].data_ptr(), d["P"].data_ptr(), d["z"].data_ptr(),
+                                                               d["h"].data_ptr(), d["k"].data_ptr(), d["m"].data_ptr(), d["r"].data_ptr(), d["l"].data_ptr(),
+                                                               d["legs"].data_ptr(), max(len(legs), 1), xs.data_ptr(), Pp, work.data_ptr(), need)}
+            if key == "radar":
+                calls["linear"] = lambda: lib.mht_smooth_tracks(ctx.handle, C.byref(mx), n, L, lp, d["x"].data_ptr(), d["P"].data_ptr(), d["z"].data_ptr(),
+                                                                d["h"].data_ptr(), xs.data_ptr(), Pp, work.data_ptr(), need)
+            for name, fn in calls.items():
+                ts = []
+                for i in range(23):
+                    t0 = time.perf_counter()
+                    _lib.check(fn(), lib)
+                    ts.append(time.perf_counter() - t0)
+                res["%s_%s_%s" % (name, key, "cov" if cov else "means")] = ts[3:]
+    ctx.close()
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def main_ais(out_path):
+    n, L = AIS_SIZE
+    lines = ["tools/smooth_cost.py --ais: the AIS-aware Rauch-Tung-Striebel smoother (mht_smooth_tracks_ais, four states) next to the linear four-state smoother",
+             "(mht_smooth_tracks) IN THE SAME RUN.  %d tracks x %d nodes, 80 %% detections, T = 2.5, models/pv.  Times are the seams' (copy of the lengths, one kernel," % (n, L),
+             "the wait), inputs packed and uploaded once: 3 warm-up calls, then the median of 20", ""]
+    emit = lambda s: (lines.append(s), print(s, flush=True))
+    res = run_child(["time-ais"], 600)
+    med = lambda k: 1e6 * float(np.median(res[k]))
+    span = lambda k: "min %.0f, max %.0f" % (1e6 * min(res[k]), 1e6 * max(res[k]))
+    for cov, label in (("cov", "with covariances"), ("means", "means only      ")):
+        a, b, c = med("linear_radar_" + cov), med("ais_radar_" + cov), med("ais_ais_" + cov)
+        emit("%s  mht_smooth_tracks                       radar-only batch: %8.0f us (%s)" % (label, a, span("linear_radar_" + cov)))
+        emit("%s  mht_smooth_tracks_ais                   radar-only batch: %8.0f us (%s)   / linear: %.2f" % (label, b, span("ais_radar_" + cov), b / a))
+        emit("%s  mht_smooth_tracks_ais  %4.1f %% AIS nodes, %d leg entries: %8.0f us (%s)   / linear: %.2f   / itself radar-only: %.2f"
+             % (label, 100 * res["ais_share"], res["ais_legs"], c, span("ais_ais_" + cov), c / a, c / b))
+        emit("")
+    emit("(the radar-only batch runs the linear kernel's arithmetic through the new kernel: what it pays on top is one byte load of `kind` per node and pass and the")
+    emit(" second filtered slot's stride in the workspace; the leg gather and the two extra steps are paid by AIS nodes only -- but by the whole wavefront, whose lanes")
+    emit(" without a message wait while the others walk their legs: with 30 % AIS nodes nearly every wavefront step has one)")
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
 def run_child(args, timeout, prefix=()):
     cmd = list(prefix) + [sys.executable, os.path.abspath(__file__)] + list(args)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
@@ -245,7 +328,7 @@ def kernel_times(prof_dir):
 
 def main():
     import smooth_ref as sr
-    out_path, n_ref, ct_mode = None, 50, False
+    out_path, n_ref, ct_mode, ais_mode = None, 50, False, False
     argv = sys.argv[1:]
     while argv:
         a = argv.pop(0)
@@ -255,9 +338,13 @@ def main():
             n_ref = int(argv.pop(0))
         elif a == "--ct":
             ct_mode = True
+        elif a == "--ais":
+            ais_mode = True
     if out_path is None:
-        out_path = os.path.join(os.environ.get("OUT_DIR", os.path.join(ROOT, "out")), "smooth_ct_cost.txt" if ct_mode else "smooth_cost.txt")
+        out_path = os.path.join(os.environ.get("OUT_DIR", os.path.join(ROOT, "out")), "smooth_ais_cost.txt" if ais_mode else "smooth_ct_cost.txt" if ct_mode else "smooth_cost.txt")
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    if ais_mode:
+        return main_ais(out_path)
     if ct_mode:
         return main_ct(out_path)
     lines = ["tools/smooth_cost.py: the device Rauch-Tung-Striebel smoother (mht_smooth_tracks, one track per lane) against the float64 NumPy recursion",
@@ -318,6 +405,8 @@ if __name__ == "__main__":
         child_time_ct()
     elif len(sys.argv) > 1 and sys.argv[1] == "accuracy-ct":
         child_accuracy_ct()
+    elif len(sys.argv) > 1 and sys.argv[1] == "time-ais":
+        child_time_ais()
     elif len(sys.argv) > 1 and sys.argv[1] == "trace-ct":
         child_trace_ct()
     else:
