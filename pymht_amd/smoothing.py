@@ -25,6 +25,13 @@ from . import _lib
 from .device import Context
 
 
+# model kind -> the seam, its workspace sizer, whether the sizer takes nx in front of (n_tracks, L_max); the AIS seam takes its per-node
+# arrays and the leg table between has_z and xs, the argument lists are the same otherwise
+_SEAMS = {"linear": ("mht_smooth_tracks", "mht_smooth_work_bytes", True),
+          "ct": ("mht_smooth_tracks_ct", "mht_smooth_ct_work_bytes", False),
+          "ais": ("mht_smooth_tracks_ais", "mht_smooth_ais_work_bytes", False)}
+
+
 def _check_model(model):
     if getattr(model, "transition", None) == "ct":
         raise NotImplementedError("smoothing: the transition of model %r depends on the state (Phi(T, w) per hypothesis, models/ct.py); the "
@@ -170,7 +177,7 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
     P_d = up(P0).permute(1, 0).contiguous()
     xs_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
     Ps_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev) if covariances else None
-    lib = ctx.lib
+    lib, extra = ctx.lib, ()
     if ais is not None:      # the per-node AIS inputs next to z / has_z, and the leg table
         per_track, legs = ais
         kp = hp.copy()
@@ -188,9 +195,9 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
         r_d = up(rp).permute(1, 0).contiguous()
         l_d = up(lp).permute(1, 0).contiguous()
         legs_d = up(legs) if len(legs) else None
-        need = int(lib.mht_smooth_ais_work_bytes(n, L_max))
-    else:
-        need = int(lib.mht_smooth_ct_work_bytes(n, L_max) if constant_turn else lib.mht_smooth_work_bytes(nx, n, L_max))
+        extra = (k_d.data_ptr(), m_d.data_ptr(), r_d.data_ptr(), l_d.data_ptr(), legs_d.data_ptr() if len(legs) else None, len(legs))
+    seam, sizer, sizer_takes_nx = _SEAMS["ais" if ais is not None else "ct" if constant_turn else "linear"]
+    need = int(getattr(lib, sizer)(*((nx,) if sizer_takes_nx else ()), n, L_max))
     work = torch.empty(need, dtype=torch.uint8, device=dev)
     # (the constant-turn seam builds its own transition per node: Phi(T, 0) stands in the struct and is not read)
     keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in (model.Phi(period), model.Q(period), model.C_RADAR, model.R_RADAR())]
@@ -198,15 +205,9 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
     mx = _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 1 if constant_turn else 0, period)
     lens_sorted = np.ascontiguousarray(lens[order])
     torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    if ais is not None:
-        _lib.check(lib.mht_smooth_tracks_ais(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                                             z_d.data_ptr(), h_d.data_ptr(), k_d.data_ptr(), m_d.data_ptr(), r_d.data_ptr(), l_d.data_ptr(),
-                                             legs_d.data_ptr() if len(legs) else None, len(legs), xs_d.data_ptr(),
-                                             Ps_d.data_ptr() if covariances else None, work.data_ptr(), need), lib)
-    else:
-        seam = lib.mht_smooth_tracks_ct if constant_turn else lib.mht_smooth_tracks
-        _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                        z_d.data_ptr(), h_d.data_ptr(), xs_d.data_ptr(), Ps_d.data_ptr() if covariances else None, work.data_ptr(), need), lib)
+    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
+                                  z_d.data_ptr(), h_d.data_ptr(), *extra, xs_d.data_ptr(), Ps_d.data_ptr() if covariances else None,
+                                  work.data_ptr(), need), lib)
     xs = xs_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
     Ps = None
     if covariances:      # packed upper triangle -> full matrices, still on the device

@@ -91,7 +91,7 @@ def _host_lib(tmp_path_factory):
     gxx = shutil.which("g++") or "g++"
     so = str(tmp_path_factory.mktemp("smooth_ais_host") / "libsmooth_ais_host.so")
     subprocess.check_call([gxx, "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-shared", "-fPIC",
-                           os.path.join(ROOT, "tests", "hostmath", "smooth_ais_host.cpp"), "-o", so])
+                           os.path.join(ROOT, "tests", "hostmath", "smooth_host.cpp"), "-o", so])
     lib = C.CDLL(so)
     lib.smooth_ais_host.restype = None
     lib.smooth_ais_host.argtypes = [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 11 + [C.c_int32]

@@ -93,7 +93,7 @@ def _host_lib(tmp_path_factory):
     gxx = shutil.which("g++") or "g++"
     so = str(tmp_path_factory.mktemp("smooth_ct_host") / "libsmooth_ct_host.so")
     subprocess.check_call([gxx, "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-shared", "-fPIC",
-                           os.path.join(ROOT, "tests", "hostmath", "smooth_ct_host.cpp"), "-o", so])
+                           os.path.join(ROOT, "tests", "hostmath", "smooth_host.cpp"), "-o", so])
     lib = C.CDLL(so)
     lib.smooth_ct_host.restype = None
     lib.smooth_ct_host.argtypes = [C.c_double] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 6 + [C.c_int32]

@@ -4,7 +4,7 @@ per-lane numbers and not a 6 x 6 matrix (csrc/mht_smooth_ct_math.h), and float64
 may push a kernel that already fills the register file into scratch.  Figures as read from the compiled objects."""
 import pytest
 
-from test_smooth_resources import _report
+from test_smooth_resources import _check_instances, _report
 
 # instance -> (VGPRs, AGPRs) the compiler reports (identical in the two builds); the assertion is "no more than this", plus: no scratch,
 # no spill, no LDS, and VGPRs + AGPRs within the 512 entries one wavefront per SIMD can have
@@ -16,15 +16,4 @@ READ = {
 
 @pytest.mark.parametrize("build_nx", [4, 6])
 def test_constant_turn_smoother_kernels_do_not_spill(build_nx, tmp_path):
-    found = _report(tmp_path, ["-DMHT_NX=6"] if build_nx == 6 else [])
-    for kern, (vgpr, agpr) in READ.items():
-        hits = [(k, v) for k, v in found.items() if kern in k]
-        assert len(hits) == 1, "kernel %s: %d instances in the compiler report of mht_smooth.hip (%d-state build)" % (kern, len(hits), build_nx)
-        name, r = hits[0]
-        print(name, r)
-        # (SGPR "spills" are not asserted, as for the linear kernels: wave-uniform model entries parked in lanes of a vector register)
-        assert r["spill"] == 0, "%s spills %d VGPRs" % (name, r["spill"])
-        assert r["scratch"] == 0, "%s uses %d B of scratch per lane: a matrix is indexed dynamically or registers spill" % (name, r["scratch"])
-        assert r["lds"] == 0, "%s uses %d B of LDS" % (name, r["lds"])
-        assert r["vgpr"] <= vgpr and r["agpr"] <= agpr, "%s needs %d VGPRs + %d AGPRs (read when written: %d + %d)" % (name, r["vgpr"], r["agpr"], vgpr, agpr)
-        assert r["vgpr"] + r["agpr"] <= 512
+    _check_instances(_report(tmp_path, ["-DMHT_NX=6"] if build_nx == 6 else []), READ, build_nx)

@@ -1,5 +1,6 @@
-"""CPU (cross-compile only): the smoother's kernels (csrc/mht_smooth.hip: smooth_rts_kernel<NX, COV>, NX = 4 and 6, with and without the
-covariance recursion) in both code objects.  One track per lane with every matrix in registers: the six-state covariance kernel keeps
+"""CPU (cross-compile only): the linear smoother's kernels (csrc/mht_smooth.hip: smooth_rts_kernel<NX, COV>, NX = 4 and 6, with and without
+the covariance recursion) in both code objects; tests/test_smooth_ct_resources.py and test_smooth_ais_resources.py hold the file's other
+kernels to the same (_report, _check_instances).  One track per lane with every matrix in registers: the six-state covariance kernel keeps
 Pf, A Pf, the Cholesky factor, G and Ps - Pp live in one backward step and takes most of a lane's 512-entry register file (the compiler
 parks part of it in the accumulator half).  What must not happen is a spill: scratch is 0 B with fully unrolled, statically indexed
 matrices, and a later change that makes them spill or index dynamically is seen here.  Figures as read from the compiled objects."""
@@ -46,10 +47,10 @@ def _report(tmp_path, extra):
     return found
 
 
-@pytest.mark.parametrize("build_nx", [4, 6])
-def test_smoother_kernels_do_not_spill(build_nx, tmp_path):
-    found = _report(tmp_path, ["-DMHT_NX=6"] if build_nx == 6 else [])
-    for kern, (vgpr, agpr) in READ.items():
+def _check_instances(found, read, build_nx):
+    """What every smoother kernel is held to: exactly one instance per name in `read`, no VGPR spill, no scratch, no LDS, no more VGPRs and
+    AGPRs than `read` says, and their sum within the 512 entries one wavefront per SIMD can have."""
+    for kern, (vgpr, agpr) in read.items():
         hits = [(k, v) for k, v in found.items() if kern in k]
         assert len(hits) == 1, "kernel %s: %d instances in the compiler report of mht_smooth.hip (%d-state build)" % (kern, len(hits), build_nx)
         name, r = hits[0]
@@ -62,6 +63,11 @@ def test_smoother_kernels_do_not_spill(build_nx, tmp_path):
         assert r["lds"] == 0, "%s uses %d B of LDS" % (name, r["lds"])
         assert r["vgpr"] <= vgpr and r["agpr"] <= agpr, "%s needs %d VGPRs + %d AGPRs (read when written: %d + %d)" % (name, r["vgpr"], r["agpr"], vgpr, agpr)
         assert r["vgpr"] + r["agpr"] <= 512
+
+
+@pytest.mark.parametrize("build_nx", [4, 6])
+def test_smoother_kernels_do_not_spill(build_nx, tmp_path):
+    _check_instances(_report(tmp_path, ["-DMHT_NX=6"] if build_nx == 6 else []), READ, build_nx)
 
 
 def test_smoother_seam_is_declared_and_exported_by_both_builds():
