@@ -2733,9 +2733,7 @@ __global__ __launch_bounds__(BLP_THREADS) void blp_light_batch_kernel(const PBat
     blp_stamp_end(a);
 }
 int launch_blp_light_batch(mht_ctx* ctx, const PBatch& av, int n_sectors, int grid_x) {
-    hipLaunchKernelGGL(blp_light_batch_kernel, dim3(grid_x, n_sectors), dim3(BLP_THREADS), 0, ctx->stream, av);
-    MHT_HIP_CHECK(hipGetLastError());
-    return MHT_OK;
+    return launch_kernel(ctx, K_BLP_LIGHT_BATCH, blp_light_batch_kernel, dim3(grid_x, n_sectors), dim3(BLP_THREADS), 0, false, av);
 }
 
 // Cluster-sharded trackers (several devices hold identical forests and solve disjoint sets of clusters): after the selections have
@@ -2793,14 +2791,7 @@ int launch_blp_epilogue(mht_ctx* ctx, const BlpArgs& a, const int32_t* nT_dev, i
 }
 
 int launch_blp_batch(mht_ctx* ctx, const PBatch& av, int n_sectors, int grid_x, size_t lds) {
-    static size_t attr = 0;
-    if (lds > 48 * 1024 && lds > attr) {
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(blp_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
-    hipLaunchKernelGGL(blp_batch_kernel, dim3(grid_x, n_sectors), dim3(BLP_THREADS), lds, ctx->stream, av);
-    MHT_HIP_CHECK(hipGetLastError());
-    return MHT_OK;
+    return launch_kernel(ctx, K_BLP_BATCH, blp_batch_kernel, dim3(grid_x, n_sectors), dim3(BLP_THREADS), lds, false, av);
 }
 
 // the LDS tier of an argument block: tier 0 = the only launch (default footprint), 1 = small footprint first, 2 = default footprint
@@ -2836,10 +2827,6 @@ int launch_blp(mht_ctx* ctx, const BlpArgs& a, int grid) {
         set_error("blp: %d measurement nodes do not fit the solver's LDS tables", a.n_mnodes);
         return MHT_E_CAPACITY;
     }
-    if (ctx->lds_attr_blp < lds) {
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(blp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        ctx->lds_attr_blp = lds;
-    }
     if (b.uf_epoch) {      // clusters from the grow launch's union-find
         size_t body = lds > uf_prologue_bytes((size_t)b.uf_cap) ? lds : uf_prologue_bytes((size_t)b.uf_cap);
         body = (body + 15) & ~(size_t)15;
@@ -2849,17 +2836,9 @@ int launch_blp(mht_ctx* ctx, const BlpArgs& a, int grid) {
             set_error("blp: the union-find prologue of %d targets does not fit the launch's LDS (%zu bytes)", b.uf_cap, lds_uf);
             return MHT_E_CAPACITY;
         }
-        if (ctx->lds_attr_blp_uf < lds_uf) {
-            MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(blp_uf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_uf));
-            ctx->lds_attr_blp_uf = lds_uf;
-        }
-        hipLaunchKernelGGL(blp_uf_kernel, dim3(grid), dim3(BLP_THREADS), lds_uf, ctx->stream, b);
-        MHT_HIP_CHECK(hipGetLastError());
-        return MHT_OK;
+        return launch_kernel(ctx, K_BLP_UF, blp_uf_kernel, dim3(grid), dim3(BLP_THREADS), lds_uf, false, b);
     }
-    hipLaunchKernelGGL(blp_kernel, dim3(grid), dim3(BLP_THREADS), lds, ctx->stream, b);
-    MHT_HIP_CHECK(hipGetLastError());
-    return MHT_OK;
+    return launch_kernel(ctx, K_BLP, blp_kernel, dim3(grid), dim3(BLP_THREADS), lds, false, b);
 }
 
 __global__ void blp_objective_kernel(const int32_t* sel, const double* cost, int nT, const int32_t* st, const int32_t* it,

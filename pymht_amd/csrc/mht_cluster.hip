@@ -508,7 +508,6 @@ size_t cluster_lds_bytes(int Tcap, int n_mnodes) {
 
 int launch_cluster(mht_ctx* ctx, const ClusterArgs& a_in, const InitArgs* init, const int32_t* sticky_overflow) {
     ClusterArgs a = a_in;
-    size_t& attr_bytes = ctx->lds_attr_cluster;
     if (a.n_mnodes > 65536 || a.Tcap > 65536) {
         set_error("cluster: %d targets / %d measurement nodes exceed the 16 + 16 bits of an edge record", a.Tcap, a.n_mnodes);
         return MHT_E_CAPACITY;
@@ -521,29 +520,13 @@ int launch_cluster(mht_ctx* ctx, const ClusterArgs& a_in, const InitArgs* init, 
         }
         a.elds = CL_ELDS_MAX; a.pcap = CL_PEND_MAX;
         const size_t lds_big = (size_t)(a.elds + a.pcap) * 4;
-        static size_t attr_big = 0;
-        if (lds_big > 48 * 1024 && lds_big > attr_big) {
-            MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(cluster_big_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big));
-            attr_big = lds_big;
-        }
         // (the initiator, if one was handed in, does not ride along: the caller runs it behind the scan, mht_forest.hip)
-        hipLaunchKernelGGL(cluster_big_kernel, dim3(1), dim3(CL_THREADS), lds_big, ctx->stream, a);
-        MHT_HIP_CHECK(hipGetLastError());
-        return MHT_OK;
+        return launch_kernel(ctx, K_CLUSTER_BIG, cluster_big_kernel, dim3(1), dim3(CL_THREADS), lds_big, false, a);
     }
     cluster_carve(a.Tcap, a.n_mnodes, a.elds, a.pcap);
     const size_t lds = cluster_lds_bytes(a.Tcap, a.n_mnodes);
-    if (lds > 48 * 1024 && lds > attr_bytes) {
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(cluster_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(cluster_init_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_bytes = lds;
-    }
-    if (init) hipLaunchKernelGGL(cluster_init_kernel, dim3(2), dim3(CL_THREADS), lds, ctx->stream, a, *init, sticky_overflow);
-    else hipLaunchKernelGGL(cluster_kernel, dim3(1), dim3(CL_THREADS), lds, ctx->stream, a);
-    MHT_HIP_CHECK(hipGetLastError());
-    return MHT_OK;
+    if (init) return launch_kernel(ctx, K_CLUSTER_INIT, cluster_init_kernel, dim3(2), dim3(CL_THREADS), lds, false, a, *init, sticky_overflow);
+    return launch_kernel(ctx, K_CLUSTER, cluster_kernel, dim3(1), dim3(CL_THREADS), lds, false, a);
 }
 
 // the LDS carve (elds, pcap) of a forest's argument block, as launch_cluster sets it
@@ -554,14 +537,7 @@ void cluster_prepare(ClusterArgs& a) {
 
 int launch_cluster_batch(mht_ctx* ctx, const PBatch& av, int n_sectors, int Tcap, int n_mnodes) {
     const size_t lds = cluster_lds_bytes(Tcap, n_mnodes);
-    static size_t attr_bytes = 0;
-    if (lds > 48 * 1024 && lds > attr_bytes) {
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(cluster_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_bytes = lds;
-    }
-    hipLaunchKernelGGL(cluster_batch_kernel, dim3(1, n_sectors), dim3(CL_THREADS), lds, ctx->stream, av);
-    MHT_HIP_CHECK(hipGetLastError());
-    return MHT_OK;
+    return launch_kernel(ctx, K_CLUSTER_BATCH, cluster_batch_kernel, dim3(1, n_sectors), dim3(CL_THREADS), lds, false, av);
 }
 
 }  // namespace mht

@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libmht_amd.so (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
@@ -89,6 +90,16 @@ struct DevStatus {
 
 struct Forest;
 
+// Every kernel instance that is launched with dynamic LDS has a slot: the index of its mark in mht_ctx::lds_raised (launch_kernel below).
+// The grow launch's instances are a table of their own (mht_fgrow.hip: family x path-record width x leaves per pass), its entries
+// follow K_FGROW in table order.
+enum FgFamily : int { FG_PLAIN, FG_WAVE, FG_ADM, FG_AIS, FG_CT, FG_BATCH, FG_BATCH_WAVE, FG_FAMILIES };
+enum KernelSlot : int {
+    K_GATE, K_CLUSTER, K_CLUSTER_INIT, K_CLUSTER_BIG, K_CLUSTER_BATCH, K_BLP, K_BLP_UF, K_BLP_BATCH, K_BLP_LIGHT_BATCH,
+    K_FGROW,
+    K_SLOTS = K_FGROW + FG_FAMILIES * 3 * 2
+};
+
 // Copy an argument block that lives in HBM (written once by the host) into registers through the CONSTANT address space: scalar
 // loads, shared by the whole wavefront (batched launches: blockIdx.y picks the sector's block).
 template <typename T>
@@ -111,6 +122,32 @@ struct mht_ctx {
     unsigned gate_epoch = 0;
     mht::DevStatus* status = nullptr;   // device
     mht::Forest* forest = nullptr;
-    // dynamic-LDS limits already raised with hipFuncSetAttribute (per context: the attribute is per device)
-    size_t lds_attr_gate = 0, lds_attr_cluster = 0, lds_attr_blp = 0, lds_attr_fgrow = 0, lds_attr_blp_uf = 0;
+    // dynamic-LDS limit of each kernel instance as this context last raised it (launch_kernel below; 0: never).  Per context and
+    // not per process: the attribute belongs to the function ON ONE DEVICE, and contexts are created on any device they are given.
+    size_t lds_raised[mht::K_SLOTS] = {};
 };
+
+namespace mht {
+
+// THE way a kernel with dynamic LDS is started: raises the instance's limit the first time this context launches it above the 48 KB
+// every function gets by default (and again when a later launch asks for more), launches on the context's stream -- any_order:
+// hipExtAnyOrderLaunch, the launch may start while the one in front of it in the stream is still running -- and reports what the
+// runtime says.  The arguments travel by value, converted to the kernel's own parameter types as in a direct launch.
+template <typename... P, typename... A>
+int launch_kernel(mht_ctx* ctx, KernelSlot slot, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, bool any_order, const A&... args) {
+    if (!kernel) {
+        set_error("launch_kernel: kernel instance %d is not part of this build", (int)slot);
+        return MHT_E_INVALID;
+    }
+    size_t& raised = ctx->lds_raised[slot];
+    if (lds > 48 * 1024 && lds > raised) {
+        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        raised = lds;
+    }
+    if (any_order) hipExtLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
+    MHT_HIP_CHECK(hipGetLastError());
+    return MHT_OK;
+}
+
+}  // namespace mht

@@ -243,35 +243,41 @@ size_t fgrow_wave_lds_bytes(int W, int pds, int AW) {      // (the batched launc
     return b < 256 ? 256 : b;
 }
 
-static int fgrow_lds_attr(mht_ctx* ctx, size_t lds) {
+// The instances of the grow launch: [family][path-record width PQ = 2, 4, 8][leaves per pass: 0 = FG_CAP, 1 = FG_CAP_SOLO] (families
+// with one capacity: column 0).  Row-major position = the instance's launch slot behind K_FGROW.  An instance that is not in this table
+// cannot be launched.
+union FgFn {
+    void (*solo)(const FGrowArgs, const CommitArgs, const FDyn, const PublishArgs);
+    void (*adm)(const FGrowArgs, const CommitArgs, const FDyn, const PublishArgs, const AddArgs);
+    void (*batch)(const FBatch);
+    constexpr FgFn() : solo(nullptr) {}
+    constexpr FgFn(decltype(solo) k) : solo(k) {}
+    constexpr FgFn(decltype(adm) k) : adm(k) {}
+    constexpr FgFn(decltype(batch) k) : batch(k) {}
+};
+static const FgFn FG_TABLE[FG_FAMILIES][3][2] = {
+    /* FG_PLAIN      */ {{fgrow_kernel<2, FG_CAP>, fgrow_kernel<2>}, {fgrow_kernel<4, FG_CAP>, fgrow_kernel<4>}, {}},
+    /* FG_WAVE       */ {{fgrow_kernel<2, 0>}, {fgrow_kernel<4, 0>}, {}},
+    /* FG_ADM        */ {{fgrow_adm_kernel<2, FG_CAP>, fgrow_adm_kernel<2>}, {fgrow_adm_kernel<4, FG_CAP>, fgrow_adm_kernel<4>}, {}},
+    /* FG_AIS        */ {{fgrow_ais_kernel<2>}, {fgrow_ais_kernel<4>}, {fgrow_ais_kernel<8>}},      // (<8>: 32-int records, N >= 8)
+#if MHT_NX == 6
+    /* FG_CT         */ {{fgrow_ct_kernel<2>}, {fgrow_ct_kernel<4>}, {}},
+#else
+    /* FG_CT         */ {},
+#endif
+    /* FG_BATCH      */ {{fgrow_batch_kernel<2>}, {fgrow_batch_kernel<4>}, {}},
+    /* FG_BATCH_WAVE */ {{fgrow_batch_kernel<2, 0>}, {fgrow_batch_kernel<4, 0>}, {}},
+};
+struct FgPick { FgFn fn; KernelSlot slot; };
+static FgPick fgrow_pick(FgFamily fam, int pds, bool wide) {
+    const int pq = pds == 8 ? 0 : (fam == FG_AIS && pds != 16) ? 2 : 1;
+    return {FG_TABLE[fam][pq][wide ? 1 : 0], (KernelSlot)(K_FGROW + (fam * 3 + pq) * 2 + (wide ? 1 : 0))};
+}
+
+static int fgrow_lds_check(size_t lds) {
     if (lds > 150 * 1024) {
         set_error("fgrow: %zu bytes of LDS per workgroup (max_meas / window too large)", lds);
         return MHT_E_CAPACITY;
-    }
-    size_t& attr_bytes = ctx->lds_attr_fgrow;
-    if (lds > 48 * 1024 && lds > attr_bytes) {
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_kernel<2, FG_CAP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_kernel<4, FG_CAP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_batch_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_batch_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_kernel<2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_kernel<4, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_batch_kernel<2, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_batch_kernel<4, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_adm_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_adm_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_adm_kernel<2, FG_CAP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_adm_kernel<4, FG_CAP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ais_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ais_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ais_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#if MHT_NX == 6
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ct_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fgrow_ct_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#endif
-        attr_bytes = lds;
     }
     return MHT_OK;
 }
@@ -297,114 +303,46 @@ void fgrow_plan(FDyn& d, int n_targets_ub, int Tcap, bool fused, bool wave) {
 int launch_fgrow(mht_ctx* ctx, const FGrowArgs& a, FDyn& d, int n_targets_ub, const CommitArgs* commit, const PublishArgs* publish, const AddArgs* adm, bool any_order) {
     static int wave_solo = -1;      // development: MHT_FG_WAVE_SOLO=1 runs the wavefront-per-target variant in the one-sector launch too
     if (wave_solo < 0) { const char* e = getenv("MHT_FG_WAVE_SOLO"); wave_solo = (e && e[0] == '1') ? 1 : 0; }
-    if (adm) {      // the commit and the admission of the initiator's births ride along (fgrow_adm_kernel)
-        MHT_REQUIRE(commit && a.ais.half == 0, "launch_fgrow: the admission rides with the commit, in a forest without AIS records");
-        fgrow_plan(d, n_targets_ub, a.Tcap, true, false);
+    // the family: the commit and the admission of the initiator's births ride along (fgrow_adm_kernel) / constant-turn forest: its own
+    // kernel, no chain workgroups / AIS forest: its own kernel on every scan (records in two halves, identities per node) / one sector
+    FgFamily fam = adm ? FG_ADM : a.ais.half > 0 ? FG_AIS : wave_solo ? FG_WAVE : FG_PLAIN;
+#if MHT_NX == 6
+    if (!adm && a.ct.on) fam = FG_CT;
+#endif
+    if (adm) MHT_REQUIRE(commit && a.ais.half == 0, "launch_fgrow: the admission rides with the commit, in a forest without AIS records");
+    fgrow_plan(d, n_targets_ub, a.Tcap, commit != nullptr, fam == FG_WAVE);
+    if (fam == FG_CT) d.n_chain = 0;
+    bool wide = false;
+    size_t lds;
+    if (fam == FG_CT) lds = fgrow_ct_lds_bytes(d.W, a.pds, a.AW);
+    else if (fam == FG_AIS) lds = fgrow_lds_bytes_cap(d.W, a.pds, a.AW, FG_CAP) + (size_t)FG_CAP * (16 + sizeof(FLeafX));      // (+ s_ais, lgx)
+    else if (fam == FG_WAVE) lds = fgrow_wave_lds_bytes(d.W, a.pds, a.AW);
+    else {
+        // 128 leaves per pass unless the larger tables cost a workgroup per CU (long scans: the hit masks grow with the scan): 3 per CU is
+        // all the launch bounds allow, fewer than with 96 leaves per pass is a loss (config-5 size, 2 048 measurements: 1 instead of 2)
         const size_t lds_hi = fgrow_lds_bytes_cap(d.W, a.pds, a.AW, FG_CAP_SOLO), lds_lo = fgrow_lds_bytes_cap(d.W, a.pds, a.AW, FG_CAP);
         auto per_cu = [](size_t b) { const size_t n = (size_t)160 * 1024 / b; return n > 3 ? (size_t)3 : n; };
-        const bool wide = per_cu(lds_hi) >= per_cu(lds_lo);
-        size_t lds = wide ? lds_hi : lds_lo;
-        const size_t need0 = (size_t)(64 + ADM_LDS_INTS) * sizeof(int);      // workgroup 0: commit partials + admission list
-        if (lds < need0) lds = need0;
-        { const int rc = fgrow_lds_attr(ctx, lds); if (rc) return rc; }
-        const bool pub = publish && publish->dst;
-        const int grid = fgrow_grid(d) + FG_BORN_WGS + FG_BORN_CHAIN_WGS + (pub ? FG_PUB_WGS : 0);
-        const PublishArgs pa = pub ? *publish : PublishArgs{};
-        if (any_order && d.ovl && d.adm_wait) {
-            const dim3 g(grid), b(FG_THREADS);
-            if (a.pds == 8 && wide) hipExtLaunchKernelGGL((fgrow_adm_kernel<2>), g, b, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, a, *commit, d, pa, *adm);
-            else if (a.pds == 8) hipExtLaunchKernelGGL((fgrow_adm_kernel<2, FG_CAP>), g, b, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, a, *commit, d, pa, *adm);
-            else if (wide) hipExtLaunchKernelGGL((fgrow_adm_kernel<4>), g, b, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, a, *commit, d, pa, *adm);
-            else hipExtLaunchKernelGGL((fgrow_adm_kernel<4, FG_CAP>), g, b, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, a, *commit, d, pa, *adm);
-            MHT_HIP_CHECK(hipGetLastError());
-            return MHT_OK;
-        }
-        if (a.pds == 8 && wide) hipLaunchKernelGGL(fgrow_adm_kernel<2>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, *commit, d, pa, *adm);
-        else if (a.pds == 8) hipLaunchKernelGGL((fgrow_adm_kernel<2, FG_CAP>), dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, *commit, d, pa, *adm);
-        else if (wide) hipLaunchKernelGGL(fgrow_adm_kernel<4>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, *commit, d, pa, *adm);
-        else hipLaunchKernelGGL((fgrow_adm_kernel<4, FG_CAP>), dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, *commit, d, pa, *adm);
-        MHT_HIP_CHECK(hipGetLastError());
-        return MHT_OK;
+        wide = per_cu(lds_hi) >= per_cu(lds_lo);
+        lds = wide ? lds_hi : lds_lo;
+        const size_t need0 = (size_t)(64 + ADM_LDS_INTS) * sizeof(int);      // workgroup 0 of the admission: commit partials + admission list
+        if (adm && lds < need0) lds = need0;
     }
-#if MHT_NX == 6
-    if (a.ct.on) {      // constant-turn forest: its own kernel, no chain workgroups
-        fgrow_plan(d, n_targets_ub, a.Tcap, commit != nullptr, false);
-        d.n_chain = 0;
-        const size_t lds = fgrow_ct_lds_bytes(d.W, a.pds, a.AW);
-        { const int rc = fgrow_lds_attr(ctx, lds); if (rc) return rc; }
-        const bool pub = publish && publish->dst;
-        const int grid = fgrow_grid(d) + (pub ? FG_PUB_WGS : 0);
-        const PublishArgs pa = pub ? *publish : PublishArgs{};
-        const CommitArgs cm = commit ? *commit : CommitArgs{};
-        if (a.pds == 8) hipLaunchKernelGGL(fgrow_ct_kernel<2>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-        else hipLaunchKernelGGL(fgrow_ct_kernel<4>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-        MHT_HIP_CHECK(hipGetLastError());
-        return MHT_OK;
-    }
-#endif
-    if (a.ais.half > 0) {      // AIS forest: its own kernel on every scan (records in two halves, identities per node)
-        fgrow_plan(d, n_targets_ub, a.Tcap, commit != nullptr, false);
-        const size_t lds = fgrow_lds_bytes_cap(d.W, a.pds, a.AW, FG_CAP) + (size_t)FG_CAP * (16 + sizeof(FLeafX));      // (+ s_ais, lgx)
-        { const int rc = fgrow_lds_attr(ctx, lds); if (rc) return rc; }
-        const bool pub = publish && publish->dst;
-        const int grid = fgrow_grid(d) + (pub ? FG_PUB_WGS : 0);
-        const PublishArgs pa = pub ? *publish : PublishArgs{};
-        const CommitArgs cm = commit ? *commit : CommitArgs{};
-        if (a.pds == 8) hipLaunchKernelGGL(fgrow_ais_kernel<2>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-        else if (a.pds == 16) hipLaunchKernelGGL(fgrow_ais_kernel<4>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-        else hipLaunchKernelGGL(fgrow_ais_kernel<8>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);      // (32-int records: N >= 8)
-        MHT_HIP_CHECK(hipGetLastError());
-        return MHT_OK;
-    }
-    fgrow_plan(d, n_targets_ub, a.Tcap, commit != nullptr, wave_solo != 0);
-    if (wave_solo) {
-        const size_t lds = fgrow_wave_lds_bytes(d.W, a.pds, a.AW);
-        { const int rc = fgrow_lds_attr(ctx, lds); if (rc) return rc; }
-        const bool pub = publish && publish->dst;
-        const int grid = fgrow_grid(d) + (pub ? FG_PUB_WGS : 0);
-        const PublishArgs pa = pub ? *publish : PublishArgs{};
-        const CommitArgs cm = commit ? *commit : CommitArgs{};
-        if (a.pds == 8) hipLaunchKernelGGL((fgrow_kernel<2, 0>), dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-        else hipLaunchKernelGGL((fgrow_kernel<4, 0>), dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-        MHT_HIP_CHECK(hipGetLastError());
-        return MHT_OK;
-    }
-    // 128 leaves per pass unless the larger tables cost a workgroup per CU (long scans: the hit masks grow with the scan): 3 per CU is
-    // all the launch bounds allow, fewer than with 96 leaves per pass is a loss (config-5 size, 2 048 measurements: 1 instead of 2)
-    const size_t lds_hi = fgrow_lds_bytes_cap(d.W, a.pds, a.AW, FG_CAP_SOLO), lds_lo = fgrow_lds_bytes_cap(d.W, a.pds, a.AW, FG_CAP);
-    auto per_cu = [](size_t b) { const size_t n = (size_t)160 * 1024 / b; return n > 3 ? (size_t)3 : n; };
-    const bool wide = per_cu(lds_hi) >= per_cu(lds_lo);
-    const size_t lds = wide ? lds_hi : lds_lo;
-    { const int rc = fgrow_lds_attr(ctx, lds); if (rc) return rc; }
+    { const int rc = fgrow_lds_check(lds); if (rc) return rc; }
+    // the grid: [commit] + one workgroup per target slot + chain workgroups (+ the newborn targets' + the report's)
     const bool pub = publish && publish->dst;
-    const int grid = fgrow_grid(d) + (pub ? FG_PUB_WGS : 0);
+    const int grid = fgrow_grid(d) + (adm ? FG_BORN_WGS + FG_BORN_CHAIN_WGS : 0) + (pub ? FG_PUB_WGS : 0);
     const PublishArgs pa = pub ? *publish : PublishArgs{};
     const CommitArgs cm = commit ? *commit : CommitArgs{};
-    if (any_order && d.fused && d.ovl && !pub) {
-        const dim3 g(grid), b(FG_THREADS);
-        if (a.pds == 8 && wide) hipExtLaunchKernelGGL((fgrow_kernel<2>), g, b, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, a, cm, d, pa);
-        else if (a.pds == 8) hipExtLaunchKernelGGL((fgrow_kernel<2, FG_CAP>), g, b, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, a, cm, d, pa);
-        else if (wide) hipExtLaunchKernelGGL((fgrow_kernel<4>), g, b, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, a, cm, d, pa);
-        else hipExtLaunchKernelGGL((fgrow_kernel<4, FG_CAP>), g, b, lds, ctx->stream, nullptr, nullptr, hipExtAnyOrderLaunch, a, cm, d, pa);
-        MHT_HIP_CHECK(hipGetLastError());
-        return MHT_OK;
-    }
-    if (a.pds == 8 && wide) hipLaunchKernelGGL(fgrow_kernel<2>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-    else if (a.pds == 8) hipLaunchKernelGGL((fgrow_kernel<2, FG_CAP>), dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-    else if (wide) hipLaunchKernelGGL(fgrow_kernel<4>, dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-    else hipLaunchKernelGGL((fgrow_kernel<4, FG_CAP>), dim3(grid), dim3(FG_THREADS), lds, ctx->stream, a, cm, d, pa);
-    MHT_HIP_CHECK(hipGetLastError());
-    return MHT_OK;
+    const bool any = any_order && d.ovl && (adm ? d.adm_wait != 0 : fam == FG_PLAIN && d.fused && !pub);
+    const FgPick k = fgrow_pick(fam, a.pds, wide);
+    return adm ? launch_kernel(ctx, k.slot, k.fn.adm, dim3(grid), dim3(FG_THREADS), lds, any, a, cm, d, pa, *adm)
+               : launch_kernel(ctx, k.slot, k.fn.solo, dim3(grid), dim3(FG_THREADS), lds, any, a, cm, d, pa);
 }
 
 int launch_fgrow_batch(mht_ctx* ctx, const FBatch& b, int n_sectors, int grid_x, size_t lds, int pds, bool wave) {
-    { const int rc = fgrow_lds_attr(ctx, lds); if (rc) return rc; }
-    if (wave && pds == 8) hipLaunchKernelGGL((fgrow_batch_kernel<2, 0>), dim3(grid_x, n_sectors), dim3(FG_THREADS), lds, ctx->stream, b);
-    else if (wave) hipLaunchKernelGGL((fgrow_batch_kernel<4, 0>), dim3(grid_x, n_sectors), dim3(FG_THREADS), lds, ctx->stream, b);
-    else if (pds == 8) hipLaunchKernelGGL(fgrow_batch_kernel<2>, dim3(grid_x, n_sectors), dim3(FG_THREADS), lds, ctx->stream, b);
-    else hipLaunchKernelGGL(fgrow_batch_kernel<4>, dim3(grid_x, n_sectors), dim3(FG_THREADS), lds, ctx->stream, b);
-    MHT_HIP_CHECK(hipGetLastError());
-    return MHT_OK;
+    { const int rc = fgrow_lds_check(lds); if (rc) return rc; }
+    const FgPick k = fgrow_pick(wave ? FG_BATCH_WAVE : FG_BATCH, pds, false);
+    return launch_kernel(ctx, k.slot, k.fn.batch, dim3(grid_x, n_sectors), dim3(FG_THREADS), lds, false, b);
 }
 
 int fgrow_grid_of(const FDyn& d) { return fgrow_grid(d); }

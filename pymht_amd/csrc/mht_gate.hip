@@ -481,15 +481,7 @@ int launch_gate(mht_ctx* ctx, GateArgs& a, int grid_leaves_hint) {
     a.max_resident = max_blocks;                      // more tiles than that: dynamic tile numbers (see grow_kernel)
     if (ntiles > max_blocks && !a.ticket)             // ticket word behind the tile states (cleared above)
         a.ticket = reinterpret_cast<int32_t*>(a.group_state + ntiles / 64 + 4);
-    size_t& attr_bytes = ctx->lds_attr_gate;
-    if (lds > 48 * 1024 && lds > attr_bytes) {
-        MHT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(grow_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_bytes = lds;
-    }
-    hipLaunchKernelGGL(grow_kernel, dim3(blocks), dim3(GATE_THREADS), lds, ctx->stream, a);
-    MHT_HIP_CHECK(hipGetLastError());
-    return MHT_OK;
+    return launch_kernel(ctx, K_GATE, grow_kernel, dim3(blocks), dim3(GATE_THREADS), lds, false, a);
 }
 
 void fill_model_only(Model& o, const mht_model* m) {
