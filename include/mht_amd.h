@@ -31,7 +31,7 @@ extern "C" {
 /* State dimension of the library build the header is used with: 4 (libmht_amd.so: the reference's CV model, models/pv.py) or 6
  * (libmht_amd6.so: the same sources compiled with -DMHT_NX=6 for BASELINE config 5's six-state model).  It sizes the model matrices
  * and the state vectors / covariances of the forest's reports; the stateless seams mht_gate_scan (4 states), mht_gate_scan_x and
- * mht_smooth_tracks (4 or 6 at run time), mht_smooth_tracks_ct (6) and mht_smooth_tracks_ais (4) do not depend on it. */
+ * mht_smooth_tracks and mht_smooth_tracks_em (4 or 6 at run time), mht_smooth_tracks_ct (6) and mht_smooth_tracks_ais (4) do not depend on it. */
 #ifndef MHT_NX
 #define MHT_NX 4
 #endif
@@ -252,6 +252,30 @@ int mht_smooth_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_trac
                           const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, const uint8_t* kind,
                           const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
                           double* xs, double* Ps, void* work, size_t work_bytes);
+
+/* ---- seam (v), EM: Q, R and the initial state learned per track by expectation-maximisation, then the smoother -- OPT-IN: nothing
+ * routes here unless the caller asks (em=5 in the Python API) ---------------------------------------------------------------------------
+ * What the reference's pykalman call does per track (pyTarget.py:580-609: em(n_iter = 5), then smooth), restated: the target is the
+ * algorithm (tests/smooth_em_ref.py), not pykalman's bits.  A and C stay the model's; theta = (Q, R, x0, P0) is per track and starts at
+ * the model's Q and R (widened) and the track's x_init, P_init.  One iteration, all four updated from the same E-step:
+ *   E-step   mht_smooth_tracks' forward and backward recursion under theta: xs_k, Ps_k, G_k, and X_k = Ps_{k+1} G_k' = Cov(x_{k+1}, x_k | z)
+ *   M-step   Q <- 1 / (L - 1) sum_{k = 0 .. L-2} [e e' + A Ps_k A' + Ps_{k+1} - X_k A' - A X_k'],  e = xs_{k+1} - A xs_k
+ *            R <- 1 / n_obs sum_{k: z_k present} [r r' + C Ps_k C'],  r = z_k - C xs_k;   x0 <- xs_0;   P0 <- Ps_0
+ *   a track of one node learns nothing (its output is its input, Q and R stay); a track without a measurement keeps R.
+ * After n_iter iterations (0 .. 64, else MHT_E_INVALID) one more E-step under the learned theta writes xs and Ps: n_iter == 0 gives
+ * mht_smooth_tracks' bits.  model: nx 4 or 6 and transition == 0 (else MHT_E_INVALID).  len, x_init, P_init, z, has_z, xs, Ps (may be
+ * NULL) and the layouts are mht_smooth_tracks'.  Next to them:
+ *   Q_out    dev [nx (nx + 1) / 2][n_tracks] f64 out: the learned Q, upper triangle row by row      R_out  dev [3][n_tracks] f64 out: r00, r01, r11
+ *   work     dev, work_bytes >= mht_smooth_em_work_bytes(nx, n_tracks, L_max) (>= mht_smooth_work_bytes of the same shape; 0 for a bad
+ *            nx or a negative size): MHT_E_INVALID if it is smaller.
+ * NOT POSITIVE DEFINITE: nothing keeps a re-estimated Q, R or P0 positive definite.  A track where one stops being so meets the square
+ * root of a negative number in a Cholesky factor and its xs, Ps, Q_out, R_out are NaN from there on -- that track's only: it never
+ * faults, and no other track's result depends on it.  One kernel launch per walk, n_iter + 1 in all, a wavefront running as long as its
+ * longest track in each.  Synchronises.  On MHT_E_INVALID nothing has been launched or written.  Exported by both builds. */
+size_t mht_smooth_em_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max);
+int mht_smooth_tracks_em(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                         const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_iter,
+                         double* xs, double* Ps, double* Q_out, double* R_out, void* work, size_t work_bytes);
 
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in

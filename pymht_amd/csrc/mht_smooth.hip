@@ -40,8 +40,10 @@
 // Workspace: the lengths, then the filtered slots of every node, [node][slot][element][track].  One slot, the filtered state at the
 // scan's time, for the linear and the constant-turn model; two for the AIS model: slot 1 is the filtered state at the message's time,
 // written for AIS nodes only.
+//
+// mht_smooth_tracks_em, the linear model with Q and R learned per track first, is a translation unit of its own: mht_smooth_em.hip.
 #include "mht_common.h"
-#include "mht_smooth_walk.h"
+#include "mht_smooth_seam.h"
 
 namespace mht {
 
@@ -63,48 +65,8 @@ __global__ void __launch_bounds__(64) smooth_ais_kernel(const SmoothArgs<4, AisS
     if (t < a.n) smooth_walk<4, COV>(a, t);
 }
 
-// mht_model_x's float32 matrices in float64 (exact): Q, C, R, and A where the model has one
-template <int N, typename Model>
-static void widen(const mht_model_x* m, Model& out, double* A = nullptr) {
-    if (A)
-        for (int i = 0; i < N * N; ++i) A[i] = (double)m->A[i];
-    for (int i = 0; i < N; ++i)
-        for (int j = i; j < N; ++j) out.Q[sym_idx(N, i, j)] = (double)m->Q[i * N + j];
-    for (int i = 0; i < 2 * N; ++i) out.C[i] = (double)m->C[i];
-    out.R[0] = (double)m->R[0]; out.R[1] = (double)m->R[1]; out.R[2] = (double)m->R[3];
-}
-
-static size_t smooth_len_bytes(int32_t n_tracks) { return (((size_t)n_tracks * 4 + 255) / 256) * 256; }
-
-static size_t smooth_work_bytes(int32_t nx, int32_t slots, int32_t n_tracks, int32_t L_max) {
-    return smooth_len_bytes(n_tracks) + (size_t)L_max * (size_t)slots * (size_t)(nx + nx * (nx + 1) / 2) * (size_t)n_tracks * 8;
-}
-
-struct SmoothBatch {      // what every seam is handed besides its model
-    int32_t n, L_max;
-    const int32_t* len;
-    const double *x_init, *P_init, *z;
-    const uint8_t* has_z;
-    double *xs, *Ps;
-    void* work;
-    size_t work_bytes;
-};
-
-// What the seams ask of a non-empty batch behind their own model checks
-static int check_batch(const char* seam, const char* sizer, int32_t nx, int32_t slots, const SmoothBatch& b, bool extras) {
-    MHT_REQUIRE(b.len && b.x_init && b.P_init && b.z && b.has_z && extras && b.xs && b.work, "%s: null array", seam);
-    for (int32_t t = 0; t < b.n; ++t)
-        MHT_REQUIRE(b.len[t] >= 1 && b.len[t] <= b.L_max, "%s: track %d has length %d (1 .. L_max = %d)", seam, t, b.len[t], b.L_max);
-    const size_t need = smooth_work_bytes(nx, slots, b.n, b.L_max);
-    if (b.work_bytes < need) {
-        set_error("%s: the workspace has %zu bytes, %zu are needed (%s)", seam, b.work_bytes, need, sizer);
-        return MHT_E_CAPACITY;
-    }
-    return MHT_OK;
-}
-
-// An empty batch is done; any other is checked, then the lengths go to the front of the workspace, the filtered means and covariances
-// behind them; then one launch (with_cov, or means_only without Ps) and a wait
+// An empty batch is done; any other is checked, then the lengths go to the workspace; then one launch (with_cov, or means_only without
+// Ps) and a wait
 template <int N, typename Steps>
 static int run_smooth(mht_ctx* ctx, const char* seam, const char* sizer, const Steps& steps, bool extras, const SmoothBatch& b,
                       void (*with_cov)(SmoothArgs<N, Steps>), void (*means_only)(SmoothArgs<N, Steps>)) {
@@ -112,14 +74,8 @@ static int run_smooth(mht_ctx* ctx, const char* seam, const char* sizer, const S
     const int rc = check_batch(seam, sizer, N, Steps::SLOTS, b, extras);
     if (rc != MHT_OK) return rc;
     MHT_HIP_CHECK(hipSetDevice(ctx->device));
-    SmoothArgs<N, Steps> a = {};
-    a.steps = steps;
-    a.n = b.n; a.L_max = b.L_max;
-    a.x_init = b.x_init; a.P_init = b.P_init; a.z = b.z; a.has_z = b.has_z; a.xs = b.xs; a.Ps = b.Ps;
-    char* q = static_cast<char*>(b.work);
-    a.len = reinterpret_cast<const int32_t*>(q); q += smooth_len_bytes(b.n);
-    a.xf = reinterpret_cast<double*>(q); q += (size_t)b.L_max * Steps::SLOTS * N * (size_t)b.n * 8;
-    a.Pf = reinterpret_cast<double*>(q);
+    SmoothArgs<N, Steps> a;
+    smooth_args<N>(steps, b, a);
     MHT_HIP_CHECK(hipMemcpyAsync(b.work, b.len, (size_t)b.n * 4, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(b.Ps ? with_cov : means_only, dim3((b.n + 63) / 64), dim3(64), 0, ctx->stream, a);
     MHT_HIP_CHECK(hipGetLastError());

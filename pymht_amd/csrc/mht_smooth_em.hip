@@ -1,0 +1,74 @@
+// mht_smooth_tracks_em (include/mht_amd.h): the linear smoother of mht_smooth.hip with Q, R and the initial state re-estimated per track by
+// expectation-maximisation before the smoothing walk, opt-in (em=5 in the Python API): what the reference's pykalman call does.  One
+// track per lane and track-minor memory as there.  The same lane walks its track n_iter + 1 times, one launch per walk
+// (mht_smooth_em.h says why, and what lives in registers and what in the workspace); Q and R are per lane, A and C stay wave-uniform.
+// Its workspace is the linear smoother's plus theta, the sums and one parked state per track.
+#include "mht_common.h"
+#include "mht_smooth_em.h"
+#include "mht_smooth_seam.h"
+
+namespace mht {
+
+template <int N, bool LAST>
+__global__ void __launch_bounds__(64) smooth_em_kernel(const SmoothEmArgs<N> a, const int first) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t < a.s.n) smooth_em_pass<N, LAST>(a, t, first != 0);
+}
+
+static size_t smooth_em_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max) {      // + theta, sq and pn of mht_smooth_em.h
+    return smooth_work_bytes(nx, 1, n_tracks, L_max) + (size_t)smooth_em_track_doubles(nx) * (size_t)n_tracks * 8;
+}
+
+}  // namespace mht
+
+using namespace mht;
+
+extern "C" size_t mht_smooth_em_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max) {
+    if ((nx != 4 && nx != 6) || n_tracks < 0 || L_max < 0) return 0;
+    return smooth_em_work_bytes(nx, n_tracks, L_max);
+}
+
+// n_iter + 1 launches of one walk each on the stream (mht_smooth_em.h says why not one), then a wait
+template <int N>
+static int run_em(mht_ctx* ctx, const mht_model_x* model, const SmoothBatch& b, int32_t n_iter, double* Q_out, double* R_out, KernelSlot slot) {
+    constexpr int NS = N * (N + 1) / 2;
+    if (b.n == 0) return MHT_OK;
+    const int rc = check_batch("mht_smooth_tracks_em", "mht_smooth_em_work_bytes", N, 1, b, Q_out && R_out);
+    if (rc != MHT_OK) return rc;
+    MHT_HIP_CHECK(hipSetDevice(ctx->device));
+    LinearSteps<N> steps = {};
+    widen<N>(model, steps.model, steps.model.A);
+    SmoothEmArgs<N> a = {};
+    char* q = smooth_args<N>(steps, b, a.s);
+    a.theta = reinterpret_cast<double*>(q); q += (size_t)(N + 2 * NS + 3) * (size_t)b.n * 8;
+    a.sq = reinterpret_cast<double*>(q); q += (size_t)(NS + 4) * (size_t)b.n * 8;
+    a.pn = reinterpret_cast<double*>(q);      // [NS + N][n]: with it the workspace holds smooth_em_track_doubles(N) per track
+    a.Q_out = Q_out; a.R_out = R_out;
+    MHT_HIP_CHECK(hipMemcpyAsync(b.work, b.len, (size_t)b.n * 4, hipMemcpyHostToDevice, ctx->stream));
+    for (int32_t it = 0; it <= n_iter; ++it) {
+        const int lrc = launch_kernel(ctx, slot, it == n_iter ? smooth_em_kernel<N, true> : smooth_em_kernel<N, false>, dim3((b.n + 63) / 64), dim3(64), 0,
+                                      false, a, it == 0 ? 1 : 0);
+        if (lrc != MHT_OK) {      // (the walks already queued read and write the caller's arrays: they are waited for before the error goes back)
+            (void)hipStreamSynchronize(ctx->stream);
+            return lrc;
+        }
+    }
+    MHT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return MHT_OK;
+}
+
+extern "C" int mht_smooth_tracks_em(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                                    const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_iter,
+                                    double* xs, double* Ps, double* Q_out, double* R_out, void* work, size_t work_bytes) {
+    MHT_REQUIRE(ctx && model, "mht_smooth_tracks_em: null argument");
+    MHT_REQUIRE(model->nx == 4 || model->nx == 6, "mht_smooth_tracks_em: nx must be 4 or 6 (got %d)", model->nx);
+    MHT_REQUIRE(model->transition == 0, "mht_smooth_tracks_em: a state-dependent transition (%d) has no linear smoother to learn under", model->transition);
+    MHT_REQUIRE(model->A && model->Q && model->C && model->R, "mht_smooth_tracks_em: null model matrix");
+    MHT_REQUIRE(n_iter >= 0 && n_iter <= SMOOTH_EM_MAX_ITER, "mht_smooth_tracks_em: n_iter must be 0 .. %d (got %d)", SMOOTH_EM_MAX_ITER, n_iter);
+    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_smooth_tracks_em: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
+    const size_t need = smooth_em_work_bytes(model->nx, n_tracks, L_max);
+    MHT_REQUIRE(n_tracks == 0 || work_bytes >= need, "mht_smooth_tracks_em: the workspace has %zu bytes, %zu are needed (mht_smooth_em_work_bytes)",
+                work_bytes, need);
+    const SmoothBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, xs, Ps, work, work_bytes};
+    return model->nx == 4 ? run_em<4>(ctx, model, b, n_iter, Q_out, R_out, K_SMOOTH_EM4) : run_em<6>(ctx, model, b, n_iter, Q_out, R_out, K_SMOOTH_EM6);
+}

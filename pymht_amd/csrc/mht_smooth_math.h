@@ -126,8 +126,10 @@ MHT_HD void smooth_cholesky(double* P, double* inv_d) {
 // k + 1 from it (xp, AP = A Pf, U = Pp: destroyed), the smoothed (xs, Ps) of node k + 1.  Out, in place: (xs, Ps) of node k.
 //   G = Pf A' Pp^-1 applied through Pp = U' U: row i of G solves g U' U = row i of Pf A' = column i of A Pf.
 //   xs_k = xf + G (xs_{k+1} - xp),  Ps_k = Pf + G (Ps_{k+1} - Pp) G'.   COV = false: means only, Ps is not touched.
-template <int N, bool COV>
-MHT_HD void smooth_backward_gain(const double* xf, const double* Pf, const double* xp, const double* AP, double* U, double* xs, double* Ps) {
+// GAIN = true: G [N][N] row-major is also handed out (the EM walk, mht_smooth_em.h, takes its lag-one covariance from it).
+template <int N, bool COV, bool GAIN = false>
+MHT_HD void smooth_backward_gain(const double* xf, const double* Pf, const double* xp, const double* AP, double* U, double* xs, double* Ps,
+                                 double* G_out = nullptr) {
     constexpr int NS = N * (N + 1) / 2;
     double inv_d[N];
     double D[COV ? NS : 1];      // Ps_{k+1} - Pp
@@ -184,6 +186,10 @@ MHT_HD void smooth_backward_gain(const double* xf, const double* Pf, const doubl
                 Ps[sym_idx(N, i, j)] = acc;
             }
         }
+    }
+    if (GAIN) {
+#pragma unroll
+        for (int i = 0; i < N * N; ++i) G_out[i] = G[i];
     }
 }
 

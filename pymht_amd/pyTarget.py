@@ -225,15 +225,20 @@ class Target:
             el.attrib[stateTag] = node.status
         return el
 
-    def getSmoothTrack(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False):
+    def getSmoothTrack(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False, em=0, emStart="model"):
         """pyTarget.py:580-609: (smoothed positions [L, 2], smoothed velocities [L, 2], ok) of the chain that ends in this node, from its
         initial state and backtrackMeasurement().  A chain of fewer than two nodes returns its measurements, NaN velocities and False, as
-        the reference does.  The smoother is pymht_amd.smoothing (device, fixed model, no EM) -- not pykalman.  The model is the
+        the reference does.  The smoother is pymht_amd.smoothing (device, fixed model; EM on request, see em) -- not pykalman.  The model is the
         tracker's for a node that came from one, else `model`, else models/pv as in the reference; many nodes at once:
         Tracker.getSmoothTracks().  constantTurn=True: the node of a constant-turn tracker (models/ct), smoothed with that model's own
         transition (refused by default; ValueError for a linear model).  ais=True: the node of an AIS-aided tracker, smoothed with the
-        AIS updates of its chain, which that tracker's AIS history supplies (ValueError for a node without such a tracker)."""
+        AIS updates of its chain, which that tracker's AIS history supplies (ValueError for a node without such a tracker).
+        em > 0: `em` EM iterations learn Q, R and the initial state from the chain before it is smoothed, as the reference's pykalman
+        call does (emStart="reference": from identity covariances, pykalman's defaults; "model": from the tracker's own); linear models,
+        not together with constantTurn or ais (ValueError)."""
         from . import smoothing
+        if em and (ais or constantTurn):
+            raise ValueError("em learns the noise of the plain linear model: not together with ais=True or constantTurn=True")
         tracker = getattr(self, "_tracker", None)
         lookup = None
         if ais:
@@ -246,7 +251,7 @@ class Target:
             else:
                 from .models import pv as model
         return smoothing.smooth_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
-                                      constantTurn=constantTurn, ais=lookup)[0]
+                                      constantTurn=constantTurn, ais=lookup, em=em, emStart=emStart)[0]
 
     @staticmethod
     def _smoothed_state_element(states, node, position, velocity, precision=2):

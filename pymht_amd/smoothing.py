@@ -15,7 +15,12 @@ which makes a track a linear model with a known A_k per step (`mht_smooth_tracks
 AIS-aided tracks are smoothed with their AIS updates only on request as well: `smooth_tracks_ais`, or `ais=True` further up.  A node that
 took a message went through two legs -- predict by dT1 to the message's time, update with the message (C = I4, R = sigma^2 I4), predict by
 dT2 to the scan's time -- before its radar update (Tracker.__fuseRadarAndAis, csrc/mht_ais_math.h), and `mht_smooth_tracks_ais` walks
-that model forward and back.  Without the request such a track is smoothed from its radar plots alone, as before."""
+that model forward and back.  Without the request such a track is smoothed from its radar plots alone, as before.
+
+The reference's EM step is available on request too: `smooth_tracks_em`, or `em=5` further up (linear models).  Per track, Q, R and the
+initial state are re-estimated from the track itself by `n_iter` expectation-maximisation iterations before the smoothing walk
+(`mht_smooth_tracks_em`); with emStart="reference" the covariances start at the identity, pykalman's documented default for what the
+reference does not hand it, and em=5 is then the reference's procedure -- restated (tests/smooth_em_ref.py), not pykalman's bits."""
 import ctypes as C
 
 import numpy as np
@@ -29,7 +34,9 @@ from .device import Context
 # arrays and the leg table between has_z and xs, the argument lists are the same otherwise
 _SEAMS = {"linear": ("mht_smooth_tracks", "mht_smooth_work_bytes", True),
           "ct": ("mht_smooth_tracks_ct", "mht_smooth_ct_work_bytes", False),
-          "ais": ("mht_smooth_tracks_ais", "mht_smooth_ais_work_bytes", False)}
+          "ais": ("mht_smooth_tracks_ais", "mht_smooth_ais_work_bytes", False),
+          "em": ("mht_smooth_tracks_em", "mht_smooth_em_work_bytes", True)}
+EM_MAX_ITER = 64      # (SMOOTH_EM_MAX_ITER of csrc/mht_smooth_em.h)
 
 
 def _check_model(model):
@@ -134,20 +141,41 @@ def smooth_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None, covariance
     return _smooth_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, covariances, False, ais=ais)
 
 
-def _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, constant_turn, ais=None):
+def _check_em(n_iter, start):
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or not 0 <= n_iter <= EM_MAX_ITER:
+        raise ValueError("smoothing: n_iter is an int in 0 .. %d (got %r)" % (EM_MAX_ITER, n_iter))
+    if start not in ("model", "reference"):
+        raise ValueError("smoothing: start is \"model\" (the tracker's Q(T), R_RADAR() and each track's P_init) or \"reference\" "
+                         "(identity Q, R and P0: pykalman's defaults); got %r" % (start,))
+    return int(n_iter), start
+
+
+def smooth_tracks_em(model, radarPeriod, tracks, n_iter=5, start="model", device=0, ctx=None, covariances=True):
+    """`smooth_tracks` with Q, R and the initial state learned per track by `n_iter` EM iterations first (linear models; a constant-turn
+    model raises NotImplementedError).  start="model": theta begins at the tracker's Q(T), R_RADAR() and each track's P_init;
+    start="reference": at identity Q, R and P0 (the reference gives pykalman the transition matrix, the observation matrix and the
+    initial mean, and pykalman's default for the rest is the identity), so that n_iter=5 is the reference's procedure.  n_iter: an int
+    in 0 .. 64 (0: `smooth_tracks` under the start values), anything else and any other `start` raise ValueError.
+    Returns per track (xs [L, nx], Ps [L, nx, nx] or None, Q [nx, nx], R [2, 2]).  A track whose re-estimated covariances stop being
+    positive definite comes back NaN, that track only."""
+    nx = _check_model(model)
+    return _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, False, em=_check_em(n_iter, start))
+
+
+def _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, constant_turn, ais=None, em=None):
     if len(tracks) == 0:
         return []
     own = ctx is None
     if own:
         ctx = Context(device, nx=nx)
     try:
-        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances, constant_turn, ais)
+        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances, constant_turn, ais, em)
     finally:
         if own:
             ctx.close()
 
 
-def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None):
+def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None, em=None):
     n, ns = len(tracks), nx * (nx + 1) // 2
     zs = [_measurement_array(t[2]) for t in tracks]
     lens = np.array([len(z) for z in zs], dtype=np.int32)
@@ -168,6 +196,9 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
         hp[j, :len(z)] = has
         x0[j] = np.asarray(tracks[t][0], dtype=np.float64).reshape(nx)
         P0[j] = np.asarray(tracks[t][1], dtype=np.float64).reshape(nx * nx)
+    identity_start = em is not None and em[1] == "reference"
+    if identity_start:
+        P0[:] = np.eye(nx).reshape(nx * nx)
     dev = ctx.device
     up = lambda a: torch.from_numpy(a).to(dev)
     # track-minor on the device: [node][element][track]
@@ -196,27 +227,42 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
         l_d = up(lp).permute(1, 0).contiguous()
         legs_d = up(legs) if len(legs) else None
         extra = (k_d.data_ptr(), m_d.data_ptr(), r_d.data_ptr(), l_d.data_ptr(), legs_d.data_ptr() if len(legs) else None, len(legs))
-    seam, sizer, sizer_takes_nx = _SEAMS["ais" if ais is not None else "ct" if constant_turn else "linear"]
+    if em is not None:      # n_iter in front of the outputs, the learned Q (packed) and R behind them
+        Q_d = torch.empty((ns, n), dtype=torch.float64, device=dev)
+        R_d = torch.empty((3, n), dtype=torch.float64, device=dev)
+    seam, sizer, sizer_takes_nx = _SEAMS["em" if em is not None else "ais" if ais is not None else "ct" if constant_turn else "linear"]
     need = int(getattr(lib, sizer)(*((nx,) if sizer_takes_nx else ()), n, L_max))
     work = torch.empty(need, dtype=torch.uint8, device=dev)
     # (the constant-turn seam builds its own transition per node: Phi(T, 0) stands in the struct and is not read)
-    keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in (model.Phi(period), model.Q(period), model.C_RADAR, model.R_RADAR())]
+    mats = (model.Phi(period), np.eye(nx) if identity_start else model.Q(period), model.C_RADAR, np.eye(2) if identity_start else model.R_RADAR())
+    keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in mats]
     fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
     mx = _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 1 if constant_turn else 0, period)
     lens_sorted = np.ascontiguousarray(lens[order])
     torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
     _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                                  z_d.data_ptr(), h_d.data_ptr(), *extra, xs_d.data_ptr(), Ps_d.data_ptr() if covariances else None,
+                                  z_d.data_ptr(), h_d.data_ptr(), *extra, *(() if em is None else (em[0],)), xs_d.data_ptr(),
+                                  Ps_d.data_ptr() if covariances else None, *(() if em is None else (Q_d.data_ptr(), R_d.data_ptr())),
                                   work.data_ptr(), need), lib)
     xs = xs_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
     Ps = None
     if covariances:      # packed upper triangle -> full matrices, still on the device
         idx = torch.tensor([min(i, j) * nx - min(i, j) * (min(i, j) - 1) // 2 + abs(i - j) for i in range(nx) for j in range(nx)], device=dev)
         Ps = Ps_d.index_select(1, idx).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
+    learned = ()
+    if em is not None:
+        iu = np.triu_indices(nx)
+        Qp, Rp = Q_d.permute(1, 0).contiguous().cpu().numpy(), R_d.permute(1, 0).contiguous().cpu().numpy()
+        Q = np.empty((n, nx, nx))
+        Q[:, iu[0], iu[1]] = Qp
+        Q[:, iu[1], iu[0]] = Qp
+        R = Rp[:, [0, 1, 1, 2]].reshape(n, 2, 2)
     out = [None] * n
     for j, t in enumerate(order):
         L = int(lens[t])
-        out[t] = (xs[j, :L], Ps[j, :L] if covariances else None)
+        if em is not None:
+            learned = (Q[j], R[j])
+        out[t] = (xs[j, :L], Ps[j, :L] if covariances else None) + learned
     return out
 
 
@@ -247,16 +293,23 @@ def chain_ais(chain, lookup):
     return ais
 
 
-def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None):
+def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None, em=0, emStart="model"):
     """`Target.getSmoothTrack` for many track nodes in one device call: per node (positions [L, 2], velocities [L, 2], ok) as the
     reference returns them.  A chain of fewer than two nodes has nothing to smooth: its measurements, NaN velocities and False.
     constantTurn=True: the nodes are a constant-turn tracker's and go through `smooth_tracks_ct` (ValueError for any other model); by
     default such a model is refused (NotImplementedError).
     ais: None, or a callable (scanNumber, mmsi) -> message (time, state, highAccuracy) of an AIS-aided tracker: the chains go through
-    `smooth_tracks_ais` with the messages their nodes took (`chain_ais`).  Not together with constantTurn (ValueError)."""
+    `smooth_tracks_ais` with the messages their nodes took (`chain_ais`).  Not together with constantTurn (ValueError).
+    em > 0: the chains go through `smooth_tracks_em(n_iter=em, start=emStart)`; not together with constantTurn or ais (ValueError before
+    anything runs).  ok is then False as well for a track whose output is not finite."""
     if ais is not None and constantTurn:
         raise ValueError("smoothing: AIS-aware smoothing is for 4-state linear models, not together with constantTurn")
+    n_iter, emStart = _check_em(em, emStart)
+    if n_iter > 0 and (ais is not None or constantTurn):
+        raise ValueError("smoothing: em learns the noise of the plain linear model, not together with constantTurn or ais")
     smooth = smooth_tracks_ais if ais is not None else smooth_tracks_ct if constantTurn else smooth_tracks
+    if n_iter > 0:
+        smooth = lambda *a, **kw: smooth_tracks_em(*a, n_iter=n_iter, start=emStart, **kw)
     (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
     out, batch, where = [None] * len(nodes), [], []
     for i, node in enumerate(nodes):
@@ -267,6 +320,6 @@ def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fal
         else:
             batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
             where.append(i)
-    for i, (xs, _) in zip(where, smooth(model, radarPeriod, batch, device=device, ctx=ctx, covariances=False)):
-        out[i] = (xs[:, 0:2], xs[:, 2:4], True)
+    for i, (xs, *_) in zip(where, smooth(model, radarPeriod, batch, device=device, ctx=ctx, covariances=False)):
+        out[i] = (xs[:, 0:2], xs[:, 2:4], n_iter == 0 or bool(np.isfinite(xs).all()))
     return out

@@ -990,12 +990,14 @@ class Tracker():
         self._drain()
         return self._ais_message
 
-    def _smooth_nodes(self, nodes, constantTurn=False, ais=False):
+    def _smooth_nodes(self, nodes, constantTurn=False, ais=False, em=0, emStart="model"):
         from . import smoothing
+        if em and (ais or constantTurn):
+            raise ValueError("em learns the noise of the plain linear model: not together with ais=True or constantTurn=True")
         return smoothing.smooth_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
-                                      ais=self._ais_lookup(constantTurn) if ais else None)
+                                      ais=self._ais_lookup(constantTurn) if ais else None, em=em, emStart=emStart)
 
-    def getSmoothTracks(self, terminated=False, constantTurn=False, ais=False):
+    def getSmoothTracks(self, terminated=False, constantTurn=False, ais=False, em=0, emStart="model"):
         """tracker.py: [track.getSmoothTrack(radarPeriod) for track in __trackNodes__] -- (positions, velocities, ok) per live track, with
         terminated=True followed by the terminated ones (__terminatedTargets__) -- smoothed in ONE batched device call
         (pymht_amd/smoothing.py: a Rauch-Tung-Striebel smoother with the tracker's own model, not pykalman).  A constant-turn tracker
@@ -1004,11 +1006,15 @@ class Tracker():
         tracker on a linear model.  ais=True (a tracker made with aisAided=True, else ValueError; not with constantTurn): the smoother
         of the model the forest filtered with -- a node that took an AIS message is predicted to the message's time, updated with it
         and predicted on to the scan (smoothing.smooth_tracks_ais), the messages looked up in __aisHistory__; a node whose message is
-        not there raises RuntimeError.  By default an AIS-aided tracker's histories are smoothed from their radar plots alone."""
+        not there raises RuntimeError.  By default an AIS-aided tracker's histories are smoothed from their radar plots alone.
+        em > 0 (linear models; not with constantTurn or ais: ValueError): Q, R and the initial state are learned per track by `em`
+        EM iterations before the smoothing walk (smoothing.smooth_tracks_em); emStart="reference" starts them at the identity as the
+        reference's pykalman call does, so that em=5, emStart="reference" is the reference's procedure, restated.  ok is False for a
+        track whose learned covariances stopped being positive definite (its output is NaN)."""
         nodes = list(self.__trackNodes__)
         if terminated:
             nodes += list(self.__terminatedTargets__)
-        return self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais)
+        return self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais, em=em, emStart=emStart)
 
     def synchronize(self):
         """Wait for everything queued on the device and fold it (reports are folded lazily otherwise)."""
@@ -1079,12 +1085,13 @@ class Tracker():
                             ("targetSizeLimit", self.targetSizeLimit), ("maxSpeedMS", self.maxSpeedMS)):
             ET.SubElement(settings, name).text = str(value)
 
-    def _storeRun(self, scenarioElement, preInitialized=True, smooth=False, constantTurn=False, ais=False, **kwargs):
+    def _storeRun(self, scenarioElement, preInitialized=True, smooth=False, constantTurn=False, ais=False, em=0, emStart="model", **kwargs):
         """One <Run>: the per-stage run times of every scan and one <Track> per live and per terminated target -- all states of
         the selected hypothesis' chain (preInitialized=True) or its first and last.  smooth=True also fills every track's
         <SmoothedStates> (one <S> per node), all tracks of the run smoothed in ONE device call (getSmoothTracks, which constantTurn is
         handed to: a constant-turn tracker smooths with constantTurn=True only; so is ais: an AIS-aided tracker's smoothed states hold
-        its AIS updates with ais=True only); by default the element stays empty."""
+        its AIS updates with ais=True only; and em, emStart, which are then -- for em > 0 only -- also written as attributes of every
+        <SmoothedStates>); by default the element stays empty."""
         import xml.etree.ElementTree as ET
         run = ET.SubElement(scenarioElement, xmltags.runTag)
         run.attrib[xmltags.iterationTag] = str(kwargs[xmltags.iterationTag] if xmltags.iterationTag in kwargs
@@ -1101,12 +1108,14 @@ class Tracker():
                                                        xmltags.maxTag: str(round(np.max(v), prec))}
                           ).text = np.array_str(v, precision=prec, max_line_width=999999)
         groups = ((list(self.__trackNodes__), {}), (self.__terminatedTargets__, {xmltags.terminatedTag: True}))
-        smoothed = (iter(self._smooth_nodes([node for nodes, _ in groups for node in nodes], constantTurn=constantTurn, ais=ais))
+        smoothed = (iter(self._smooth_nodes([node for nodes, _ in groups for node in nodes], constantTurn=constantTurn, ais=ais, em=em, emStart=emStart))
                     if (smooth and preInitialized) else None)
         for nodes, extra in groups:
             for node in nodes:
                 if preInitialized:
-                    node._storeNode(run, self.radarPeriod, smooth=(next(smoothed) if smoothed is not None else False), **extra)
+                    track = node._storeNode(run, self.radarPeriod, smooth=(next(smoothed) if smoothed is not None else False), **extra)
+                    if smoothed is not None and em > 0:
+                        track.find(xmltags.smoothedstatesTag).attrib.update({"em": str(em), "emStart": emStart})
                 else:
                     node._storeNodeSparse(run, **extra)
         return run
