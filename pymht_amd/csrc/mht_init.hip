@@ -12,8 +12,9 @@
 // GNN = the reference's Hungarian assignment on a big-M padded square matrix = a minimum-cost maximum-cardinality matching of the
 // sparse "allowed" graph; its connected components are tiny (a leftover has at most a couple of partners within v_max * dt), so
 // it is solved exactly per component by successive shortest augmenting paths, one thread per component.
-// Arithmetic follows the reference's dtypes (float32 states, covariances, distances); its host BLAS orders 4-term dot products
-// differently from any fixed order, so states agree to ~1e-6 relative, decisions (births, counters) exactly (tests/golden G8).
+// Arithmetic follows the reference's dtypes (float32 states, covariances, distances) and the order of its host BLAS (mht_math.h:
+// gemv_row for matrix x vector, gemm_chain for matrix x matrix), so birth states and covariances agree BIT FOR BIT and decisions
+// (births, counters) exactly (tests/golden G8; tests/test_initiator_shapes_gpu.py past one workgroup and the LDS tables).
 #include "mht_kernels.h"
 #include "mht_init_dev.h"
 #include <new>
@@ -141,8 +142,8 @@ extern "C" int mht_initiator_create(mht_ctx* ctx, mht_initiator** out, const mht
     init_layout(in, probe);
     in->arena_bytes = probe.off + 4096;
     if (hipMalloc(reinterpret_cast<void**>(&in->arena), in->arena_bytes) != hipSuccess) {
-        delete in;
         set_error("mht_initiator_create: hipMalloc of %zu bytes failed", in->arena_bytes);
+        delete in;
         return MHT_E_HIP;
     }
     IArena ar{in->arena, 0};
@@ -154,10 +155,16 @@ extern "C" int mht_initiator_create(mht_ctx* ctx, mht_initiator** out, const mht
     for (int i = 0; i < 8; ++i) a.C[i] = cfg->C[i];
     for (int i = 0; i < 4; ++i) a.R[i] = cfg->R[i];
     for (int i = 0; i < 16; ++i) a.P0[i] = cfg->P0[i];
-    MHT_HIP_CHECK(hipMemsetAsync(in->arena, 0, in->arena_bytes, ctx->stream));
     in->host_bytes = (size_t)cfg->max_born * (32 + 64 + 4 + 8) + 256;
-    MHT_HIP_CHECK(hipHostMalloc(&in->host, in->host_bytes, hipHostMallocDefault));
-    MHT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // (a failure from here on gives back what has been allocated: mht_initiator_destroy frees the arena, the staging buffer and `in`)
+    hipError_t err = hipMemsetAsync(in->arena, 0, in->arena_bytes, ctx->stream);
+    if (err == hipSuccess) err = hipHostMalloc(&in->host, in->host_bytes, hipHostMallocDefault);
+    if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+    if (err != hipSuccess) {
+        set_error("mht_initiator_create: %s (arena of %zu bytes, %zu bytes of pinned staging)", hipGetErrorString(err), in->arena_bytes, in->host_bytes);
+        (void)mht_initiator_destroy(in);
+        return MHT_E_HIP;
+    }
     *out = in;
     return MHT_OK;
 }

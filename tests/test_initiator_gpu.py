@@ -10,14 +10,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def make_initiator(ctx, M_required, N_checks, max_meas=1024):
+def make_initiator(ctx, M_required, N_checks, max_meas=1024, max_prelim=2048, max_born=256):
     from scipy.stats import chi2
     from pymht_amd import _lib
     from pymht_amd.models import pv
     from pymht_amd.models.constants import sigmaQ_tracker
     cfg = _lib.MhtInitiatorConfig()
     cfg.m_required, cfg.n_checks = M_required, N_checks
-    cfg.max_meas, cfg.max_prelim, cfg.max_born = max_meas, 2048, 256
+    cfg.max_meas, cfg.max_prelim, cfg.max_born = max_meas, max_prelim, max_born
     cfg.v_max = 20.0
     cfg.gamma = float(chi2(df=2).ppf(0.99))
     cfg.merge_threshold = 4 * 2.5 ** 2
@@ -27,7 +27,7 @@ def make_initiator(ctx, M_required, N_checks, max_meas=1024):
     cfg.P0[:] = np.asarray(pv.P0, np.float32).reshape(-1).tolist()
     cfg.sigma_q = float(sigmaQ_tracker)
     h = C.c_void_p()
-    _lib.check(ctx.lib.mht_initiator_create(ctx.handle, C.byref(h), C.byref(cfg)))
+    _lib.check(ctx.lib.mht_initiator_create(ctx.handle, C.byref(h), C.byref(cfg)), ctx.lib)
     return h
 
 
