@@ -31,7 +31,8 @@ extern "C" {
 /* State dimension of the library build the header is used with: 4 (libmht_amd.so: the reference's CV model, models/pv.py) or 6
  * (libmht_amd6.so: the same sources compiled with -DMHT_NX=6 for BASELINE config 5's six-state model).  It sizes the model matrices
  * and the state vectors / covariances of the forest's reports; the stateless seams mht_gate_scan (4 states), mht_gate_scan_x and
- * mht_smooth_tracks and mht_smooth_tracks_em (4 or 6 at run time), mht_smooth_tracks_ct (6) and mht_smooth_tracks_ais (4) do not depend on it. */
+ * mht_smooth_tracks and mht_smooth_tracks_em (4 or 6 at run time), mht_smooth_tracks_ct (6) and mht_smooth_tracks_ais (4), and the mht_score_tracks*
+ * seams next to them, do not depend on it. */
 #ifndef MHT_NX
 #define MHT_NX 4
 #endif
@@ -276,6 +277,56 @@ size_t mht_smooth_em_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max);
 int mht_smooth_tracks_em(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                          const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_iter,
                          double* xs, double* Ps, double* Q_out, double* R_out, void* work, size_t work_bytes);
+
+/* ---- seam (v), EM with its trace: mht_smooth_tracks_em with the log-likelihood of every track under every theta_i handed out ------
+ * Every argument of mht_smooth_tracks_em, its checks, its error codes, and its bits in xs, Ps, Q_out, R_out; behind them
+ *   ll_trace  dev [n_iter + 1][n_tracks] f64 out: row i is each track's log-likelihood (mht_score_tracks' ll, below) under theta_i --
+ *             theta_0 the call's start values (row 0 is mht_score_tracks' ll of the same arguments, bit for bit), theta_{n_iter} what
+ *             the output walk runs under.  EM never decreases it; a track of one node has 0.0 in every row.
+ * One forward-only launch in front of each walk, n_iter + 1 more than mht_smooth_tracks_em, on the same stream.  NULL ll_trace with a
+ * non-empty batch: MHT_E_INVALID.  Exported by both builds. */
+int mht_smooth_tracks_em_ll(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                            const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_iter,
+                            double* xs, double* Ps, double* Q_out, double* R_out, void* work, size_t work_bytes, double* ll_trace);
+
+/* ---- seam (vi): how well the model explains the plots of a batch of track histories -- log-likelihood and innovation consistency,
+ * stateless, forward pass only ------------------------------------------------------------------------------------------------------
+ * The forward (filter) recursion of mht_smooth_tracks, operation for operation -- the filtered states behind a score are that
+ * smoother's own -- with nothing kept per node.  Node 0 is the initial state and is NOT an observation (pykalman's loglikelihood()
+ * counts one at time 0: these are not its figures).  Per track, over every node k >= 1 with a radar measurement, with
+ * v = z_k - C xp_k and S = C Pp_k C' + R:
+ *   nis   = sum v' S^-1 v                                  the normalised innovation squared; over a consistent filter it is chi-square
+ *                                                          with 2 nObs degrees of freedom
+ *   ll    = - 1/2 sum (ln det S + v' S^-1 v + 2 ln 2 pi)   = sum ln N(z_k; C xp_k, S)
+ *   nObs  = the number of such nodes
+ * A track of one node, or one never detected, gives exactly ll = 0.0, nis = 0.0, nObs = 0.  A det S that is not positive gives NaN in
+ * ll and nis of that track only.  model, len, x_init, P_init, z, has_z, their layouts and checks are mht_smooth_tracks'
+ * (MHT_E_INVALID for nx other than 4 or 6, transition != 0, a length outside 1 .. L_max).  Next to them:
+ *   ll_out   dev [n_tracks] f64 out       nis_out  dev [n_tracks] f64 out       nobs_out  dev [n_tracks] int32 out
+ *   work     dev, work_bytes >= mht_score_work_bytes(nx, n_tracks, L_max) (the lengths, nothing per node; 0 for a bad nx or a negative
+ *            size): MHT_E_INVALID if it is smaller.
+ * One launch, one track per lane; no track's figures depend on its place in the batch.  Synchronises.  On MHT_E_INVALID nothing has
+ * been launched or written.  Exported by both builds (nx at run time).
+ * mht_score_tracks_ct: the same under the constant-turn model of mht_smooth_tracks_ct (nx == 6, transition == 1, period > 0; A ignored),
+ * same sizer with nx = 6.
+ * mht_score_tracks_ais: the same under the AIS-aware model of mht_smooth_tracks_ais (nx == 4), with that seam's kind, ais_z, ais_r,
+ * leg, legs, n_legs and their contract.  A node that took a message (kind >= 2) is scored at the message's time as well, with
+ * v = m - xp(t_m), S = Pp(t_m) + r I4 and ln det S = 2 sum ln U_ii of the Cholesky factor S = U' U the update takes:
+ *   ll -= 1/2 (ln det S + v' S^-1 v + 4 ln 2 pi);   nis_ais_out dev [n_tracks] f64 out: sum v' S^-1 v over the messages;
+ *   nais_out dev [n_tracks] int32 out: their number.   nis and nObs stay radar-only.  A batch without any message gives
+ * mht_score_tracks' ll, nis and nObs bit for bit.  Same sizer with nx = 4. */
+size_t mht_score_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max);
+int mht_score_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                     const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* ll_out, double* nis_out,
+                     int32_t* nobs_out, void* work, size_t work_bytes);
+int mht_score_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                        const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* ll_out, double* nis_out,
+                        int32_t* nobs_out, void* work, size_t work_bytes);
+int mht_score_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                         const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, const uint8_t* kind,
+                         const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
+                         double* ll_out, double* nis_out, int32_t* nobs_out, double* nis_ais_out, int32_t* nais_out, void* work,
+                         size_t work_bytes);
 
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in

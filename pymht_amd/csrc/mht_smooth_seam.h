@@ -61,4 +61,9 @@ static char* smooth_args(const Steps& steps, const SmoothBatch& b, SmoothArgs<N,
     return q;
 }
 
+// One forward-only score launch over a checked linear batch whose lengths are in the workspace (mht_smooth_score.hip), queued on the
+// context's stream and not waited for: ll [n] <- each track's log-likelihood under the call's (x_init, P_init, Q, R) (theta null) or
+// under its own theta [N + 2 NS + 3][n] in the EM workspace's layout.  What mht_smooth_tracks_em_ll puts in front of each EM walk.
+int score_linear_launch(mht_ctx* ctx, const mht_model_x* model, const SmoothBatch& b, const double* theta, double* ll);
+
 }  // namespace mht

@@ -253,6 +253,26 @@ class Target:
         return smoothing.smooth_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
                                       constantTurn=constantTurn, ais=lookup, em=em, emStart=emStart)[0]
 
+    def getTrackLikelihood(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False):
+        """(logLikelihood, nis, nObs) of the chain that ends in this node under the model getSmoothTrack would smooth it with -- how well
+        that model explains the chain's plots (pymht_amd.smoothing.score_tracks defines the figures; a chain of fewer than two nodes
+        gives (0.0, 0.0, 0)).  model, constantTurn and ais as for getSmoothTrack, with the same refusals; with ais=True the tuple is
+        (logLikelihood, nis, nObs, nisAis, nAis).  Many nodes at once: Tracker.getTrackLikelihoods()."""
+        from . import smoothing
+        tracker = getattr(self, "_tracker", None)
+        lookup = None
+        if ais:
+            if tracker is None:
+                raise ValueError("ais=True needs the node of an AIS-aided Tracker: the messages are in the tracker's history")
+            lookup = tracker._ais_lookup(constantTurn)
+        if model is None:
+            if tracker is not None:
+                model = tracker._model_mod
+            else:
+                from .models import pv as model
+        return smoothing.score_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
+                                     constantTurn=constantTurn, ais=lookup)[0]
+
     @staticmethod
     def _smoothed_state_element(states, node, position, velocity, precision=2):
         """One <S> of <SmoothedStates>, in the layout of _state_element: the node's time, smoothed position and velocity (north before east)."""

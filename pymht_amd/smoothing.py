@@ -20,7 +20,13 @@ that model forward and back.  Without the request such a track is smoothed from 
 The reference's EM step is available on request too: `smooth_tracks_em`, or `em=5` further up (linear models).  Per track, Q, R and the
 initial state are re-estimated from the track itself by `n_iter` expectation-maximisation iterations before the smoothing walk
 (`mht_smooth_tracks_em`); with emStart="reference" the covariances start at the identity, pykalman's documented default for what the
-reference does not hand it, and em=5 is then the reference's procedure -- restated (tests/smooth_em_ref.py), not pykalman's bits."""
+reference does not hand it, and em=5 is then the reference's procedure -- restated (tests/smooth_em_ref.py), not pykalman's bits.
+
+The same histories are SCORED here too: `score_tracks`, `score_tracks_ct`, `score_tracks_ais` (and `score_nodes`, `Tracker.getTrackLikelihoods`)
+run the forward half of the smoother of that model and return per track the log-likelihood of its plots, their normalised innovation
+squared summed (NIS) and their number (`mht_score_tracks*`, one forward-only launch, nothing stored per node); node 0 is the initial state
+and not an observation, so the figures are not pykalman's loglikelihood(), which counts one at time 0.  `smooth_tracks_em(likelihoods=True)`
+hands out the log-likelihood under every EM iterate (`mht_smooth_tracks_em_ll`)."""
 import ctypes as C
 
 import numpy as np
@@ -150,38 +156,46 @@ def _check_em(n_iter, start):
     return int(n_iter), start
 
 
-def smooth_tracks_em(model, radarPeriod, tracks, n_iter=5, start="model", device=0, ctx=None, covariances=True):
+def smooth_tracks_em(model, radarPeriod, tracks, n_iter=5, start="model", device=0, ctx=None, covariances=True, likelihoods=False):
     """`smooth_tracks` with Q, R and the initial state learned per track by `n_iter` EM iterations first (linear models; a constant-turn
     model raises NotImplementedError).  start="model": theta begins at the tracker's Q(T), R_RADAR() and each track's P_init;
     start="reference": at identity Q, R and P0 (the reference gives pykalman the transition matrix, the observation matrix and the
     initial mean, and pykalman's default for the rest is the identity), so that n_iter=5 is the reference's procedure.  n_iter: an int
     in 0 .. 64 (0: `smooth_tracks` under the start values), anything else and any other `start` raise ValueError.
     Returns per track (xs [L, nx], Ps [L, nx, nx] or None, Q [nx, nx], R [2, 2]).  A track whose re-estimated covariances stop being
-    positive definite comes back NaN, that track only."""
+    positive definite comes back NaN, that track only.
+    likelihoods=True (a bool, else TypeError): each track's tuple gains a last element ll [n_iter + 1], its log-likelihood
+    (`score_tracks`' definition) under theta_0 -- the start values: ll[0] is `score_tracks`' figure under them, bit for bit -- theta_1, ..
+    and theta_n_iter, what the output was smoothed under.  EM never decreases it: the trace says whether the iterations improved the
+    fit and whether they were still moving.  The other outputs are the same bits; it costs n_iter + 1 forward-only launches
+    (`mht_smooth_tracks_em_ll`)."""
     nx = _check_model(model)
-    return _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, False, em=_check_em(n_iter, start))
+    if not isinstance(likelihoods, (bool, np.bool_)):
+        raise TypeError("smoothing: likelihoods is a bool (got %r)" % (likelihoods,))
+    return _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, False, em=_check_em(n_iter, start), likelihoods=bool(likelihoods))
 
 
-def _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, constant_turn, ais=None, em=None):
+def _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, constant_turn, ais=None, em=None, likelihoods=False):
     if len(tracks) == 0:
         return []
     own = ctx is None
     if own:
         ctx = Context(device, nx=nx)
     try:
-        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances, constant_turn, ais, em)
+        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances, constant_turn, ais, em, likelihoods)
     finally:
         if own:
             ctx.close()
 
 
-def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None, em=None):
-    n, ns = len(tracks), nx * (nx + 1) // 2
+def _pack(ctx, tracks, nx, identity_start=False):
+    """The batch on the device, track-minor ([node][element][track]), tracks of similar length side by side: a wavefront runs as long as
+    the longest of its 64 tracks (stable: equal lengths keep their order).  Returns (lens, order, L_max, hp, (x_d, P_d, z_d, h_d))."""
+    n = len(tracks)
     zs = [_measurement_array(t[2]) for t in tracks]
     lens = np.array([len(z) for z in zs], dtype=np.int32)
     if lens.min() < 1:
         raise ValueError("smoothing: a track without nodes")
-    # tracks of similar length side by side: a wavefront runs as long as the longest of its 64 tracks (stable: equal lengths keep their order)
     order = np.argsort(-lens, kind="stable")
     L_max = int(lens.max())
     zp = np.zeros((n, L_max, 2))
@@ -196,54 +210,76 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
         hp[j, :len(z)] = has
         x0[j] = np.asarray(tracks[t][0], dtype=np.float64).reshape(nx)
         P0[j] = np.asarray(tracks[t][1], dtype=np.float64).reshape(nx * nx)
-    identity_start = em is not None and em[1] == "reference"
     if identity_start:
         P0[:] = np.eye(nx).reshape(nx * nx)
-    dev = ctx.device
-    up = lambda a: torch.from_numpy(a).to(dev)
-    # track-minor on the device: [node][element][track]
+    up = lambda a: torch.from_numpy(a).to(ctx.device)
     z_d = up(zp).permute(1, 2, 0).contiguous()
     h_d = up(hp).permute(1, 0).contiguous()
     x_d = up(x0).permute(1, 0).contiguous()
     P_d = up(P0).permute(1, 0).contiguous()
+    return lens, order, L_max, hp, (x_d, P_d, z_d, h_d)
+
+
+def _pack_ais(ctx, ais, order, hp, L_max):
+    """The per-node AIS inputs next to z / has_z, and the leg table: (the seam's arguments between has_z and its outputs, the device
+    arrays behind them -- kept by the caller until the seam has returned)."""
+    per_track, legs = ais
+    n = len(order)
+    up = lambda a: torch.from_numpy(a).to(ctx.device)
+    kp = hp.copy()
+    mp, rp, lp = np.zeros((n, L_max, 4)), np.ones((n, L_max)), np.zeros((n, L_max), dtype=np.int32)
+    for j, t in enumerate(order):
+        has_m, msg, r, leg = per_track[t]
+        kp[j, :len(has_m)] += 2 * has_m.astype(np.uint8)
+        mp[j, :len(has_m)], rp[j, :len(has_m)], lp[j, :len(has_m)] = msg, r, leg
+    # the seam cannot see these device arrays: its contract is checked here, before the upload
+    fused = kp >= 2
+    if not np.array_equal(kp & 1, hp) or (fused.any() and (lp[fused].min() < 0 or lp[fused].max() >= len(legs))) or not (rp > 0).all():
+        raise ValueError("smoothing: inconsistent AIS inputs (a leg index outside the table of %d entries, or a variance that is not positive)" % len(legs))
+    k_d = up(kp).permute(1, 0).contiguous()
+    m_d = up(mp).permute(1, 2, 0).contiguous()
+    r_d = up(rp).permute(1, 0).contiguous()
+    l_d = up(lp).permute(1, 0).contiguous()
+    legs_d = up(legs) if len(legs) else None
+    return (k_d.data_ptr(), m_d.data_ptr(), r_d.data_ptr(), l_d.data_ptr(), legs_d.data_ptr() if len(legs) else None, len(legs)), (k_d, m_d, r_d, l_d, legs_d)
+
+
+def _model_x(model, period, nx, constant_turn, identity_start=False):
+    """(the seam's mht_model_x, the float32 arrays it points into).  The constant-turn seams build their own transition per node:
+    Phi(T, 0) stands in the struct and is not read."""
+    mats = (model.Phi(period), np.eye(nx) if identity_start else model.Q(period), model.C_RADAR, np.eye(2) if identity_start else model.R_RADAR())
+    keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in mats]
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    return _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 1 if constant_turn else 0, period), keep
+
+
+def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None, em=None, likelihoods=False):
+    n, ns = len(tracks), nx * (nx + 1) // 2
+    identity_start = em is not None and em[1] == "reference"
+    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx, identity_start)
+    dev = ctx.device
     xs_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
     Ps_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev) if covariances else None
-    lib, extra = ctx.lib, ()
-    if ais is not None:      # the per-node AIS inputs next to z / has_z, and the leg table
-        per_track, legs = ais
-        kp = hp.copy()
-        mp, rp, lp = np.zeros((n, L_max, 4)), np.ones((n, L_max)), np.zeros((n, L_max), dtype=np.int32)
-        for j, t in enumerate(order):
-            has_m, msg, r, leg = per_track[t]
-            kp[j, :len(has_m)] += 2 * has_m.astype(np.uint8)
-            mp[j, :len(has_m)], rp[j, :len(has_m)], lp[j, :len(has_m)] = msg, r, leg
-        # the seam cannot see these device arrays: its contract is checked here, before the upload
-        fused = kp >= 2
-        if not np.array_equal(kp & 1, hp) or (fused.any() and (lp[fused].min() < 0 or lp[fused].max() >= len(legs))) or not (rp > 0).all():
-            raise ValueError("smoothing: inconsistent AIS inputs (a leg index outside the table of %d entries, or a variance that is not positive)" % len(legs))
-        k_d = up(kp).permute(1, 0).contiguous()
-        m_d = up(mp).permute(1, 2, 0).contiguous()
-        r_d = up(rp).permute(1, 0).contiguous()
-        l_d = up(lp).permute(1, 0).contiguous()
-        legs_d = up(legs) if len(legs) else None
-        extra = (k_d.data_ptr(), m_d.data_ptr(), r_d.data_ptr(), l_d.data_ptr(), legs_d.data_ptr() if len(legs) else None, len(legs))
+    lib, extra, trace = ctx.lib, (), ()
+    if ais is not None:
+        extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
     if em is not None:      # n_iter in front of the outputs, the learned Q (packed) and R behind them
         Q_d = torch.empty((ns, n), dtype=torch.float64, device=dev)
         R_d = torch.empty((3, n), dtype=torch.float64, device=dev)
     seam, sizer, sizer_takes_nx = _SEAMS["em" if em is not None else "ais" if ais is not None else "ct" if constant_turn else "linear"]
+    if likelihoods:      # the same call with the trace of log-likelihoods behind its arguments
+        seam = "mht_smooth_tracks_em_ll"
+        ll_d = torch.empty((em[0] + 1, n), dtype=torch.float64, device=dev)
+        trace = (ll_d.data_ptr(),)
     need = int(getattr(lib, sizer)(*((nx,) if sizer_takes_nx else ()), n, L_max))
     work = torch.empty(need, dtype=torch.uint8, device=dev)
-    # (the constant-turn seam builds its own transition per node: Phi(T, 0) stands in the struct and is not read)
-    mats = (model.Phi(period), np.eye(nx) if identity_start else model.Q(period), model.C_RADAR, np.eye(2) if identity_start else model.R_RADAR())
-    keep = [np.ascontiguousarray(np.asarray(m, dtype=np.float32).ravel()) for m in mats]
-    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-    mx = _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 1 if constant_turn else 0, period)
+    mx, keep = _model_x(model, period, nx, constant_turn, identity_start)
     lens_sorted = np.ascontiguousarray(lens[order])
     torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
     _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
                                   z_d.data_ptr(), h_d.data_ptr(), *extra, *(() if em is None else (em[0],)), xs_d.data_ptr(),
                                   Ps_d.data_ptr() if covariances else None, *(() if em is None else (Q_d.data_ptr(), R_d.data_ptr())),
-                                  work.data_ptr(), need), lib)
+                                  work.data_ptr(), need, *trace), lib)
     xs = xs_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
     Ps = None
     if covariances:      # packed upper triangle -> full matrices, still on the device
@@ -257,12 +293,79 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
         Q[:, iu[0], iu[1]] = Qp
         Q[:, iu[1], iu[0]] = Qp
         R = Rp[:, [0, 1, 1, 2]].reshape(n, 2, 2)
+    if likelihoods:
+        ll = ll_d.permute(1, 0).contiguous().cpu().numpy()      # [track][n_iter + 1]
     out = [None] * n
     for j, t in enumerate(order):
         L = int(lens[t])
         if em is not None:
-            learned = (Q[j], R[j])
+            learned = (Q[j], R[j]) + ((ll[j],) if likelihoods else ())
         out[t] = (xs[j, :L], Ps[j, :L] if covariances else None) + learned
+    return out
+
+
+_SCORE_SEAMS = {"linear": "mht_score_tracks", "ct": "mht_score_tracks_ct", "ais": "mht_score_tracks_ais"}
+
+
+def score_tracks(model, radarPeriod, tracks, device=0, ctx=None):
+    """How well `model` explains each of a batch of track histories: per track (logLikelihood, nis, nObs).  `model` and `tracks` as for
+    `smooth_tracks` (the same checks and refusals; an empty list gives an empty list).  Over every node k >= 1 with a radar plot, with
+    v = z_k - C xp_k and S = C Pp_k C' + R from the filter `smooth_tracks` runs forward (the same filtered states, bit for bit):
+        nis = sum v' S^-1 v                                  chi-square with 2 nObs degrees of freedom over a consistent filter
+        logLikelihood = -1/2 sum (ln det S + v' S^-1 v + 2 ln 2 pi)
+    Node 0 is the initial state and is not an observation -- pykalman's loglikelihood() counts one at time 0, so these are not its
+    figures.  A track of one node, or one never detected, gives (0.0, 0.0, 0).  One forward-only device launch (`mht_score_tracks`)."""
+    return _score_on(ctx, device, model, radarPeriod, tracks, _check_model(model), False)
+
+
+def score_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None):
+    """`score_tracks` under the constant-turn model `smooth_tracks_ct` smooths with (anything else raises ValueError)."""
+    return _score_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), True)
+
+
+def score_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None):
+    """`score_tracks` under the AIS-aware model of `smooth_tracks_ais`, same `tracks` and refusals: per track
+    (logLikelihood, nis, nObs, nisAis, nAis).  A node that took a message is scored at the message's time as well, v = m - xp,
+    S = Pp + sigma^2 I4: its ln N(m; xp, S) goes into logLikelihood, v' S^-1 v into nisAis (chi-square with 4 nAis degrees of freedom);
+    nis and nObs stay radar-only.  A batch without any message gives `score_tracks`' numbers bit for bit."""
+    nx = _check_ais_model(model)
+    ais = _ais_inputs(model, tracks)
+    return _score_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, False, ais=ais)
+
+
+def _score_on(ctx, device, model, radarPeriod, tracks, nx, constant_turn, ais=None):
+    if len(tracks) == 0:
+        return []
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        return _score(ctx, model, float(radarPeriod), tracks, nx, constant_turn, ais)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _score(ctx, model, period, tracks, nx, constant_turn, ais=None):
+    n = len(tracks)
+    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
+    dev, lib, extra = ctx.device, ctx.lib, ()
+    outs = [torch.empty(n, dtype=dt, device=dev) for dt in (torch.float64, torch.float64, torch.int32)]
+    if ais is not None:
+        extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
+        outs += [torch.empty(n, dtype=dt, device=dev) for dt in (torch.float64, torch.int32)]
+    need = int(lib.mht_score_work_bytes(nx, n, L_max))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mx, keep = _model_x(model, period, nx, constant_turn)
+    lens_sorted = np.ascontiguousarray(lens[order])
+    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
+    seam = _SCORE_SEAMS["ais" if ais is not None else "ct" if constant_turn else "linear"]
+    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
+                                  z_d.data_ptr(), h_d.data_ptr(), *extra, *(o.data_ptr() for o in outs), work.data_ptr(), need), lib)
+    cols = [o.cpu().numpy() for o in outs]
+    out = [None] * n
+    for j, t in enumerate(order):
+        out[t] = tuple(float(c[j]) if c.dtype == np.float64 else int(c[j]) for c in cols)
     return out
 
 
@@ -322,4 +425,25 @@ def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fal
             where.append(i)
     for i, (xs, *_) in zip(where, smooth(model, radarPeriod, batch, device=device, ctx=ctx, covariances=False)):
         out[i] = (xs[:, 0:2], xs[:, 2:4], n_iter == 0 or bool(np.isfinite(xs).all()))
+    return out
+
+
+def score_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None):
+    """`score_tracks` for many track nodes in one device call, built on `chain_inputs` / `chain_ais` like `smooth_nodes` (the same
+    switches and refusals): per node (logLikelihood, nis, nObs), with ais also (.., nisAis, nAis).  A chain of fewer than two nodes has
+    nothing to explain: (0.0, 0.0, 0)."""
+    if ais is not None and constantTurn:
+        raise ValueError("smoothing: AIS-aware scoring is for 4-state linear models, not together with constantTurn")
+    score = score_tracks_ais if ais is not None else score_tracks_ct if constantTurn else score_tracks
+    (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
+    out, batch, where = [None] * len(nodes), [], []
+    for i, node in enumerate(nodes):
+        chain, inputs = chain_inputs(node, model.P0)
+        if len(chain) < 2:
+            out[i] = (0.0, 0.0, 0) + ((0.0, 0) if ais is not None else ())
+        else:
+            batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
+            where.append(i)
+    for i, res in zip(where, score(model, radarPeriod, batch, device=device, ctx=ctx)):
+        out[i] = res
     return out

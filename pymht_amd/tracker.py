@@ -1016,6 +1016,21 @@ class Tracker():
             nodes += list(self.__terminatedTargets__)
         return self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais, em=em, emStart=emStart)
 
+    def getTrackLikelihoods(self, terminated=False, constantTurn=False, ais=False):
+        """How well the tracker's model explains each track's plots: (logLikelihood, nis, nObs) per live track, in the order of
+        getSmoothTracks, with terminated=True followed by the terminated ones -- scored in ONE forward-only device call
+        (smoothing.score_nodes / score_tracks, which define the figures: node 0 is the initial state and no observation; nis, the
+        normalised innovation squared summed over the track's nObs plots, is chi-square with 2 nObs degrees of freedom when the filter
+        is consistent -- the figure to tune sigmaQ and R by).  constantTurn and ais as for getSmoothTracks, with the same refusals: a
+        constant-turn tracker raises NotImplementedError without constantTurn=True, ais=True needs an AIS-aided tracker and excludes
+        constantTurn (ValueError); with ais=True each tuple is (logLikelihood, nis, nObs, nisAis, nAis), the messages scored too."""
+        from . import smoothing
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        return smoothing.score_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
+                                     ais=self._ais_lookup(constantTurn) if ais else None)
+
     def synchronize(self):
         """Wait for everything queued on the device and fold it (reports are folded lazily otherwise)."""
         self._drain()
