@@ -328,6 +328,32 @@ int mht_score_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_track
                          double* ll_out, double* nis_out, int32_t* nobs_out, double* nis_ais_out, int32_t* nais_out, void* work,
                          size_t work_bytes);
 
+/* mht_score_tracks_grid, mht_score_tracks_ct_grid: seam (vi) under n_cand candidate noise models in ONE launch -- the likelihood surface
+ * Q and R are tuned over.  Candidate g replaces the model's Q and R and nothing else (A, C and the period stay the batch's; the model's
+ * own Q and R are not read), and its row holds what mht_score_tracks / mht_score_tracks_ct give for a model carrying its matrices, bit
+ * for bit where those are representable in the model's float32.  Candidates are float64: a tuning grid is not quantised.
+ *   n_cand    1 .. 4096, else MHT_E_INVALID
+ *   Q_cand    host [n_cand][nx*nx] f64 row-major; the upper triangle is read
+ *   R_cand    host [n_cand][4] f64; entries 0, 1 and 3 are read
+ *   ll_out    dev [n_cand][n_tracks] f64 out       nis_out  dev [n_cand][n_tracks] f64 out
+ *   nobs_out  dev [n_tracks] int32 out (it does not depend on the candidate)
+ *   work      dev, work_bytes >= mht_score_grid_work_bytes(nx, n_tracks, L_max, n_cand) (the lengths and the candidate table, each
+ *             rounded up to 256 bytes; 0 for a bad nx, a negative size or an n_cand outside its range): MHT_E_INVALID if it is smaller.
+ * Everything else, the model checks included, is mht_score_tracks' and mht_score_tracks_ct's.  One launch of ceil(n_tracks / 64) x n_cand
+ * workgroups, one (track, candidate) per lane, a workgroup's candidate the same for all its lanes; a det S that is not positive gives NaN
+ * in that (candidate, track) only.  Synchronises.  On MHT_E_INVALID nothing has been launched or written; n_tracks == 0 returns MHT_OK and
+ * writes nothing.  The AIS-aware model has no grid (its leg table carries a Q per entry): the linear grid scores such histories as
+ * mht_score_tracks does.  Exported by both builds (nx at run time). */
+size_t mht_score_grid_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max, int32_t n_cand);
+int mht_score_tracks_grid(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                          const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_cand,
+                          const double* Q_cand, const double* R_cand, double* ll_out, double* nis_out, int32_t* nobs_out, void* work,
+                          size_t work_bytes);
+int mht_score_tracks_ct_grid(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                             const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_cand,
+                             const double* Q_cand, const double* R_cand, double* ll_out, double* nis_out, int32_t* nobs_out, void* work,
+                             size_t work_bytes);
+
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in
  * front of the scan; models/ais.py) that gates with it (eta2_ais, tracker.py:111): the leaf is predicted to the message's time,

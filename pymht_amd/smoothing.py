@@ -26,7 +26,12 @@ The same histories are SCORED here too: `score_tracks`, `score_tracks_ct`, `scor
 run the forward half of the smoother of that model and return per track the log-likelihood of its plots, their normalised innovation
 squared summed (NIS) and their number (`mht_score_tracks*`, one forward-only launch, nothing stored per node); node 0 is the initial state
 and not an observation, so the figures are not pykalman's loglikelihood(), which counts one at time 0.  `smooth_tracks_em(likelihoods=True)`
-hands out the log-likelihood under every EM iterate (`mht_smooth_tracks_em_ll`)."""
+hands out the log-likelihood under every EM iterate (`mht_smooth_tracks_em_ll`).
+
+To TUNE the noise by those figures the histories are scored under many candidate (Q, R) at once: `score_tracks_grid`,
+`score_tracks_ct_grid` (and `score_nodes_grid`, `Tracker.getLikelihoodSurface`) pack and upload a batch once and score every
+(track, candidate) in one launch (`mht_score_tracks_grid`); `noise_grid` makes the candidates of a grid of scalings of the model's own
+matrices, `best_cell` picks the cell of the largest likelihood -- the pooled maximum-likelihood pair over the grid."""
 import ctypes as C
 
 import numpy as np
@@ -369,6 +374,90 @@ def _score(ctx, model, period, tracks, nx, constant_turn, ais=None):
     return out
 
 
+GRID_MAX_CAND = 4096      # (SCORE_GRID_MAX_CAND of csrc/mht_smooth_score_grid.hip)
+
+
+def noise_grid(model, radarPeriod, qScales, rScales):
+    """The candidates of a likelihood surface over scalings of the model's own noise: (Q [G, nx, nx], R [G, 2, 2]) float64 with
+    G = len(qScales) * len(rScales), candidate iq * len(rScales) + ir being qScales[iq] * Q32 and rScales[ir] * R32 -- Q32 = Q(T) and
+    R32 = R_RADAR() as float32, the matrices every seam is handed (`_model_x`), so that scale 1 is the tracker's model itself.  The
+    products are float64: the grid is not rounded to float32.  Scales are finite and positive, else ValueError."""
+    q, r = (np.asarray(s, dtype=np.float64).reshape(-1) for s in (qScales, rScales))
+    for name, s in (("qScales", q), ("rScales", r)):
+        if s.size == 0 or not (np.isfinite(s).all() and (s > 0).all()):
+            raise ValueError("smoothing: %s are finite positive factors, at least one (got %r)" % (name, s.tolist()))
+    nx = int(np.asarray(model.C_RADAR).shape[1])
+    Q32 = np.asarray(model.Q(float(radarPeriod)), dtype=np.float32).astype(np.float64).reshape(nx, nx)
+    R32 = np.asarray(model.R_RADAR(), dtype=np.float32).astype(np.float64).reshape(2, 2)
+    Q = np.repeat(q, len(r))[:, None, None] * Q32
+    R = np.tile(r, len(q))[:, None, None] * R32
+    return Q, R
+
+
+def _check_candidates(Q, R, nx):
+    """(Q [G, nx, nx], R [G, 2, 2]) float64 C-contiguous, or ValueError"""
+    Q, R = np.ascontiguousarray(Q, dtype=np.float64), np.ascontiguousarray(R, dtype=np.float64)
+    if Q.ndim != 3 or Q.shape[1:] != (nx, nx) or R.ndim != 3 or R.shape[1:] != (2, 2) or len(Q) != len(R):
+        raise ValueError("smoothing: the candidates are Q [G, %d, %d] and R [G, 2, 2] (got %r and %r)" % (nx, nx, Q.shape, R.shape))
+    if not 1 <= len(Q) <= GRID_MAX_CAND:
+        raise ValueError("smoothing: 1 .. %d candidates a call (got %d)" % (GRID_MAX_CAND, len(Q)))
+    # (NaN is not symmetric either: the seam reads the upper triangle and would never see a bad lower one)
+    if not (np.array_equal(Q, Q.transpose(0, 2, 1)) and np.array_equal(R, R.transpose(0, 2, 1))):
+        raise ValueError("smoothing: a candidate covariance is not symmetric")
+    return Q, R
+
+
+def score_tracks_grid(model, radarPeriod, tracks, Q, R, device=0, ctx=None):
+    """`score_tracks` under G candidate noise models in ONE device launch (`mht_score_tracks_grid`): the histories are packed and
+    uploaded once, and every (track, candidate) is a lane of its own.  Q [G, nx, nx] and R [G, 2, 2] (float64, symmetric, 1 <= G <= 4096,
+    else ValueError; `noise_grid` makes a grid of scalings) replace the model's Q(T) and R_RADAR(); Phi(T) and C_RADAR stay.  `model`
+    and `tracks` as for `score_tracks`, with its checks and refusals.
+    Returns (ll [G, n], nis [G, n], nObs [n]) as NumPy arrays in the order of `tracks`; nObs does not depend on the candidate.  Row g is
+    what `score_tracks` gives for a model that carries candidate g -- bit for bit where the candidate is representable in float32, the
+    precision a model's matrices are handed over in; the candidates themselves are not rounded.  A candidate that is no covariance
+    (det S not positive at some plot) gives NaN in its (candidate, track) cells only.  An empty list gives shapes (G, 0), (G, 0), (0,)."""
+    return _score_grid_on(ctx, device, model, radarPeriod, tracks, Q, R, _check_model(model), False)
+
+
+def score_tracks_ct_grid(model, radarPeriod, tracks, Q, R, device=0, ctx=None):
+    """`score_tracks_grid` under the constant-turn model `score_tracks_ct` scores with (anything else raises ValueError)."""
+    return _score_grid_on(ctx, device, model, radarPeriod, tracks, Q, R, _check_ct_model(model), True)
+
+
+def _score_grid_on(ctx, device, model, radarPeriod, tracks, Q, R, nx, constant_turn):
+    Q, R = _check_candidates(Q, R, nx)
+    if len(tracks) == 0:
+        return np.zeros((len(Q), 0)), np.zeros((len(Q), 0)), np.zeros(0, dtype=np.int32)
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        return _score_grid(ctx, model, float(radarPeriod), tracks, Q, R, nx, constant_turn)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _score_grid(ctx, model, period, tracks, Q, R, nx, constant_turn):
+    n, G = len(tracks), len(Q)
+    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
+    dev, lib = ctx.device, ctx.lib
+    ll_d, nis_d = (torch.empty((G, n), dtype=torch.float64, device=dev) for _ in range(2))
+    nobs_d = torch.empty(n, dtype=torch.int32, device=dev)
+    need = int(lib.mht_score_grid_work_bytes(nx, n, L_max, G))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mx, keep = _model_x(model, period, nx, constant_turn)
+    lens_sorted = np.ascontiguousarray(lens[order])
+    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
+    seam = lib.mht_score_tracks_ct_grid if constant_turn else lib.mht_score_tracks_grid
+    _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(), z_d.data_ptr(),
+                    h_d.data_ptr(), G, Q.ctypes.data_as(C.c_void_p), R.ctypes.data_as(C.c_void_p), ll_d.data_ptr(), nis_d.data_ptr(),
+                    nobs_d.data_ptr(), work.data_ptr(), need), lib)
+    back = np.empty(n, dtype=np.int64)      # the callers' track t sits in packed column back[t]
+    back[order] = np.arange(n)
+    return ll_d.cpu().numpy()[:, back], nis_d.cpu().numpy()[:, back], nobs_d.cpu().numpy()[back]
+
+
 def chain_inputs(node, default_P0):
     """What the reference hands to its smoother for the track that ends in `node`: the initial state of the chain and
     backtrackMeasurement().  P_init is the first node's own covariance (the birth's), `default_P0` where it has none."""
@@ -447,3 +536,31 @@ def score_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fals
     for i, res in zip(where, score(model, radarPeriod, batch, device=device, ctx=ctx)):
         out[i] = res
     return out
+
+
+def best_cell(ll):
+    """The index (a tuple of ints) of the largest finite entry of a likelihood surface, the first in C order on ties; None if no entry
+    is finite (NaN marks a candidate that is no covariance, -inf is no likelihood either)."""
+    ll = np.asarray(ll, dtype=np.float64)
+    finite = np.isfinite(ll)
+    if not finite.any():
+        return None
+    return tuple(int(i) for i in np.unravel_index(np.argmax(np.where(finite, ll, -np.inf)), ll.shape))
+
+
+def score_nodes_grid(model, radarPeriod, nodes, Q, R, device=0, ctx=None, constantTurn=False):
+    """`score_tracks_grid` for many track nodes in one device call, built on `chain_inputs` like `score_nodes`: (ll [G, n], nis [G, n],
+    nObs [n]) with a column per node.  A chain of fewer than two nodes has nothing to explain: zeros in its column.  constantTurn as
+    for `score_nodes`; the messages of an AIS-aided tracker are not scored (the grid has no AIS model)."""
+    score = score_tracks_ct_grid if constantTurn else score_tracks_grid
+    nx = (_check_ct_model if constantTurn else _check_model)(model)
+    Q, R = _check_candidates(Q, R, nx)
+    batch, where = [], []
+    for i, node in enumerate(nodes):
+        chain, inputs = chain_inputs(node, model.P0)
+        if len(chain) >= 2:
+            batch.append(inputs)
+            where.append(i)
+    ll, nis, nobs = np.zeros((len(Q), len(nodes))), np.zeros((len(Q), len(nodes))), np.zeros(len(nodes), dtype=np.int32)
+    ll[:, where], nis[:, where], nobs[where] = score(model, radarPeriod, batch, Q, R, device=device, ctx=ctx)
+    return ll, nis, nobs

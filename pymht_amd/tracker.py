@@ -1031,6 +1031,33 @@ class Tracker():
         return smoothing.score_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
                                      ais=self._ais_lookup(constantTurn) if ais else None)
 
+    def getLikelihoodSurface(self, qScales, rScales, terminated=False, constantTurn=False):
+        """getTrackLikelihoods under a grid of noise levels in ONE device call: candidate (iq, ir) scores the same tracks with
+        qScales[iq] * Q(T) and rScales[ir] * R in place of the tracker's own (smoothing.noise_grid, score_nodes_grid; scales finite and
+        positive, else ValueError).  The pooled maximum-likelihood (Q, R) over the grid for ALL tracks -- one pair the constructor can
+        take, which per-track EM does not give -- and how flat the optimum is.  Returns a dict:
+            qScales, rScales     the grid, float64
+            ll, nis [nq, nr]     the tracks' log-likelihoods and NIS summed (np.sum in float64 on the host)
+            nObs                 the plots scored, int (the same for every cell)
+            trackLl, trackNis [nq, nr, n], trackNObs [n]     per track, in getTrackLikelihoods' order
+            best                 (iq, ir) of the largest finite ll, the first on ties; None if no cell is finite
+        Cell (iq, ir) with both scales 1 holds getTrackLikelihoods' figures bit for bit.  terminated and constantTurn as there, with
+        the same refusals.  There is no ais switch: the messages of an AIS-aided tracker are NOT scored, its tracks are scored from
+        their radar plots under the linear model."""
+        from . import smoothing
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        Q, R = smoothing.noise_grid(self._model_mod, self.radarPeriod, qScales, rScales)
+        q, r = np.asarray(qScales, dtype=np.float64).reshape(-1), np.asarray(rScales, dtype=np.float64).reshape(-1)
+        ll, nis, nobs = smoothing.score_nodes_grid(self._model_mod, self.radarPeriod, nodes, Q, R, ctx=self._ctx, constantTurn=constantTurn)
+        shape = (len(q), len(r), len(nodes))
+        out = {"qScales": q, "rScales": r, "trackLl": ll.reshape(shape), "trackNis": nis.reshape(shape), "trackNObs": nobs,
+               "nObs": int(nobs.sum())}
+        out["ll"], out["nis"] = np.sum(out["trackLl"], axis=2), np.sum(out["trackNis"], axis=2)
+        out["best"] = smoothing.best_cell(out["ll"])
+        return out
+
     def synchronize(self):
         """Wait for everything queued on the device and fold it (reports are folded lazily otherwise)."""
         self._drain()
