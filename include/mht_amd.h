@@ -32,7 +32,7 @@ extern "C" {
  * (libmht_amd6.so: the same sources compiled with -DMHT_NX=6 for BASELINE config 5's six-state model).  It sizes the model matrices
  * and the state vectors / covariances of the forest's reports; the stateless seams mht_gate_scan (4 states), mht_gate_scan_x and
  * mht_smooth_tracks and mht_smooth_tracks_em (4 or 6 at run time), mht_smooth_tracks_ct (6) and mht_smooth_tracks_ais (4), and the mht_score_tracks*
- * seams next to them, do not depend on it. */
+ * and mht_trace_tracks* seams next to them, do not depend on it. */
 #ifndef MHT_NX
 #define MHT_NX 4
 #endif
@@ -353,6 +353,39 @@ int mht_score_tracks_ct_grid(mht_ctx* ctx, const mht_model_x* model, int32_t n_t
                              const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_cand,
                              const double* Q_cand, const double* R_cand, double* ll_out, double* nis_out, int32_t* nobs_out, void* work,
                              size_t work_bytes);
+
+/* mht_trace_tracks, mht_trace_tracks_ct, mht_trace_tracks_ais: seam (vi) with its terms handed out PER NODE -- the innovation sequence the
+ * filter-consistency checks need (NIS inside its chi-square interval over time, whiteness of the innovations), and what says WHERE a model
+ * stops fitting a track.  The walks, models, inputs and checks are mht_score_tracks', mht_score_tracks_ct's and mht_score_tracks_ais's;
+ * the filtered states behind a trace are the score's own bits.  In place of the sums:
+ *   radar_out  dev [L_max][7][n_tracks] f64 out.  At node k >= 1 of a track with a radar measurement, with v = z_k - C xp_k and
+ *              S = C Pp_k C' + R:  elements 0, 1: v;  2, 3, 4: S00, S01, S11;  5: nis_k = v' S^-1 v;
+ *              6: ll_k = - 1/2 (ln det S + nis_k + 2 ln 2 pi) = ln N(z_k; C xp_k, S)
+ *   ais_out    (mht_trace_tracks_ais) dev [L_max][16][n_tracks] f64 out.  At a node that took a message (kind >= 2), at the message's
+ *              time, with v = m - xp(t_m) and S = Pp(t_m) + r I4:  elements 0 .. 3: v;  4 .. 13: the upper triangle of S, row by row;
+ *              14: nisAis_k = v' S^-1 v;  15: llAis_k = - 1/2 (ln det S + nisAis_k + 4 ln 2 pi)
+ * EVERY other cell of both arrays is written as well, with a quiet NaN: node 0 (the initial state, not an observation), a node without
+ * a measurement or without a message, and the rows len[t] <= k < L_max behind a track's end -- the arrays need not be initialised.  A
+ * det S that is not positive (a pivot of the factorisation, for a message) leaves v and S as computed and gives NaN in nis and ll of
+ * that node of that track only; has_z and kind, which the caller owns, tell such a node from one without a measurement.  Added up in
+ * node order (llAis_k in front of ll_k at a node with both) a track's ll_k, nis_k and nisAis_k are mht_score_tracks*' ll, nis and
+ * nis_ais bit for bit, and the cells that are not NaN-by-absence count nObs and nAis.
+ *   work       dev, work_bytes >= mht_trace_work_bytes(nx, n_tracks, L_max) (the lengths, nothing per node; 0 for a bad nx or a negative
+ *              size): MHT_E_INVALID if it is smaller.
+ * One launch, one track per lane, the stores of a wavefront contiguous; no track's figures depend on its place in the batch.
+ * Synchronises.  On MHT_E_INVALID nothing has been launched or written; n_tracks == 0 returns MHT_OK and writes nothing.  Exported by
+ * both builds (nx at run time). */
+size_t mht_trace_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max);
+int mht_trace_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                     const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* radar_out, void* work,
+                     size_t work_bytes);
+int mht_trace_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                        const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* radar_out, void* work,
+                        size_t work_bytes);
+int mht_trace_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                         const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, const uint8_t* kind,
+                         const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
+                         double* radar_out, double* ais_out, void* work, size_t work_bytes);
 
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in

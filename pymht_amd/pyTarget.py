@@ -273,6 +273,26 @@ class Target:
         return smoothing.score_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
                                      constantTurn=constantTurn, ais=lookup)[0]
 
+    def getTrackInnovations(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False):
+        """getTrackLikelihood with its terms handed out per node of the chain that ends in this node: a dict of NumPy arrays v [L, 2],
+        S [L, 2, 2], nis [L], ll [L], observed [L] (with ais=True also vAis, SAis, nisAis, llAis, message), NaN rows where a node has
+        no plot (pymht_amd.smoothing.trace_tracks defines the figures; a chain of fewer than two nodes has no observed node).  model,
+        constantTurn and ais as for getTrackLikelihood, with the same refusals.  Many nodes at once: Tracker.getTrackInnovations()."""
+        from . import smoothing
+        tracker = getattr(self, "_tracker", None)
+        lookup = None
+        if ais:
+            if tracker is None:
+                raise ValueError("ais=True needs the node of an AIS-aided Tracker: the messages are in the tracker's history")
+            lookup = tracker._ais_lookup(constantTurn)
+        if model is None:
+            if tracker is not None:
+                model = tracker._model_mod
+            else:
+                from .models import pv as model
+        return smoothing.trace_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
+                                     constantTurn=constantTurn, ais=lookup)[0]
+
     @staticmethod
     def _smoothed_state_element(states, node, position, velocity, precision=2):
         """One <S> of <SmoothedStates>, in the layout of _state_element: the node's time, smoothed position and velocity (north before east)."""

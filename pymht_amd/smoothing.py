@@ -31,7 +31,12 @@ hands out the log-likelihood under every EM iterate (`mht_smooth_tracks_em_ll`).
 To TUNE the noise by those figures the histories are scored under many candidate (Q, R) at once: `score_tracks_grid`,
 `score_tracks_ct_grid` (and `score_nodes_grid`, `Tracker.getLikelihoodSurface`) pack and upload a batch once and score every
 (track, candidate) in one launch (`mht_score_tracks_grid`); `noise_grid` makes the candidates of a grid of scalings of the model's own
-matrices, `best_cell` picks the cell of the largest likelihood -- the pooled maximum-likelihood pair over the grid."""
+matrices, `best_cell` picks the cell of the largest likelihood -- the pooled maximum-likelihood pair over the grid.
+
+The sums say whether a model fits a track; WHERE it stops fitting is in the sequence they add up: `trace_tracks`, `trace_tracks_ct`,
+`trace_tracks_ais` (and `trace_nodes`, `Tracker.getTrackInnovations`) run the score's walk and hand out per node the innovation, its
+covariance, the node's NIS and log-likelihood term (`mht_trace_tracks*`, one launch, 7 doubles per node and track, 16 more per AIS
+message); `consistency` runs the filter-consistency tests of the tracking literature on them, on the host."""
 import ctypes as C
 
 import numpy as np
@@ -371,6 +376,184 @@ def _score(ctx, model, period, tracks, nx, constant_turn, ais=None):
     out = [None] * n
     for j, t in enumerate(order):
         out[t] = tuple(float(c[j]) if c.dtype == np.float64 else int(c[j]) for c in cols)
+    return out
+
+
+_TRACE_SEAMS = {"linear": "mht_trace_tracks", "ct": "mht_trace_tracks_ct", "ais": "mht_trace_tracks_ais"}
+TRACE_RADAR_DOUBLES, TRACE_AIS_DOUBLES = 7, 16      # (csrc/mht_smooth_trace.h)
+
+
+def trace_tracks(model, radarPeriod, tracks, device=0, ctx=None):
+    """The innovation sequence behind `score_tracks`: per track a dict of NumPy arrays with a row per node,
+        v [L, 2]       z_k - C xp_k                      S [L, 2, 2]    C Pp_k C' + R
+        nis [L]        v' S^-1 v                         ll [L]         -1/2 (ln det S + nis + 2 ln 2 pi) = ln N(z_k; C xp_k, S)
+        observed [L]   bool: the node has a radar plot (never node 0, the initial state)
+    NaN in every row that is not observed.  `model` and `tracks` as for `score_tracks` (the same checks and refusals; an empty list
+    gives an empty list).  The filter is `score_tracks`' own, bit for bit: a track's ll and nis added up in node order are its
+    logLikelihood and nis there, and observed.sum() its nObs -- the sums say whether a model fits a track, the sequence says where it
+    stops (a manoeuvre, a misassociated plot, a run of correlated innovations from a Q too small: `consistency`).  An observed node
+    whose det S is not positive keeps v and S and has NaN in nis and ll.  One device launch (`mht_trace_tracks`)."""
+    return _trace_on(ctx, device, model, radarPeriod, tracks, _check_model(model), False)
+
+
+def trace_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None):
+    """`trace_tracks` under the constant-turn model `score_tracks_ct` scores with (anything else raises ValueError)."""
+    return _trace_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), True)
+
+
+def trace_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None):
+    """`trace_tracks` under the AIS-aware model of `score_tracks_ais`, same `tracks` and refusals.  Each dict also holds, at the
+    message's time of a node that took one (v = m - xp, S = Pp + sigma^2 I4; NaN rows elsewhere):
+        vAis [L, 4]    SAis [L, 4, 4]    nisAis [L]    llAis [L] = -1/2 (ln det S + nisAis + 4 ln 2 pi)    message [L] bool
+    `score_tracks_ais`' logLikelihood is llAis and ll added up in node order, llAis in front of ll at a node with both; nisAis adds
+    up to its nisAis.  A batch without any message gives `trace_tracks`' radar arrays bit for bit."""
+    nx = _check_ais_model(model)
+    ais = _ais_inputs(model, tracks)
+    return _trace_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, False, ais=ais)
+
+
+def _trace_on(ctx, device, model, radarPeriod, tracks, nx, constant_turn, ais=None):
+    if len(tracks) == 0:
+        return []
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        return _trace(ctx, model, float(radarPeriod), tracks, nx, constant_turn, ais)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _trace_dict(radar, observed, ais=None, message=None):
+    """One track's dict from its rows radar [L, 7] (and ais [L, 16]) as the seam lays them out."""
+    L = len(radar)
+    out = {"v": radar[:, 0:2].copy(), "S": radar[:, [2, 3, 3, 4]].reshape(L, 2, 2), "nis": radar[:, 5].copy(), "ll": radar[:, 6].copy(),
+           "observed": np.asarray(observed, dtype=bool).copy()}
+    if ais is not None:
+        iu = np.triu_indices(4)
+        S = np.empty((L, 4, 4))
+        S[:, iu[0], iu[1]] = ais[:, 4:14]
+        S[:, iu[1], iu[0]] = ais[:, 4:14]
+        out.update({"vAis": ais[:, 0:4].copy(), "SAis": S, "nisAis": ais[:, 14].copy(), "llAis": ais[:, 15].copy(),
+                    "message": np.asarray(message, dtype=bool).copy()})
+    return out
+
+
+def _blank_trace(L, ais=False):
+    """The trace of a chain nothing was filtered over: L rows, none observed."""
+    return _trace_dict(np.full((L, TRACE_RADAR_DOUBLES), np.nan), np.zeros(L, dtype=bool),
+                       np.full((L, TRACE_AIS_DOUBLES), np.nan) if ais else None, np.zeros(L, dtype=bool))
+
+
+def _trace(ctx, model, period, tracks, nx, constant_turn, ais=None):
+    n = len(tracks)
+    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
+    dev, lib, extra = ctx.device, ctx.lib, ()
+    outs = [torch.empty((L_max, TRACE_RADAR_DOUBLES, n), dtype=torch.float64, device=dev)]
+    if ais is not None:
+        extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
+        outs.append(torch.empty((L_max, TRACE_AIS_DOUBLES, n), dtype=torch.float64, device=dev))
+    need = int(lib.mht_trace_work_bytes(nx, n, L_max))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mx, keep = _model_x(model, period, nx, constant_turn)
+    lens_sorted = np.ascontiguousarray(lens[order])
+    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
+    seam = _TRACE_SEAMS["ais" if ais is not None else "ct" if constant_turn else "linear"]
+    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
+                                  z_d.data_ptr(), h_d.data_ptr(), *extra, *(o.data_ptr() for o in outs), work.data_ptr(), need), lib)
+    rows = [o.permute(2, 0, 1).contiguous().cpu().numpy() for o in outs]      # [track][node][element]
+    out = [None] * n
+    for j, t in enumerate(order):
+        L = int(lens[t])
+        out[t] = _trace_dict(rows[0][j, :L], hp[j, :L], rows[1][j, :L] if ais is not None else None,
+                             ais[0][t][0] if ais is not None else None)
+    return out
+
+
+def trace_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None):
+    """`trace_tracks` for many track nodes in one device call, built on `chain_inputs` / `chain_ais` like `score_nodes` (the same
+    switches and refusals): per node the dict of its chain, with ais also the message arrays.  A chain of fewer than two nodes has
+    nothing to explain: its rows are NaN and not observed."""
+    if ais is not None and constantTurn:
+        raise ValueError("smoothing: AIS-aware tracing is for 4-state linear models, not together with constantTurn")
+    trace = trace_tracks_ais if ais is not None else trace_tracks_ct if constantTurn else trace_tracks
+    (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
+    out, batch, where = [None] * len(nodes), [], []
+    for i, node in enumerate(nodes):
+        chain, inputs = chain_inputs(node, model.P0)
+        if len(chain) < 2:
+            out[i] = _blank_trace(len(chain), ais is not None)
+        else:
+            batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
+            where.append(i)
+    for i, res in zip(where, trace(model, radarPeriod, batch, device=device, ctx=ctx)):
+        out[i] = res
+    return out
+
+
+def consistency(traces, alpha=0.05):
+    """The filter-consistency tests of the tracking literature (Bar-Shalom, Li, Kirubarajan: Estimation with Applications to Tracking
+    and Navigation, ch. 5.4) on the radar innovations of `trace_tracks*` dicts, pooled over `traces`; host only, float64.  A dict of
+        nObs             the observed nodes
+        nisMean          their nis summed, divided by nObs: 2 under a consistent filter
+        nisInterval      (lo, hi) = chi2.ppf([alpha/2, 1 - alpha/2], 2 nObs) / nObs: where nisMean then lies with probability 1 - alpha
+        nisInside        lo <= nisMean <= hi.  Below: the filter's S is too large (R or Q too large); above: too small, or a bias
+        outlierFraction  the share of observed nodes with nis > chi2.ppf(1 - alpha, 2); alpha under a consistent filter
+        rho1             the lag-one autocorrelation of the whitened innovations e_k = L_k^-1 v_k, S_k = L_k L_k', over the nPairs
+                         pairs of consecutive nodes k, k + 1 of one track that both have a plot:
+                         sum e_k . e_{k+1} / sqrt(sum |e_k|^2  sum |e_{k+1}|^2)
+        rho1Bound        norm.ppf(1 - alpha/2) / sqrt(2 nPairs): |rho1| stays below it with probability 1 - alpha when the
+                         innovations are white (a Q too small, or an unmodelled manoeuvre, correlates them)
+        white            |rho1| <= rho1Bound
+        nPairs, alpha
+    Without an observed node (without a pair) the statistics that need one are NaN and their verdict is None; so is the verdict over a
+    statistic that is NaN.  An observed node with a NaN nis (a det S that was not positive) makes nisMean and outlierFraction NaN, as it
+    makes the track's score NaN.  alpha outside (0, 1) raises ValueError."""
+    from scipy.stats import chi2, norm
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not 0.0 < float(alpha) < 1.0:
+        raise ValueError("smoothing: alpha is a probability strictly between 0 and 1 (got %r)" % (alpha,))
+    alpha = float(alpha)
+    nan = float("nan")
+    n_obs = n_pairs = 0
+    nis_sum = num = den_a = den_b = 0.0
+    outliers = 0
+    threshold = float(chi2.ppf(1.0 - alpha, 2))
+    for tr in traces:
+        obs = np.asarray(tr["observed"], dtype=bool)
+        nis = np.asarray(tr["nis"], dtype=np.float64)[obs]
+        n_obs += int(obs.sum())
+        nis_sum += float(np.sum(nis))
+        outliers += int(np.sum(nis > threshold))
+        pair = obs[:-1] & obs[1:]
+        if not pair.any():
+            continue
+        v, S = np.asarray(tr["v"], dtype=np.float64), np.asarray(tr["S"], dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):      # (rows that are not observed are NaN, and are not read below)
+            l00 = np.sqrt(S[:, 0, 0])
+            l10 = S[:, 0, 1] / l00
+            l11 = np.sqrt(S[:, 1, 1] - l10 * l10)
+            e0 = v[:, 0] / l00
+            e = np.stack([e0, (v[:, 1] - l10 * e0) / l11], axis=1)
+        a, b = e[:-1][pair], e[1:][pair]
+        n_pairs += int(pair.sum())
+        num += float(np.sum(a * b))
+        den_a += float(np.sum(a * a))
+        den_b += float(np.sum(b * b))
+    out = {"nObs": n_obs, "nPairs": n_pairs, "alpha": alpha, "nisMean": nan, "nisInterval": (nan, nan), "nisInside": None,
+           "outlierFraction": nan, "rho1": nan, "rho1Bound": nan, "white": None}
+    if n_obs > 0:
+        lo, hi = (float(q) / n_obs for q in chi2.ppf([alpha / 2.0, 1.0 - alpha / 2.0], 2 * n_obs))
+        out["nisMean"], out["nisInterval"] = nis_sum / n_obs, (lo, hi)
+        if np.isfinite(out["nisMean"]):
+            out["nisInside"] = bool(lo <= out["nisMean"] <= hi)
+            out["outlierFraction"] = outliers / n_obs
+    if n_pairs > 0:
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["rho1"] = float(np.float64(num) / np.sqrt(np.float64(den_a) * np.float64(den_b)))
+        out["rho1Bound"] = float(norm.ppf(1.0 - alpha / 2.0) / np.sqrt(2.0 * n_pairs))
+        if np.isfinite(out["rho1"]):
+            out["white"] = bool(abs(out["rho1"]) <= out["rho1Bound"])
     return out
 
 

@@ -1031,6 +1031,26 @@ class Tracker():
         return smoothing.score_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
                                      ais=self._ais_lookup(constantTurn) if ais else None)
 
+    def getTrackInnovations(self, terminated=False, constantTurn=False, ais=False):
+        """getTrackLikelihoods with its terms handed out per node: one dict of NumPy arrays per track, in getTrackLikelihoods' order --
+        v [L, 2], S [L, 2, 2], nis [L], ll [L], observed [L] (and with ais=True vAis [L, 4], SAis [L, 4, 4], nisAis [L], llAis [L],
+        message [L]), NaN rows where a node has no plot (no message): the innovation sequence of the tracker's filter, which says WHERE
+        on a track the model stops fitting (smoothing.trace_nodes / trace_tracks define the figures; one device call).  Added up in
+        node order they are getTrackLikelihoods' sums bit for bit.  terminated, constantTurn and ais as there, with the same refusals."""
+        from . import smoothing
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        return smoothing.trace_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
+                                     ais=self._ais_lookup(constantTurn) if ais else None)
+
+    def getConsistency(self, alpha=0.05, terminated=False, constantTurn=False, ais=False):
+        """The filter-consistency statistics of the tracks' radar innovations, pooled over getTrackInnovations' traces
+        (smoothing.consistency: the time-average NIS against its chi-square interval, the share of outliers, the lag-one
+        autocorrelation of the whitened innovations against its bound); alpha is the tests' size."""
+        from . import smoothing
+        return smoothing.consistency(self.getTrackInnovations(terminated=terminated, constantTurn=constantTurn, ais=ais), alpha=alpha)
+
     def getLikelihoodSurface(self, qScales, rScales, terminated=False, constantTurn=False):
         """getTrackLikelihoods under a grid of noise levels in ONE device call: candidate (iq, ir) scores the same tracks with
         qScales[iq] * Q(T) and rScales[ir] * R in place of the tracker's own (smoothing.noise_grid, score_nodes_grid; scales finite and
