@@ -387,6 +387,35 @@ int mht_trace_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_track
                          const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
                          double* radar_out, double* ais_out, void* work, size_t work_bytes);
 
+/* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
+ * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);
+ * with d_ij = sqrt(dx dx + dy dy) in float64 and only pairs with d_ij < c (strictly) assignable,
+ *     total = min over partial one-to-one assignments of  sum d_ij^p + c^p / 2 (n + m - 2 |assigned|)            (GOSPA = total^(1/p))
+ * and at the optimum loc = sum d_ij^p over the assigned pairs, nMissed = m - |assigned|, nFalse = n - |assigned|.
+ *   n_steps    steps of the batch; 0 returns MHT_OK and writes nothing
+ *   est_off    host [n_steps + 1]: step s has estimates est_off[s] .. est_off[s + 1] - 1 of est_xy; est_off[0] == 0, non-decreasing
+ *   est_xy     dev [est_off[n_steps]][2] f64 (NULL if there is none)
+ *   tru_off    host [n_steps + 1], tru_xy dev [tru_off[n_steps]][2] f64: the same for the true positions
+ *   c, p       the cut-off, finite and positive (and c^p a finite positive float64); p = 1 or 2.  p = 2 takes no root, p = 1 one;
+ *              there is no pow
+ *   step_out   dev [n_steps][2] f64 out: total, loc
+ *   count_out  dev [n_steps][3] int32 out: nAssigned, nMissed, nFalse
+ *   match_out  dev [est_off[n_steps]] int32 out: per estimate the index of its true position LOCAL to the step, or -1
+ *   work       dev, work_bytes >= mht_gospa_work_bytes(n_steps, n_est_total, n_tru_total) (the offsets; 0 for a negative size and for
+ *              an empty batch)
+ * Every cell of the three outputs that belongs to a step is written: they need not be initialised.  The sums are float64, in an order
+ * that is the same wherever in the batch a step sits.  Where several assignments are optimal one of them is reported.  A coordinate
+ * that is not finite never satisfies d < c: its object is never assigned (pymht_amd.evaluation refuses such input).  Should a step's
+ * search run into its iteration bound -- every loop is counted, none spins -- its total and loc are NaN and its matches -1.
+ * One launch, one step per workgroup of one wavefront, the search tables in LDS (csrc/mht_gospa.h).  Synchronises.
+ * MHT_E_INVALID: a null pointer where a size is not zero, a negative count, offsets that decrease or do not start at 0, a bad c or p,
+ * a short workspace.  MHT_E_CAPACITY: a step with more than 2048 objects on either side.  On either nothing has been launched or
+ * written.  Exported by both builds. */
+size_t mht_gospa_work_bytes(int32_t n_steps, int32_t n_est_total, int32_t n_tru_total);
+int mht_gospa_steps(mht_ctx* ctx, int32_t n_steps, const int32_t* est_off, const double* est_xy, const int32_t* tru_off,
+                    const double* tru_xy, double c, int32_t p, double* step_out, int32_t* count_out, int32_t* match_out, void* work,
+                    size_t work_bytes);
+
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in
  * front of the scan; models/ais.py) that gates with it (eta2_ais, tracker.py:111): the leaf is predicted to the message's time,

@@ -151,6 +151,7 @@ def _declare(lib, nx=4):
         "mht_trace_tracks": [vp, C.POINTER(MhtModelX), i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_trace_tracks_ct": [vp, C.POINTER(MhtModelX), i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_trace_tracks_ais": [vp, C.POINTER(MhtModelX), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_size_t],
+        "mht_gospa_steps": [vp, i32, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
         "mht_forest_create_ex": [vp, vp, vp, C.c_uint32],
         "mht_forest_set_ais": [vp, vp, i32, vp, i32, dbl, dbl],
         "mht_forest_read_mmsi": [vp, i32, i32, i32, vp, vp],
@@ -210,6 +211,8 @@ def _declare(lib, nx=4):
     lib.mht_score_grid_work_bytes.restype = C.c_size_t
     lib.mht_trace_work_bytes.argtypes = [i32, i32, i32]
     lib.mht_trace_work_bytes.restype = C.c_size_t
+    lib.mht_gospa_work_bytes.argtypes = [i32, i32, i32]
+    lib.mht_gospa_work_bytes.restype = C.c_size_t
 
 
 def check(rc, lib=None):

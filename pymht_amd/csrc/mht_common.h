@@ -98,6 +98,7 @@ enum KernelSlot : int {
     K_GATE, K_CLUSTER, K_CLUSTER_INIT, K_CLUSTER_BIG, K_CLUSTER_BATCH, K_BLP, K_BLP_UF, K_BLP_BATCH, K_BLP_LIGHT_BATCH,
     K_SMOOTH_EM4, K_SMOOTH_EM6,      // (no LDS: the slots only route mht_smooth_tracks_em through launch_kernel)
     K_SMOOTH_SCORE,                  // (no LDS either: every kernel of mht_smooth_score.hip goes through launch_kernel under this one)
+    K_GOSPA,                         // gospa_kernel (mht_gospa.hip): the search tables of the launch's largest step, 56 KB at 2048 x 2048
     K_FGROW,
     K_SLOTS = K_FGROW + FG_FAMILIES * 3 * 2
 };

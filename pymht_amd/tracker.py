@@ -1051,6 +1051,58 @@ class Tracker():
         from . import smoothing
         return smoothing.consistency(self.getTrackInnovations(terminated=terminated, constantTurn=constantTurn, ais=ais), alpha=alpha)
 
+    def getGospa(self, truth, c, p=2, terminated=True, smooth=False, constantTurn=False, ais=False):
+        """The track histories scored against ground truth: GOSPA per step (evaluation.gospa_steps, which defines the figures; one
+        device launch for all steps), the one figure here that says whether the tracker FOUND the targets -- missed targets, false
+        tracks and track switches, which no likelihood sees.
+
+        truth   a sequence of (time, positions [m, >= 2]), or a pair (times, positions per time) such as
+                (sc["times"], sc["truth"]) of a scenario; only the first two columns of the positions are read
+        c, p    GOSPA's cut-off and exponent (1 or 2)
+        The steps are the truth's times.  The estimates of a step are the positions of the nodes with that time stamp (compared with
+        == on the float the MeasurementList carried) on the track histories of __trackNodes__, with terminated=True (the default)
+        also of __terminatedTargets__; nodes at other times -- the initial state of a track is one -- are left out and counted in
+        nIgnored.  smooth=True: the positions are getSmoothTracks' instead of the filtered ones, constantTurn and ais select that
+        call's smoother and carry its refusals (without smooth=True they are refused: ValueError).
+
+        THESE ARE THE HISTORIES AS THEY STAND AT THE CALL: resolved by the N-scan window, every track one chain.  They are not the
+        estimates the tracker reported online at each scan, which a hypothesis pruned since may have produced.
+
+        Returns gospa_steps' dict (gospa, total, localisation, missed, false, nAssigned, nMissed, nFalse over the steps, match per
+        step) plus times, trackIds (per step the track ID of every estimate, in the order of match), idSwitches (evaluation.id_switches
+        over the truths' rows: (total, perTruth)), nIgnored, and the means over the steps meanGospa, meanLocalisation, meanMissed,
+        meanFalse (NaN without steps)."""
+        from . import evaluation
+        if (constantTurn or ais) and not smooth:
+            raise ValueError("getGospa: constantTurn and ais select the smoother of smooth=True; the filtered positions need neither")
+        c, p = evaluation._check_cutoff(c, p)
+        times, Y = evaluation.truth_steps(truth)
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        smoothed = self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais) if smooth else None
+        step_of = {}
+        for s, t in enumerate(times):
+            step_of.setdefault(float(t), s)
+        X, ids, nIgnored = [[] for _ in times], [[] for _ in times], 0
+        for i, leaf in enumerate(nodes):
+            chain = leaf.backtrackNodes()
+            tid = leaf.ID if leaf.ID is not None else chain[0].ID if chain[0].ID is not None else -(i + 1)
+            for k, node in enumerate(chain):
+                s = step_of.get(float(node.time))
+                if s is None:
+                    nIgnored += 1
+                    continue
+                pos = smoothed[i][0][k] if smooth and len(chain) >= 2 else node.x_0[0:2]      # (a chain of one node has nothing to smooth)
+                X[s].append(np.asarray(pos, dtype=np.float64).reshape(2))
+                ids[s].append(tid)
+        out = evaluation.gospa_steps([np.array(x, dtype=np.float64).reshape(-1, 2) for x in X], Y, c, p, ctx=self._ctx)
+        out["times"], out["trackIds"], out["nIgnored"] = times, ids, nIgnored
+        out["idSwitches"] = evaluation.id_switches(out["match"], ids)
+        for key, name in (("gospa", "meanGospa"), ("localisation", "meanLocalisation"), ("missed", "meanMissed"), ("false", "meanFalse")):
+            out[name] = float(np.mean(out[key])) if len(times) else float("nan")
+        return out
+
     def getLikelihoodSurface(self, qScales, rScales, terminated=False, constantTurn=False):
         """getTrackLikelihoods under a grid of noise levels in ONE device call: candidate (iq, ir) scores the same tracks with
         qScales[iq] * Q(T) and rScales[ir] * R in place of the tracker's own (smoothing.noise_grid, score_nodes_grid; scales finite and
