@@ -416,6 +416,47 @@ int mht_gospa_steps(mht_ctx* ctx, int32_t n_steps, const int32_t* est_off, const
                     const double* tru_xy, double c, int32_t p, double* step_out, int32_t* count_out, int32_t* match_out, void* work,
                     size_t work_bytes);
 
+/* mht_ospa2_windows: whole tracks scored against truth trajectories -- OSPA(2) (Beard, Vo, Vo, "A solution for large-scale multi-object
+ * tracking", IEEE TSP 2020) of a batch of windows of one run.  Per-step GOSPA says whether the targets were found at each step; it
+ * cannot say whether they were KEPT: a track cut into two fragments, or two tracks that swap targets, score 0 at every step.  OSPA(2)
+ * is OSPA between the SET OF TRACKS and the SET OF TRUTH TRAJECTORIES, with the time-averaged cut-off distance of a pair as its base
+ * distance, so a fragment pays the cut-off for every step of the trajectory it does not cover.
+ * A run has n_steps steps, n_trk tracks and n_tru truths, each with a position and a presence flag at every step (gaps allowed).  A
+ * window is the inclusive range of steps [lo, hi].  For one window:
+ *   members    a track / truth present at one or more of its steps; n_w and m_w of them, N = max(n_w, m_w)
+ *   D_ij       of members i, j: over the U >= 1 steps of the window at which at least one of the two is present, a step is NEAR if both
+ *              are present and d = sqrt(dx dx + dy dy) < c (float64, strictly), else FAR.  No near step: D_ij = c exactly and (i, j) is no
+ *              edge.  Else D_ij = (c nFar + sum of d over the near steps) / U, an edge iff D_ij < c as computed.  The time average
+ *              has order 1: there is no pow.
+ *   total      min over one-to-one assignments on edges of  sum D_ij^p + c^p (N - nAssigned)        (OSPA(2) = (total / N)^(1/p), 0 if N = 0)
+ *   loc        sum D_ij^p over the assigned pairs; the cardinality part is c^p (N - nAssigned)
+ * (OSPA on D, since D <= c: leaving a member of the smaller side out costs what assigning it at c would.)
+ *   trk_xy     dev [n_steps][n_trk][2] f64, 16-byte aligned; trk_on dev [n_steps][n_trk] uint8, non-zero = present.  Step-major: the lanes
+ *              of a wavefront read consecutive objects.  A position whose flag is 0 never reaches a result (it may be NaN).
+ *   tru_xy     dev [n_steps][n_tru][2], tru_on dev [n_steps][n_tru]: the same for the truths
+ *   win_lo, win_hi   host [n_win]: 0 <= lo <= hi < n_steps
+ *   c, p       as in mht_gospa_steps
+ *   win_out    dev [n_win][2] f64 out: total, loc
+ *   count_out  dev [n_win][3] int32 out: nAssigned, n_w, m_w
+ *   match_out  dev [n_win][n_trk] int32 out: the truth index of a track, -1 for an unassigned member, -2 for a track that is no member
+ *   work       dev, 16-byte aligned, work_bytes >= mht_ospa2_work_bytes(n_trk, n_tru, n_steps, n_win): the windows, the member lists and
+ *              one n_trk x n_tru float64 matrix per window (0 for a negative size, a side above 2048 and an empty batch)
+ * Every cell of the three outputs is written.  A window's outputs are the same wherever in the batch it stands.  Should a window's search
+ * run into its iteration bound its total and loc are NaN and no track of it is assigned.  Three launches on the context's stream
+ * (membership; the base distances, O(n_win n_trk n_tru W); one wavefront per window for the search of csrc/mht_gospa.h with its tables
+ * in LDS), then the seam waits.  n_win == 0 or n_steps == 0: MHT_OK, nothing launched or written.
+ * MHT_E_INVALID: a null array with a non-zero count, a negative count, p not 1 or 2, a bad c, a window with lo < 0, hi >= n_steps or
+ * lo > hi, positions or workspace not aligned, a short workspace.  MHT_E_CAPACITY: more than 2048 tracks or truths.  On either nothing has
+ * been launched or written.  Exported by both builds.
+ * mht_ospa2_set_timing(1) makes later calls of this process (of at most 32768 windows) record events around the three launches;
+ * mht_ospa2_stage_times gives the last such call's ms [3]: membership, base distances, assignment (tools/ospa2_cost.py). */
+size_t mht_ospa2_work_bytes(int32_t n_trk, int32_t n_tru, int32_t n_steps, int32_t n_win);
+int mht_ospa2_windows(mht_ctx* ctx, int32_t n_steps, int32_t n_trk, const double* trk_xy, const uint8_t* trk_on, int32_t n_tru,
+                      const double* tru_xy, const uint8_t* tru_on, int32_t n_win, const int32_t* win_lo, const int32_t* win_hi, double c,
+                      int32_t p, double* win_out, int32_t* count_out, int32_t* match_out, void* work, size_t work_bytes);
+void mht_ospa2_set_timing(int32_t on);
+void mht_ospa2_stage_times(float* ms);
+
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in
  * front of the scan; models/ais.py) that gates with it (eta2_ais, tracker.py:111): the leaf is predicted to the message's time,

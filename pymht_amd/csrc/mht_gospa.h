@@ -169,9 +169,28 @@ GOSPA_FN double gospa_dp(const GospaStep& s, double rx, double ry, int j) {
     return s.p == 2 ? d2 : sqrt(d2);
 }
 
-// The assignment: owner[j] of every column on return.  false: a loop ran into its bound.  *sweeps counts the sweeps.
-GOSPA_FN bool gospa_solve(const GospaStep& s, const GospaTables& t, int32_t* sweeps) {
-    const int nr = s.n_rows, nc = s.n_cols;
+// Where the search takes an edge's weight from (its COST): row(i) makes row i the one the next sweep relaxes from (wavefront-uniform),
+// edge(j, w) says whether (that row, column j) is an edge and gives its weight w = d^p - c^p.  GospaXYCost is GOSPA's own, distances
+// between positions; mht_ospa2.h reads a matrix of base distances instead.
+struct GospaXYCost {
+    const GospaStep& s;
+    double rx, ry;
+    GOSPA_FN explicit GospaXYCost(const GospaStep& step) : s(step), rx(0.0), ry(0.0) {}
+    GOSPA_FN void row(int i) {
+        rx = gospa_uniform(s.row_xy[2 * i]);
+        ry = gospa_uniform(s.row_xy[2 * i + 1]);
+    }
+    GOSPA_FN bool edge(int j, double& w) const {
+        const double dp = gospa_dp(s, rx, ry, j);
+        w = dp - s.cp;
+        return dp < s.lim;
+    }
+};
+
+// The assignment of nr rows to nc >= nr columns under a cost: owner[j] of every column on return.  false: a loop ran into its bound.
+// *sweeps counts the sweeps.
+template <class Cost>
+GOSPA_FN bool gospa_search(Cost& cost, int nr, int nc, const GospaTables& t, int32_t* sweeps) {
     const double inf = HUGE_VAL;
     GOSPA_EACH_LANE(lane) {
         for (int j = lane; j < nc; j += GOSPA_LANES) {
@@ -195,7 +214,8 @@ GOSPA_FN bool gospa_solve(const GospaStep& s, const GospaTables& t, int32_t* swe
         bool found = false;
         for (int sweep = 0; sweep < nc + 2; ++sweep) {
             ++n_sweeps;
-            const double rx = gospa_uniform(s.row_xy[2 * i0]), ry = gospa_uniform(s.row_xy[2 * i0 + 1]), ui = gospa_uniform(t.u[i0]);
+            cost.row(i0);
+            const double ui = gospa_uniform(t.u[i0]);
             if (-ui < min_exit) {
                 min_exit = -ui;
                 way_exit = j0;
@@ -208,10 +228,11 @@ GOSPA_FN bool gospa_solve(const GospaStep& s, const GospaTables& t, int32_t* swe
                 int bj = 0x7fffffff;
                 for (int k = 0, j = lane; j < nc; ++k, j += GOSPA_LANES) {
                     if ((um >> k) & 1u) continue;
-                    const double dp = gospa_dp(s, rx, ry, j);
+                    double w;
+                    const bool is_edge = cost.edge(j, w);
                     double m = t.minv[j];
-                    if (dp < s.lim) {
-                        const double cur = (dp - s.cp) - ui - t.v[j];
+                    if (is_edge) {
+                        const double cur = w - ui - t.v[j];
                         if (cur < m) {
                             m = cur;
                             t.minv[j] = cur;
@@ -284,6 +305,12 @@ GOSPA_FN bool gospa_solve(const GospaStep& s, const GospaTables& t, int32_t* swe
     }
     if (sweeps) *sweeps = n_sweeps;
     return ok;
+}
+
+// GOSPA's own instance: the cost from the step's positions
+GOSPA_FN bool gospa_solve(const GospaStep& s, const GospaTables& t, int32_t* sweeps) {
+    GospaXYCost cost(s);
+    return gospa_search(cost, s.n_rows, s.n_cols, t, sweeps);
 }
 
 // One step from its sets to its outputs: step_out [2] = total, loc; count_out [3] = nAssigned, nMissed, nFalse; match_out [n_est] =

@@ -1103,6 +1103,61 @@ class Tracker():
             out[name] = float(np.mean(out[key])) if len(times) else float("nan")
         return out
 
+    def getOspa2(self, truth, c, p=2, window=None, every=1, terminated=True, smooth=False, constantTurn=False, ais=False, truthIds=None):
+        """The track histories scored against the truth TRAJECTORIES: OSPA(2) over windows of steps (evaluation.ospa2_windows, which
+        defines the figures).  Per-scan GOSPA assigns every scan on its own, so this is the figure that sees whether the targets were
+        KEPT: a track cut into fragments, two tracks that swap targets and a late confirmation all cost here and score 0 there.
+
+        truth      getGospa's two forms: a sequence of (time, positions [m, >= 2]), or a pair (times, positions per time)
+        truthIds   None: a truth's identity is its row index, and every step needs the same number of rows (ValueError otherwise).  Else
+                   per step the identities of the step's rows (any hashable, as evaluation.id_switches takes them).  A row whose first
+                   two columns are NaN is absent at that step.
+        c, p       the cut-off and the exponent (1 or 2)
+        window, every   None: one window, the whole run; W: sliding windows of W steps that end at steps 0, every, 2 every, ...
+        The steps are the truth's times.  A track is one history -- a node of __trackNodes__, with terminated=True (the default) also of
+        __terminatedTargets__, and its ancestors -- present at the steps whose time one of its nodes carries (compared with == on the
+        float the MeasurementList carried); nodes at other times, the initial state of a track among them, are left out and counted in
+        nIgnored.  smooth, constantTurn and ais as in getGospa, with the same refusals.
+
+        THESE ARE THE HISTORIES AS THEY STAND AT THE CALL: resolved by the N-scan window, every track one chain.  They are not the
+        estimates the tracker reported online at each scan, which a hypothesis pruned since may have produced.
+
+        Returns ospa2_windows' dict (ospa2, total, localisation, cardinality, nAssigned, nTracks, nTruths, windows, match [n_win, n]
+        with the truth's COLUMN: its row index, or its place in order of first appearance under truthIds) plus times (of the windows'
+        last steps), trackIds [n], nIgnored and meanOspa2 (NaN without windows)."""
+        from . import evaluation
+        if (constantTurn or ais) and not smooth:
+            raise ValueError("getOspa2: constantTurn and ais select the smoother of smooth=True; the filtered positions need neither")
+        c, p = evaluation._check_cutoff(c, p)
+        times, Y = evaluation.truth_steps(truth)
+        truthXY, truthOn = evaluation.truth_trajectories(Y, truthIds)
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        smoothed = self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais) if smooth else None
+        step_of = {}
+        for s, t in enumerate(times):
+            step_of.setdefault(float(t), s)
+        trackXY = np.full((len(times), len(nodes), 2), np.nan)
+        trackOn = np.zeros((len(times), len(nodes)), dtype=np.uint8)
+        ids, nIgnored = [], 0
+        for i, leaf in enumerate(nodes):
+            chain = leaf.backtrackNodes()
+            ids.append(leaf.ID if leaf.ID is not None else chain[0].ID if chain[0].ID is not None else -(i + 1))
+            for k, node in enumerate(chain):
+                s = step_of.get(float(node.time))
+                if s is None:
+                    nIgnored += 1
+                    continue
+                pos = smoothed[i][0][k] if smooth and len(chain) >= 2 else node.x_0[0:2]      # (a chain of one node has nothing to smooth)
+                trackXY[s, i] = np.asarray(pos, dtype=np.float64).reshape(2)
+                trackOn[s, i] = 1
+        out = evaluation.ospa2_windows(trackXY, trackOn, truthXY, truthOn, c, p, window=window, every=every, ctx=self._ctx)
+        out["times"] = times[out["windows"][:, 1]] if len(out["windows"]) else np.zeros(0)
+        out["trackIds"], out["nIgnored"] = ids, nIgnored
+        out["meanOspa2"] = float(np.mean(out["ospa2"])) if len(out["ospa2"]) else float("nan")
+        return out
+
     def getLikelihoodSurface(self, qScales, rScales, terminated=False, constantTurn=False):
         """getTrackLikelihoods under a grid of noise levels in ONE device call: candidate (iq, ir) scores the same tracks with
         qScales[iq] * Q(T) and rScales[ir] * R in place of the tracker's own (smoothing.noise_grid, score_nodes_grid; scales finite and
