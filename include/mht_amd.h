@@ -387,6 +387,53 @@ int mht_trace_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_track
                          const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
                          double* radar_out, double* ais_out, void* work, size_t work_bytes);
 
+/* mht_filter_tracks, mht_filter_tracks_ct, mht_filter_tracks_ais: the FILTERED state and covariance of every node of a batch of track
+ * histories -- what seam (v) computes on its way forward and keeps in its workspace, and what the score and trace seams compute and
+ * discard.  The walks, models, inputs and checks are mht_trace_tracks', mht_trace_tracks_ct's and mht_trace_tracks_ais's: the float64
+ * filter of the smoothers, run over the history from the chain's initial state (not the forest's own float32 / float64 chains).  In
+ * place of the trace:
+ *   xf   dev [L_max][nx][n_tracks] f64 out: the filtered mean of node k.  Node 0 is x_init; node k >= 1 is the state behind the step to
+ *        the node and, with a measurement, its radar update -- at the scan's time (an AIS message is taken on the way there)
+ *   Pf   dev [L_max][nx (nx + 1) / 2][n_tracks] f64 out: its covariance, the upper triangle row by row (the layout of seam (v)'s Ps)
+ * The rows len[t] <= k < L_max behind a track's end are written as well, with a quiet NaN: the arrays need not be initialised.  The
+ * filtered states are the smoother's own bits: for every track, rows len[t] - 1 of xf and Pf equal those of xs and Ps of
+ * mht_smooth_tracks* on the same batch (the last node's filtered state is its smoothed state).
+ *   work dev, work_bytes >= mht_filter_work_bytes(nx, n_tracks, L_max) (the lengths, nothing per node: mht_score_work_bytes' figure; 0
+ *        for a bad nx or a negative size): MHT_E_INVALID if it is smaller.
+ * One launch, one track per lane, the stores of a wavefront contiguous; no track's figures depend on its place in the batch.
+ * Synchronises.  On MHT_E_INVALID nothing has been launched or written; n_tracks == 0 returns MHT_OK and writes nothing.  Exported by
+ * both builds (nx at run time). */
+size_t mht_filter_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max);
+int mht_filter_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                      const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* xf, double* Pf, void* work,
+                      size_t work_bytes);
+int mht_filter_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                         const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* xf, double* Pf, void* work,
+                         size_t work_bytes);
+int mht_filter_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                          const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, const uint8_t* kind,
+                          const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
+                          double* xf, double* Pf, void* work, size_t work_bytes);
+
+/* mht_nees_nodes: is the covariance a filter reports honest?  The estimation error e = x - truth and the normalised estimation error
+ * squared e' P^-1 e of every node of a batch against ground truth -- the test that sees the unmeasured states, which the innovations
+ * (mht_trace_tracks*) do not.  The inputs lie where mht_filter_tracks* (xf, Pf) or mht_smooth_tracks* (xs, Ps) wrote them:
+ *   nx       4 or 6;  D: 2, 4 or nx -- the leading components [x, y, vx, vy, ...] the truth carries
+ *   x        dev [L_max][nx][n_tracks] f64;  P dev [L_max][nx (nx + 1) / 2][n_tracks] f64, the packed upper triangle
+ *   truth    dev [L_max][nx][n_tracks] f64: components >= D are not read
+ *   present  dev [L_max][n_tracks] uint8: non-zero where the node has a truth to be held against
+ *   out      dev [L_max][nx + 3][n_tracks] f64 out: elements 0 .. nx - 1: e (NaN at components >= D);  nx: nees2, over the position;
+ *            nx + 1: nees4, over position and velocity;  nx + 2: neesN, over the full state
+ * One factorisation P = U' U and one forward substitution U' y = e per cell give all three: the sum of y_j^2 over j < d is the NEES of
+ * the leading d components under their marginal covariance, exactly.  A figure that needs components beyond D is NaN.  A cell whose flag
+ * is 0, or whose x or P holds a NaN (the rows behind a track's end), is NaN throughout.  A pivot j that is not positive gives NaN in
+ * every figure that includes component j, in that cell only; the figures in front of it stay valid.  EVERY cell is written.
+ * One launch, one cell per lane with the track index fastest (loads and stores of a wavefront contiguous).  Synchronises.
+ * MHT_E_INVALID: a bad nx or D, a negative size, a null array of a batch that is not empty; nothing has then been launched or written.
+ * n_tracks == 0 or L_max == 0 returns MHT_OK.  Exported by both builds. */
+int mht_nees_nodes(mht_ctx* ctx, int32_t nx, int32_t n_tracks, int32_t L_max, int32_t D, const double* x, const double* P,
+                   const double* truth, const uint8_t* present, double* out);
+
 /* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
  * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);
  * with d_ij = sqrt(dx dx + dy dy) in float64 and only pairs with d_ij < c (strictly) assignable,

@@ -15,7 +15,13 @@ not depend on each other: `gospa_steps` packs them, uploads once and solves all 
 Per-step GOSPA says whether the targets were found at each step, not whether they were KEPT: every step is assigned on its own, so a
 track cut into two fragments scores like an unbroken one.  `ospa2_windows` scores whole tracks against whole truth trajectories, OSPA(2)
 (Beard, Vo, Vo 2020) over windows of steps (`mht_ospa2_windows`, csrc/mht_ospa2.hip), and `Tracker.getOspa2` applies it to a tracker's
-histories."""
+histories.
+
+Neither says whether the COVARIANCE the tracker reports is honest.  `nees_nodes` takes the estimation error of every node against the
+true state and its normalised square e' P^-1 e (NEES) -- over the position, over position and velocity and over the full state, from
+one factorisation (`mht_nees_nodes`, csrc/mht_nees.hip) -- which sees the unmeasured states the innovation tests of
+pymht_amd.smoothing.consistency cannot; `nees_consistency` runs the chi-square tests of the literature on the figures, on the host,
+and `Tracker.getNees` applies both to a tracker's filtered or smoothed histories under GOSPA's pairing."""
 import ctypes as C
 
 import numpy as np
@@ -334,3 +340,156 @@ def truth_trajectories(Y, truthIds=None):
                 XY[s, col[who]] = rows[s][r]
     on = ~(np.isnan(XY[:, :, 0]) & np.isnan(XY[:, :, 1]))
     return XY, on.astype(np.uint8)
+
+
+# ---- NEES: is the reported covariance honest? ------------------------------------------------------------------------------------------
+def _nees_launch(ctx, nx, n, L_max, D, x_d, P_d, truth, present):
+    """One `mht_nees_nodes` call on states that lie on the device in the seams' layouts (x_d [L_max, nx, n], P_d [L_max, ns, n] packed):
+    truth [L_max, nx, n] float64 and present [L_max, n] uint8 go up, out [L_max, nx + 3, n] comes down."""
+    dev, lib = ctx.device, ctx.lib
+    t_d = torch.from_numpy(np.ascontiguousarray(truth, dtype=np.float64)).to(dev)
+    p_d = torch.from_numpy(np.ascontiguousarray(present, dtype=np.uint8)).to(dev)
+    out_d = torch.empty((L_max, nx + 3, n), dtype=torch.float64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
+    _lib.check(lib.mht_nees_nodes(ctx.handle, nx, n, L_max, D, x_d.data_ptr(), P_d.data_ptr(), t_d.data_ptr(), p_d.data_ptr(), out_d.data_ptr()), lib)
+    return out_d.cpu().numpy()
+
+
+def _nees_dict(rows, nx):
+    """One track's dict from its rows [L, nx + 3] as the seam lays them out"""
+    return {"error": rows[:, :nx].copy(), "nees2": rows[:, nx].copy(), "nees4": rows[:, nx + 1].copy(), "nees": rows[:, nx + 2].copy()}
+
+
+def nees_nodes(x, P, truth, device=0, ctx=None):
+    """The estimation error and the normalised estimation error squared (NEES) of every node of a batch of tracks against ground truth.
+
+    x, P, truth   per track x [L, nx] (nx 4 or 6, the same for all), P [L, nx, nx] symmetric (the upper triangle is read) -- as
+                  `smoothing.filter_tracks` and `smoothing.smooth_tracks` return them -- and truth [L, D] with D one of 2, 4, nx, the
+                  same for all: the leading components [x, y, vx, vy, ...] of the true state at the node.  A NaN row of truth: the
+                  node has no truth (not scored)
+    device, ctx   the GPU ordinal, or an existing pymht_amd.device.Context (a Tracker's) to run on
+    ValueError for shapes that do not fit -- before any device is needed; an empty list gives an empty list.
+    Returns per track a dict of float64 arrays with a row per node:
+        error [L, nx]   x - truth on the leading D components, NaN beyond
+        nees2 [L]       the position error under the marginal position covariance, e' P_2^-1 e: chi-square, 2 degrees of freedom,
+                        when P is honest
+        nees4 [L]       position and velocity, 4 degrees of freedom (NaN if D < 4)
+        nees [L]        the full state, nx degrees of freedom (NaN if D < nx; nees4's figure at nx = 4)
+    From one Cholesky factorisation P = U' U per node: with U' y = e the sum of y_j^2 over j < d is the NEES of the leading d components,
+    exactly.  A node without truth, or whose x or P holds a NaN, is NaN throughout; a pivot j that is not positive gives NaN in every
+    figure that includes component j and leaves the figures in front of it.  One upload, one launch (`mht_nees_nodes`), no host
+    fallback.  `nees_consistency` runs the tests on the result."""
+    if not (len(x) == len(P) == len(truth)):
+        raise ValueError("nees: %d tracks of states, %d of covariances and %d of truth" % (len(x), len(P), len(truth)))
+    n = len(x)
+    if n == 0:
+        return []
+    X = [np.asarray(a, dtype=np.float64) for a in x]
+    nx = X[0].shape[1] if X[0].ndim == 2 else -1
+    if nx not in (4, 6):
+        raise ValueError("nees: the states are [L, 4] or [L, 6] arrays (track 0 has shape %r)" % (X[0].shape,))
+    Pm = [np.asarray(a, dtype=np.float64) for a in P]
+    T = [np.asarray(a, dtype=np.float64) for a in truth]
+    D = T[0].shape[1] if T[0].ndim == 2 else -1
+    if D not in (2, 4, nx):
+        raise ValueError("nees: the truth carries 2, 4 or nx = %d leading components of the state (track 0 has shape %r)" % (nx, T[0].shape))
+    for t in range(n):
+        L = len(X[t])
+        if X[t].shape != (L, nx) or Pm[t].shape != (L, nx, nx) or T[t].shape != (L, D) or L < 1:
+            raise ValueError("nees: track %d has shapes %r, %r and %r; [L, %d], [L, %d, %d] and [L, %d] with L >= 1 are wanted"
+                             % (t, X[t].shape, Pm[t].shape, T[t].shape, nx, nx, nx, D))
+    lens = np.array([len(a) for a in X])
+    L_max, ns = int(lens.max()), nx * (nx + 1) // 2
+    iu = np.triu_indices(nx)
+    xp, Pp = np.full((L_max, nx, n), np.nan), np.full((L_max, ns, n), np.nan)      # (rows behind a track's end: NaN, as the seams write them)
+    tp, pp = np.zeros((L_max, nx, n)), np.zeros((L_max, n), dtype=np.uint8)
+    for t in range(n):
+        L = lens[t]
+        there = ~np.isnan(T[t]).any(axis=1)
+        xp[:L, :, t], Pp[:L, :, t] = X[t], Pm[t][:, iu[0], iu[1]]
+        tp[:L, :D, t], pp[:L, t] = np.where(there[:, None], T[t], 0.0), there
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        up = lambda a: torch.from_numpy(a).to(ctx.device)
+        out = _nees_launch(ctx, nx, n, L_max, D, up(xp), up(Pp), tp, pp)
+    finally:
+        if own:
+            ctx.close()
+    return [_nees_dict(np.ascontiguousarray(out[:lens[t], :, t]), nx) for t in range(n)]
+
+
+def nees_consistency(results, alpha=0.05):
+    """The NEES tests of the tracking literature (Bar-Shalom, Li, Kirubarajan: Estimation with Applications to Tracking and Navigation,
+    ch. 5.4) on the dicts of `nees_nodes`, host only, float64.  A cell is a node with truth (a finite error[0]).  A result may carry
+    `step` [L] (int; negative: no step): the step of the run each node belongs to (`Tracker.getNees` fills it in); without it a node's
+    step is its row.  Returns a dict:
+        alpha, nCells
+        rmsPosition     sqrt of the mean of e_x^2 + e_y^2 over the cells;  rmsVelocity: of e_vx^2 + e_vy^2 over the cells that carry it
+        dims            {dof: figures} for dof in 2, 4, nx where the truth carries that many components, each a dict of
+          n               the cells
+          mean            the NEES summed over the cells, divided by dof n: 1 when the covariance is honest
+          interval        (lo, hi) = chi2.ppf([alpha/2, 1 - alpha/2], dof n) / (dof n)
+          inside          lo <= mean <= hi.  Above: the covariance is too small (optimistic), or the estimate is biased; below: too
+                          large (pessimistic)
+          outlierFraction the share of cells above chi2.ppf(1 - alpha, dof): alpha when the covariance is honest
+          perStep         {"step", "n", "mean", "lo", "hi", "inside"}: arrays over the steps that have a cell -- the same test per
+                          step, pooled over the step's tracks
+    The PER-STEP test is Bar-Shalom's test proper: the tracks of a step are independent, so the sum of their NEES is chi-square with
+    dof n degrees of freedom.  The POOLED figures add up all cells, and consecutive errors of one track are correlated (the filter's
+    error is a first-order process): the sum over a track is NOT chi-square with dof L degrees of freedom, its spread is wider, so the
+    pooled interval is approximate -- too narrow -- and is a summary, not a test of exact size.  A cell whose figure is NaN (a P that is
+    not positive definite) makes the means that include it NaN and their verdicts None, as a NaN nis does in smoothing.consistency;
+    without cells the figures are NaN and the verdicts None.  alpha outside (0, 1) raises ValueError."""
+    from scipy.stats import chi2
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not 0.0 < float(alpha) < 1.0:
+        raise ValueError("nees: alpha is a probability strictly between 0 and 1 (got %r)" % (alpha,))
+    alpha = float(alpha)
+    nan = float("nan")
+    err, figs, steps = [], {"nees2": [], "nees4": [], "nees": []}, []
+    nx = None
+    for r in results:
+        e = np.asarray(r["error"], dtype=np.float64)
+        if e.ndim != 2 or (nx is not None and e.shape[1] != nx):
+            raise ValueError("nees: the results do not have one state dimension")
+        nx = e.shape[1]
+        cell = np.isfinite(e[:, 0])
+        step = np.asarray(r["step"], dtype=np.int64) if "step" in r else np.arange(len(e), dtype=np.int64)
+        cell &= step >= 0
+        err.append(e[cell])
+        steps.append(step[cell])
+        for k in figs:
+            figs[k].append(np.asarray(r[k], dtype=np.float64)[cell])
+    out = {"alpha": alpha, "nCells": 0, "rmsPosition": nan, "rmsVelocity": nan, "dims": {}}
+    if nx is None:
+        return out
+    err, steps = np.concatenate(err), np.concatenate(steps)
+    out["nCells"] = int(len(err))
+    if len(err) == 0:
+        return out
+    out["rmsPosition"] = float(np.sqrt(np.mean(np.sum(err[:, 0:2] ** 2, axis=1))))
+    vel = np.isfinite(err[:, 3])
+    if vel.any():
+        out["rmsVelocity"] = float(np.sqrt(np.mean(np.sum(err[vel, 2:4] ** 2, axis=1))))
+    for dof, key in ((2, "nees2"), (4, "nees4"), (nx, "nees")):
+        carried = np.isfinite(err[:, dof - 1])      # (the truth of the cell carries dof components)
+        if dof in out["dims"] or not carried.any():
+            continue
+        q, st = np.concatenate(figs[key])[carried], steps[carried]
+        n = int(len(q))
+        lo, hi = (float(v) / (dof * n) for v in chi2.ppf([alpha / 2.0, 1.0 - alpha / 2.0], dof * n))
+        mean = float(np.sum(q)) / (dof * n)
+        fig = {"n": n, "mean": mean, "interval": (lo, hi), "inside": None, "outlierFraction": nan}
+        if np.isfinite(mean):
+            fig["inside"] = bool(lo <= mean <= hi)
+            fig["outlierFraction"] = float(np.sum(q > float(chi2.ppf(1.0 - alpha, dof)))) / n
+        which = np.unique(st)
+        cnt = np.array([int(np.sum(st == s)) for s in which], dtype=np.int64)
+        with np.errstate(invalid="ignore"):
+            m = np.array([np.sum(q[st == s]) for s in which], dtype=np.float64) / (dof * cnt)
+        slo, shi = chi2.ppf(alpha / 2.0, dof * cnt) / (dof * cnt), chi2.ppf(1.0 - alpha / 2.0, dof * cnt) / (dof * cnt)
+        fig["perStep"] = {"step": which, "n": cnt, "mean": m, "lo": slo, "hi": shi,
+                          "inside": np.array([None if not np.isfinite(v) else bool(a <= v <= b) for v, a, b in zip(m, slo, shi)], dtype=object)}
+        out["dims"][dof] = fig
+    return out

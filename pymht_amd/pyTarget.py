@@ -253,6 +253,27 @@ class Target:
         return smoothing.smooth_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
                                       constantTurn=constantTurn, ais=lookup, em=em, emStart=emStart)[0]
 
+    def getFilteredTrack(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False):
+        """(xf [L, nx], Pf [L, nx, nx]) of the chain that ends in this node: the filtered state and covariance of every node, which
+        getSmoothTrack's smoother computes on its way forward (pymht_amd.smoothing.filter_tracks defines them; node 0 is the chain's
+        initial state).  They are the float64 filter of the smoothers and scores, run over the history with the model from the chain's
+        initial state -- not the forest's own float32 / float64 chains bit for bit.  model, constantTurn and ais as for getSmoothTrack,
+        with the same refusals.  Many nodes at once: Tracker.getFilteredTracks()."""
+        from . import smoothing
+        tracker = getattr(self, "_tracker", None)
+        lookup = None
+        if ais:
+            if tracker is None:
+                raise ValueError("ais=True needs the node of an AIS-aided Tracker: the messages are in the tracker's history")
+            lookup = tracker._ais_lookup(constantTurn)
+        if model is None:
+            if tracker is not None:
+                model = tracker._model_mod
+            else:
+                from .models import pv as model
+        return smoothing.filter_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
+                                      constantTurn=constantTurn, ais=lookup)[0]
+
     def getTrackLikelihood(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False):
         """(logLikelihood, nis, nObs) of the chain that ends in this node under the model getSmoothTrack would smooth it with -- how well
         that model explains the chain's plots (pymht_amd.smoothing.score_tracks defines the figures; a chain of fewer than two nodes

@@ -36,7 +36,11 @@ matrices, `best_cell` picks the cell of the largest likelihood -- the pooled max
 The sums say whether a model fits a track; WHERE it stops fitting is in the sequence they add up: `trace_tracks`, `trace_tracks_ct`,
 `trace_tracks_ais` (and `trace_nodes`, `Tracker.getTrackInnovations`) run the score's walk and hand out per node the innovation, its
 covariance, the node's NIS and log-likelihood term (`mht_trace_tracks*`, one launch, 7 doubles per node and track, 16 more per AIS
-message); `consistency` runs the filter-consistency tests of the tracking literature on them, on the host."""
+message); `consistency` runs the filter-consistency tests of the tracking literature on them, on the host.
+
+The filtered state and covariance themselves, per node, are handed out by `filter_tracks`, `filter_tracks_ct`, `filter_tracks_ais` (and
+`filter_nodes`, `Tracker.getFilteredTracks`): the forward half of the smoother with its (xf, Pf) stored (`mht_filter_tracks*`, one
+launch) -- what `pymht_amd.evaluation.nees_nodes` holds against ground truth."""
 import ctypes as C
 
 import numpy as np
@@ -263,7 +267,9 @@ def _model_x(model, period, nx, constant_turn, identity_start=False):
     return _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 1 if constant_turn else 0, period), keep
 
 
-def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None, em=None, likelihoods=False):
+def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None, em=None, likelihoods=False, on_device=False):
+    """on_device=True (internal: Tracker.getNees): nothing is downloaded -- (xs_d [L_max, nx, n], Ps_d [L_max, ns, n], lens, order, L_max),
+    the seam's outputs where they lie, packed column j holding track order[j]."""
     n, ns = len(tracks), nx * (nx + 1) // 2
     identity_start = em is not None and em[1] == "reference"
     lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx, identity_start)
@@ -290,6 +296,8 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
                                   z_d.data_ptr(), h_d.data_ptr(), *extra, *(() if em is None else (em[0],)), xs_d.data_ptr(),
                                   Ps_d.data_ptr() if covariances else None, *(() if em is None else (Q_d.data_ptr(), R_d.data_ptr())),
                                   work.data_ptr(), need, *trace), lib)
+    if on_device:
+        return xs_d, Ps_d, lens, order, L_max
     xs = xs_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
     Ps = None
     if covariances:      # packed upper triangle -> full matrices, still on the device
@@ -488,6 +496,106 @@ def trace_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fals
             batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
             where.append(i)
     for i, res in zip(where, trace(model, radarPeriod, batch, device=device, ctx=ctx)):
+        out[i] = res
+    return out
+
+
+_FILTER_SEAMS = {"linear": "mht_filter_tracks", "ct": "mht_filter_tracks_ct", "ais": "mht_filter_tracks_ais"}
+
+
+def filter_tracks(model, radarPeriod, tracks, device=0, ctx=None):
+    """The filtered state and covariance of every node of a batch of track histories: per track (xf [L, nx], Pf [L, nx, nx]) float64.
+    `model` and `tracks` as for `smooth_tracks` (the same checks and refusals; an empty list gives an empty list).  Node 0 is
+    (x_init, P_init); node k >= 1 is predicted from node k - 1 and, with a plot, updated with it.
+
+    WHAT THESE COVARIANCES ARE: those of the float64 filter the smoothers and the scores run -- the tracker's model, A = Phi(T),
+    Q = Q(T), C_RADAR, R_RADAR(), over the history from the chain's initial state.  They are the forward half of `smooth_tracks` bit
+    for bit (a track's last row is the last row of its xs and Ps) and the states behind `score_tracks` and `trace_tracks`.  They are NOT
+    the forest's own chains bit for bit: the forest filters in float32 (float64 for AIS-fused covariances) with tabulated gains.
+    One device launch (`mht_filter_tracks`), no host fallback."""
+    return _filter_on(ctx, device, model, radarPeriod, tracks, _check_model(model), False)
+
+
+def filter_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None):
+    """`filter_tracks` under the constant-turn model `smooth_tracks_ct` smooths with (anything else raises ValueError): nx = 6,
+    A_k = Phi(T, w) at the filtered turn rate of the node in front, no Jacobian."""
+    return _filter_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), True)
+
+
+def filter_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None):
+    """`filter_tracks` under the AIS-aware model of `smooth_tracks_ais`, same `tracks` and refusals.  The state handed out for a node
+    that took a message is the one at the SCAN's time, behind both legs and the radar update; the state at the message's time is an
+    intermediate.  A batch without any message gives `filter_tracks`' numbers bit for bit."""
+    nx = _check_ais_model(model)
+    ais = _ais_inputs(model, tracks)
+    return _filter_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, False, ais=ais)
+
+
+def _filter_on(ctx, device, model, radarPeriod, tracks, nx, constant_turn, ais=None):
+    if len(tracks) == 0:
+        return []
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        return _filter(ctx, model, float(radarPeriod), tracks, nx, constant_turn, ais)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _unpack_index(nx, dev):
+    """Per entry (i, j) of a full nx x nx matrix, row-major, its place in the packed upper triangle (sym_idx, csrc/mht_smooth_math.h)"""
+    return torch.tensor([min(i, j) * nx - min(i, j) * (min(i, j) - 1) // 2 + abs(i - j) for i in range(nx) for j in range(nx)], device=dev)
+
+
+def _filter(ctx, model, period, tracks, nx, constant_turn, ais=None, on_device=False):
+    """on_device=True (internal: Tracker.getNees): nothing is downloaded -- (xf_d [L_max, nx, n], Pf_d [L_max, ns, n], lens, order, L_max),
+    the seam's outputs where they lie, packed column j holding track order[j]."""
+    n, ns = len(tracks), nx * (nx + 1) // 2
+    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
+    dev, lib, extra = ctx.device, ctx.lib, ()
+    xf_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
+    Pf_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev)
+    if ais is not None:
+        extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
+    need = int(lib.mht_filter_work_bytes(nx, n, L_max))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mx, keep = _model_x(model, period, nx, constant_turn)
+    lens_sorted = np.ascontiguousarray(lens[order])
+    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
+    seam = _FILTER_SEAMS["ais" if ais is not None else "ct" if constant_turn else "linear"]
+    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
+                                  z_d.data_ptr(), h_d.data_ptr(), *extra, xf_d.data_ptr(), Pf_d.data_ptr(), work.data_ptr(), need), lib)
+    if on_device:
+        return xf_d, Pf_d, lens, order, L_max
+    xf = xf_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
+    Pf = Pf_d.index_select(1, _unpack_index(nx, dev)).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
+    out = [None] * n
+    for j, t in enumerate(order):
+        L = int(lens[t])
+        out[t] = (xf[j, :L], Pf[j, :L])
+    return out
+
+
+def filter_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None):
+    """`filter_tracks` for many track nodes in one device call, built on `chain_inputs` / `chain_ais` like `trace_nodes` (the same
+    switches and refusals): per node (xf [L, nx], Pf [L, nx, nx]) of its chain -- the float64 filter of the smoothers and scores, run
+    over the history with `model` from the chain's initial state, not the forest's float32 / float64 chains bit for bit.  A chain of
+    fewer than two nodes was never filtered: its initial state and covariance, and no device is needed to say so."""
+    if ais is not None and constantTurn:
+        raise ValueError("smoothing: AIS-aware filtering is for 4-state linear models, not together with constantTurn")
+    run = filter_tracks_ais if ais is not None else filter_tracks_ct if constantTurn else filter_tracks
+    nx = (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
+    out, batch, where = [None] * len(nodes), [], []
+    for i, node in enumerate(nodes):
+        chain, inputs = chain_inputs(node, model.P0)
+        if len(chain) < 2:
+            out[i] = (inputs[0].reshape(1, nx).copy(), inputs[1].reshape(1, nx, nx).copy())
+        else:
+            batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
+            where.append(i)
+    for i, res in zip(where, run(model, radarPeriod, batch, device=device, ctx=ctx)):
         out[i] = res
     return out
 

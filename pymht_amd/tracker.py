@@ -1016,6 +1016,20 @@ class Tracker():
             nodes += list(self.__terminatedTargets__)
         return self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais, em=em, emStart=emStart)
 
+    def getFilteredTracks(self, terminated=False, constantTurn=False, ais=False):
+        """The filtered state and covariance along every track history: (xf [L, nx], Pf [L, nx, nx]) per live track, in the order of
+        getSmoothTracks, with terminated=True followed by the terminated ones -- ONE forward-only device call
+        (smoothing.filter_nodes / filter_tracks).  These are the states of the float64 filter the smoothers and the scores run: the
+        tracker's model over the history from the chain's initial state -- the forward half of getSmoothTracks bit for bit, and NOT
+        the forest's own float32 / float64 chains bit for bit (a node's P_0 keeps returning the forest's covariance while the node
+        is in the ring, and None afterwards).  constantTurn and ais as for getSmoothTracks, with the same refusals."""
+        from . import smoothing
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        return smoothing.filter_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
+                                      ais=self._ais_lookup(constantTurn) if ais else None)
+
     def getTrackLikelihoods(self, terminated=False, constantTurn=False, ais=False):
         """How well the tracker's model explains each track's plots: (logLikelihood, nis, nObs) per live track, in the order of
         getSmoothTracks, with terminated=True followed by the terminated ones -- scored in ONE forward-only device call
@@ -1051,6 +1065,29 @@ class Tracker():
         from . import smoothing
         return smoothing.consistency(self.getTrackInnovations(terminated=terminated, constantTurn=constantTurn, ais=ais), alpha=alpha)
 
+    def _step_estimates(self, nodes, times, smooth, constantTurn, ais):
+        """The estimates getGospa and getNees hold against the truth of each step: (X, ids, nIgnored, where) -- per step the positions
+        [k, 2] of the nodes with that time stamp on the histories of `nodes` (the forest's filtered positions, or getSmoothTracks'
+        with smooth), their track IDs, the nodes at no step's time, and per step the (history, node) indices of the estimates."""
+        smoothed = self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais) if smooth else None
+        step_of = {}
+        for s, t in enumerate(times):
+            step_of.setdefault(float(t), s)
+        X, ids, where, nIgnored = [[] for _ in times], [[] for _ in times], [[] for _ in times], 0
+        for i, leaf in enumerate(nodes):
+            chain = leaf.backtrackNodes()
+            tid = leaf.ID if leaf.ID is not None else chain[0].ID if chain[0].ID is not None else -(i + 1)
+            for k, node in enumerate(chain):
+                s = step_of.get(float(node.time))
+                if s is None:
+                    nIgnored += 1
+                    continue
+                pos = smoothed[i][0][k] if smooth and len(chain) >= 2 else node.x_0[0:2]      # (a chain of one node has nothing to smooth)
+                X[s].append(np.asarray(pos, dtype=np.float64).reshape(2))
+                ids[s].append(tid)
+                where[s].append((i, k))
+        return [np.array(x, dtype=np.float64).reshape(-1, 2) for x in X], ids, nIgnored, where
+
     def getGospa(self, truth, c, p=2, terminated=True, smooth=False, constantTurn=False, ais=False):
         """The track histories scored against ground truth: GOSPA per step (evaluation.gospa_steps, which defines the figures; one
         device launch for all steps), the one figure here that says whether the tracker FOUND the targets -- missed targets, false
@@ -1080,27 +1117,104 @@ class Tracker():
         nodes = list(self.__trackNodes__)
         if terminated:
             nodes += list(self.__terminatedTargets__)
-        smoothed = self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais) if smooth else None
-        step_of = {}
-        for s, t in enumerate(times):
-            step_of.setdefault(float(t), s)
-        X, ids, nIgnored = [[] for _ in times], [[] for _ in times], 0
-        for i, leaf in enumerate(nodes):
-            chain = leaf.backtrackNodes()
-            tid = leaf.ID if leaf.ID is not None else chain[0].ID if chain[0].ID is not None else -(i + 1)
-            for k, node in enumerate(chain):
-                s = step_of.get(float(node.time))
-                if s is None:
-                    nIgnored += 1
-                    continue
-                pos = smoothed[i][0][k] if smooth and len(chain) >= 2 else node.x_0[0:2]      # (a chain of one node has nothing to smooth)
-                X[s].append(np.asarray(pos, dtype=np.float64).reshape(2))
-                ids[s].append(tid)
-        out = evaluation.gospa_steps([np.array(x, dtype=np.float64).reshape(-1, 2) for x in X], Y, c, p, ctx=self._ctx)
+        X, ids, nIgnored, _ = self._step_estimates(nodes, times, smooth, constantTurn, ais)
+        out = evaluation.gospa_steps(X, Y, c, p, ctx=self._ctx)
         out["times"], out["trackIds"], out["nIgnored"] = times, ids, nIgnored
         out["idSwitches"] = evaluation.id_switches(out["match"], ids)
         for key, name in (("gospa", "meanGospa"), ("localisation", "meanLocalisation"), ("missed", "meanMissed"), ("false", "meanFalse")):
             out[name] = float(np.mean(out[key])) if len(times) else float("nan")
+        return out
+
+    def getNees(self, truth, c, dims=None, smooth=False, constantTurn=False, ais=False, terminated=True, alpha=0.05):
+        """Is the covariance the tracker reports honest?  The estimation error of the track histories against the true STATES and its
+        normalised square (NEES) per node, and the chi-square tests on it (evaluation.nees_nodes and nees_consistency define the
+        figures) -- the test that sees a velocity bias or a P too small in the unmeasured states, which getConsistency's innovation
+        tests, on the two measured coordinates, pass.
+
+        truth   getGospa's two forms; here the columns beyond the first two are read as well: a truth row is the leading components
+                [x, y, vx, vy, ...] of the true state, e.g. (sc["times"], sc["truth"]) of utils/scenario.make_scenario ([T, 4] per step)
+        c       the cut-off of the pairing: a node is scored against the truth GOSPA (p = 2) assigns it at its step, evaluation.gospa_steps
+                on getGospa's own estimates -- the forest's filtered positions, or getSmoothTracks' with smooth=True.  Every other
+                node has no truth and is not scored
+        dims    2, 4 or the model's state dimension: the components scored.  None: the largest of them every step's truth carries.
+                ValueError if a step's truth has fewer columns
+        smooth  False: the states scored are getFilteredTracks' (xf, Pf) -- the float64 filter of the smoothers and scores run over
+                the history, not the forest's own chains bit for bit.  True: the smoothed (xs, Ps) of smoothing.smooth_tracks*, whose
+                covariances nothing else checks; constantTurn and ais select the smoother and carry getSmoothTracks' refusals
+                (without smooth=True they are refused: ValueError)
+        alpha   the size of nees_consistency's tests
+
+        SELECTION: only pairs closer than c are scored, so a small c cuts the tail off the errors and biases the NEES LOW -- a filter
+        looks more honest, or more pessimistic, than it is.  Choose c several standard deviations of the position error wide; then
+        the pairs lost are the tracker's misses (getGospa counts them), not the error's tail.
+
+        THESE ARE THE HISTORIES AS THEY STAND AT THE CALL: resolved by the N-scan window, every track one chain.  They are not the
+        estimates the tracker reported online at each scan, which a hypothesis pruned since may have produced.
+
+        The filter's (smoother's) outputs stay on the device: only the truth goes up and the figures come down (one mht_nees_nodes
+        launch behind the filter's or smoother's one; with smooth=True the pairing runs getSmoothTracks' means-only smoother first).
+        Returns a dict: tracks (per history, in getGospa's order, nees_nodes' dict plus step [L], the step of each node or -1),
+        trackIds, consistency (nees_consistency's dict), dims, times, nAssigned (the nodes scored), nUnassigned (nodes at a step's
+        time that GOSPA left unassigned) and nIgnored (nodes at no step's time)."""
+        from . import evaluation, smoothing
+        if (constantTurn or ais) and not smooth:
+            raise ValueError("getNees: constantTurn and ais select the smoother of smooth=True; the filtered states need neither")
+        c, _ = evaluation._check_cutoff(c, 2)
+        times, Y = evaluation.truth_steps(truth)
+        model = self._model_mod
+        nx = int(np.asarray(model.C_RADAR).shape[1])
+        Y = [np.asarray(y, dtype=np.float64).reshape(-1, np.shape(y)[1] if np.ndim(y) == 2 else 2) for y in Y]
+        cols = min([y.shape[1] for y in Y if len(y)], default=nx)
+        allowed = sorted({2, 4, nx})
+        if dims is None:
+            dims = max([d for d in allowed if d <= cols], default=None)
+        if isinstance(dims, bool) or dims not in allowed:
+            raise ValueError("getNees: dims is one of %r, the components of the state the truth is held against (got %r)" % (allowed, dims))
+        if cols < dims:
+            raise ValueError("getNees: dims = %d, and the truth of some step has only %d columns" % (dims, cols))
+        dims = int(dims)
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        lookup = self._ais_lookup(constantTurn) if ais else None
+        X, ids, nIgnored, where = self._step_estimates(nodes, times, smooth, constantTurn, ais)
+        match = evaluation.gospa_steps(X, Y, c, 2, ctx=self._ctx)["match"]
+        chains = [smoothing.chain_inputs(node, model.P0) for node in nodes]
+        trackIds = [leaf.ID if leaf.ID is not None else ch[0].ID if ch[0].ID is not None else -(i + 1) for i, (leaf, (ch, _)) in enumerate(zip(nodes, chains))]
+        out = {"tracks": [], "trackIds": trackIds, "dims": dims, "times": times, "nAssigned": 0, "nUnassigned": 0, "nIgnored": nIgnored}
+        if nodes:
+            batch = [inp if lookup is None else inp + (smoothing.chain_ais(ch, lookup),) for ch, inp in chains]
+            if lookup is not None:
+                nx = smoothing._check_ais_model(model)
+                extra = dict(ais=smoothing._ais_inputs(model, batch))
+                batch = [t[:3] for t in batch]
+            else:
+                nx = (smoothing._check_ct_model if constantTurn else smoothing._check_model)(model)
+                extra = {}
+            period = float(self.radarPeriod)
+            if smooth:
+                x_d, P_d, lens, order, L_max = smoothing._smooth(self._ctx, model, period, batch, nx, True, constantTurn, on_device=True, **extra)
+            else:
+                x_d, P_d, lens, order, L_max = smoothing._filter(self._ctx, model, period, batch, nx, False, on_device=True)
+            n = len(nodes)
+            back = np.empty(n, dtype=np.int64)      # history i sits in packed column back[i]
+            back[order] = np.arange(n)
+            tp, pp = np.zeros((L_max, nx, n)), np.zeros((L_max, n), dtype=np.uint8)
+            steps = [np.full(int(L), -1, dtype=np.int64) for L in lens]
+            for s, (mt, wh) in enumerate(zip(match, where)):
+                for e, (i, k) in enumerate(wh):
+                    steps[i][k] = s
+                    if mt[e] >= 0:
+                        tp[k, :dims, back[i]], pp[k, back[i]] = Y[s][int(mt[e]), :dims], 1
+                        out["nAssigned"] += 1
+                    else:
+                        out["nUnassigned"] += 1
+            rows = evaluation._nees_launch(self._ctx, nx, n, L_max, dims, x_d, P_d, tp, pp)
+            for i in range(n):
+                d = evaluation._nees_dict(np.ascontiguousarray(rows[:lens[i], :, back[i]]), nx)
+                d["step"] = steps[i]
+                out["tracks"].append(d)
+        out["consistency"] = evaluation.nees_consistency(out["tracks"], alpha=alpha)
         return out
 
     def getOspa2(self, truth, c, p=2, window=None, every=1, terminated=True, smooth=False, constantTurn=False, ais=False, truthIds=None):
