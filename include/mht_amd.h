@@ -415,6 +415,46 @@ int mht_filter_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_trac
                           const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
                           double* xf, double* Pf, void* work, size_t work_bytes);
 
+/* mht_imm_tracks, mht_imm_tracks_ct: an INTERACTING-MULTIPLE-MODEL filter (Blom and Bar-Shalom 1988) over a batch of track histories.
+ * The float64 filter of mht_filter_tracks / mht_filter_tracks_ct is run under n_modes noise levels at once, mixed through a Markov
+ * chain over the modes; per node it hands out the posterior probability of every mode -- a manoeuvre detector per track and scan --
+ * and one combined state and covariance in the layout of mht_filter_tracks (what mht_nees_nodes takes), per track the log-likelihood
+ * of its plots under the mixture, comparable with mht_score_tracks' figure.  The batch (len .. has_z) and the model checks are
+ * mht_filter_tracks' and mht_filter_tracks_ct's; the model's own Q and R are not read.
+ *   n_modes  1 .. 4
+ *   Q        host [n_modes][nx][nx] f64, R host [n_modes][2][2] f64: mode j's noise (the upper triangles are read)
+ *   Pi       host [n_modes][n_modes] f64: Pi[i][j] = P(mode j at node k | mode i at node k - 1); entries in [0, 1] (zeros are legal),
+ *            every row adding up to 1 within 1e-9
+ *   mu0      host [n_modes] f64: the probabilities at node 0, in [0, 1], adding up to 1 within 1e-9
+ *   mu       dev [L_max][n_modes][n_tracks] f64 out;  x dev [L_max][nx][n_tracks] f64 out;  P dev [L_max][nx (nx + 1) / 2][n_tracks] f64
+ *            out, the upper triangle row by row;  ll dev [n_tracks] f64 out;  nobs dev [n_tracks] int32 out
+ * Node 0: every mode holds (x_init, P_init), mu = mu0, (x, P) = (x_init, P_init).  Node k >= 1, sums over i ascending:
+ *   cbar_j = sum_i Pi[i][j] mu_i;  where cbar_j > 0 mode j starts from the mixture w_ij = Pi[i][j] mu_i / cbar_j of the modes' states,
+ *   x0_j = sum_i w_ij x_i, P0_j = sum_i w_ij (P_i + (x_i - x0_j)(x_i - x0_j)'), else from its own;  it advances under Q_j (constant turn:
+ *   Phi(T, w) at x0_j[4]) and, with a plot, updates under R_j with lam_j = ln N(z; C xp_j, S_j), mht_score_tracks' term;  then
+ *   m = max_j lam_j, u_j = cbar_j exp(lam_j - m), s = sum_j u_j, mu_j = u_j / s, ll += m + ln s, nobs += 1 -- without a plot mu_j = cbar_j;
+ *   x = sum_j mu_j x_j, P = sum_j mu_j (P_j + (x_j - x)(x_j - x)').
+ * With n_modes == 1 (Pi = [[1]]) x and P are mht_filter_tracks' bits and ll, nobs are mht_score_tracks'.  A track of one node, or one
+ * never detected, gives exactly ll = 0.0 and nobs = 0.  A mode whose det S is not positive at some plot makes that track's ll NaN and its
+ * rows from that node on unspecified; no other track is touched.  The rows len[t] <= k < L_max behind a track's end are written with a
+ * quiet NaN: the arrays need not be initialised.
+ *   work dev, work_bytes >= mht_imm_work_bytes(nx, n_tracks, L_max, n_modes) (the lengths, the modes, Pi, mu0; 0 for a bad nx or
+ *        n_modes, a negative size or an empty batch): MHT_E_INVALID if it is smaller.
+ * One launch, one (track, mode) per lane -- the four lanes of a quad are the modes of a track and read each other's registers; no
+ * track's figures depend on its place in the batch.  Synchronises.  On MHT_E_INVALID (a null array, n_modes outside 1 .. 4, a length
+ * outside 1 .. L_max, a short workspace, the wrong nx or transition, an entry of Pi or mu0 outside [0, 1], a sum that is not 1) nothing
+ * has been launched or written; n_tracks == 0 returns MHT_OK and writes nothing.  The AIS-aware model is not run under an IMM (out of
+ * scope: its per-node message arrays are not taken).  Exported by both builds (nx at run time). */
+size_t mht_imm_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max, int32_t n_modes);
+int mht_imm_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len, const double* x_init,
+                   const double* P_init, const double* z, const uint8_t* has_z, int32_t n_modes, const double* Q, const double* R,
+                   const double* Pi, const double* mu0, double* mu, double* x, double* P, double* ll, int32_t* nobs, void* work,
+                   size_t work_bytes);
+int mht_imm_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len, const double* x_init,
+                      const double* P_init, const double* z, const uint8_t* has_z, int32_t n_modes, const double* Q, const double* R,
+                      const double* Pi, const double* mu0, double* mu, double* x, double* P, double* ll, int32_t* nobs, void* work,
+                      size_t work_bytes);
+
 /* mht_nees_nodes: is the covariance a filter reports honest?  The estimation error e = x - truth and the normalised estimation error
  * squared e' P^-1 e of every node of a batch against ground truth -- the test that sees the unmeasured states, which the innovations
  * (mht_trace_tracks*) do not.  The inputs lie where mht_filter_tracks* (xf, Pf) or mht_smooth_tracks* (xs, Ps) wrote them:

@@ -274,6 +274,25 @@ class Target:
         return smoothing.filter_nodes(model, radarPeriod, [self], device=device, ctx=None if tracker is None else tracker._ctx,
                                       constantTurn=constantTurn, ais=lookup)[0]
 
+    def getModeProbabilities(self, radarPeriod, model=None, device=0, qScales=(1.0, 16.0), stay=0.95, constantTurn=False):
+        """A dict mu [L, r], x [L, nx], P [L, nx, nx], logLikelihood, nObs of the chain that ends in this node under an
+        interacting-multiple-model filter with one mode per entry of qScales (pymht_amd.smoothing.imm_modes makes the modes,
+        imm_tracks defines the figures; the default scales are a starting point, not tuned; a chain of fewer than two nodes gives mu0
+        and its initial state).  model and constantTurn as for getFilteredTrack, with the same refusals.  Many nodes at once:
+        Tracker.getModeProbabilities()."""
+        from . import smoothing
+        tracker = getattr(self, "_tracker", None)
+        if model is None:
+            if tracker is not None:
+                model = tracker._model_mod
+            else:
+                from .models import pv as model
+        (smoothing._check_ct_model if constantTurn else smoothing._check_model)(model)
+        Q, R, Pi, mu0 = smoothing.imm_modes(model, radarPeriod, qScales, stay=stay)
+        per, ll, nobs = smoothing.imm_nodes(model, radarPeriod, [self], Q, R, Pi, mu0, device=device,
+                                            ctx=None if tracker is None else tracker._ctx, constantTurn=constantTurn)
+        return dict(mu=per[0][0], x=per[0][1], P=per[0][2], logLikelihood=float(ll[0]), nObs=int(nobs[0]))
+
     def getTrackLikelihood(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False):
         """(logLikelihood, nis, nObs) of the chain that ends in this node under the model getSmoothTrack would smooth it with -- how well
         that model explains the chain's plots (pymht_amd.smoothing.score_tracks defines the figures; a chain of fewer than two nodes

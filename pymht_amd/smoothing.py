@@ -40,7 +40,13 @@ message); `consistency` runs the filter-consistency tests of the tracking litera
 
 The filtered state and covariance themselves, per node, are handed out by `filter_tracks`, `filter_tracks_ct`, `filter_tracks_ais` (and
 `filter_nodes`, `Tracker.getFilteredTracks`): the forward half of the smoother with its (xf, Pf) stored (`mht_filter_tracks*`, one
-launch) -- what `pymht_amd.evaluation.nees_nodes` holds against ground truth."""
+launch) -- what `pymht_amd.evaluation.nees_nodes` holds against ground truth.
+
+One noise level rarely fits a whole track: a ship steams straight, turns for a few scans and steams on.  `imm_tracks`, `imm_tracks_ct`
+(and `imm_nodes`, `Tracker.getModeProbabilities`) run an interacting-multiple-model filter over the histories -- the same state under up
+to four (Q, R), mixed through a Markov chain over the modes (`mht_imm_tracks*`, one launch, one (track, mode) per lane) -- and hand out
+per node the probability of every mode and one combined state and covariance in `filter_tracks`' layout, per track the log-likelihood
+under the mixture, comparable with `score_tracks`'; `imm_modes` makes the modes of scalings of the model's own noise."""
 import ctypes as C
 
 import numpy as np
@@ -598,6 +604,138 @@ def filter_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fal
     for i, res in zip(where, run(model, radarPeriod, batch, device=device, ctx=ctx)):
         out[i] = res
     return out
+
+
+IMM_MAX_MODES = 4      # (IMM_MAX_MODES of csrc/mht_imm.h)
+
+
+def imm_modes(model, radarPeriod, qScales, rScales=None, stay=0.95):
+    """The modes of an interacting-multiple-model filter over scalings of the model's own noise: (Q [r, nx, nx], R [r, 2, 2], Pi [r, r],
+    mu0 [r]) float64, one mode per entry of qScales (1 .. 4 of them), mode j being qScales[j] * Q32 and rScales[j] * R32 as `noise_grid`
+    makes candidates (the float32 matrices every seam is handed, times float64 scales; rScales defaults to all ones and has qScales'
+    length otherwise).  Pi has `stay` on the diagonal and (1 - stay) / (r - 1) elsewhere ([[1.]] for one mode), mu0 is uniform.  Scales
+    that are not finite and positive, too many of them, or a `stay` outside (0, 1] raise ValueError."""
+    q = np.asarray(qScales, dtype=np.float64).reshape(-1)
+    r = np.ones_like(q) if rScales is None else np.asarray(rScales, dtype=np.float64).reshape(-1)
+    for name, sc in (("qScales", q), ("rScales", r)):
+        if sc.size == 0 or not (np.isfinite(sc).all() and (sc > 0).all()):
+            raise ValueError("smoothing: %s are finite positive factors, at least one (got %r)" % (name, sc.tolist()))
+    if len(q) > IMM_MAX_MODES or len(r) != len(q):
+        raise ValueError("smoothing: 1 .. %d modes, a scale of Q and of R each (got %d and %d)" % (IMM_MAX_MODES, len(q), len(r)))
+    if isinstance(stay, bool) or not isinstance(stay, (int, float, np.integer, np.floating)) or not 0.0 < float(stay) <= 1.0:
+        raise ValueError("smoothing: stay is the probability of keeping a mode, in (0, 1] (got %r)" % (stay,))
+    nx, n = int(np.asarray(model.C_RADAR).shape[1]), len(q)
+    Q32 = np.asarray(model.Q(float(radarPeriod)), dtype=np.float32).astype(np.float64).reshape(nx, nx)
+    R32 = np.asarray(model.R_RADAR(), dtype=np.float32).astype(np.float64).reshape(2, 2)
+    Pi = np.ones((1, 1)) if n == 1 else np.where(np.eye(n, dtype=bool), float(stay), (1.0 - float(stay)) / (n - 1))
+    return q[:, None, None] * Q32, r[:, None, None] * R32, Pi, np.full(n, 1.0 / n)
+
+
+def _check_modes(Q, R, Pi, mu0, nx):
+    """(Q [r, nx, nx], R [r, 2, 2], Pi [r, r], mu0 [r]) float64 C-contiguous, or ValueError: `_check_candidates`' checks capped at four
+    modes, and Pi's rows and mu0 distributions over them (the seam's own check, made before a device is needed)"""
+    Q, R = _check_candidates(Q, R, nx)
+    r = len(Q)
+    if r > IMM_MAX_MODES:
+        raise ValueError("smoothing: 1 .. %d modes a call (got %d)" % (IMM_MAX_MODES, r))
+    Pi = np.ascontiguousarray(Pi, dtype=np.float64)
+    mu0 = np.full(r, 1.0 / r) if mu0 is None else np.ascontiguousarray(mu0, dtype=np.float64)
+    if Pi.shape != (r, r) or mu0.shape != (r,):
+        raise ValueError("smoothing: Pi is [%d, %d] and mu0 [%d] for %d modes (got %r and %r)" % (r, r, r, r, Pi.shape, mu0.shape))
+    for name, p in (("Pi", Pi), ("mu0", mu0[None, :])):
+        if not ((p >= 0.0) & (p <= 1.0)).all() or not (np.abs(p.sum(axis=1) - 1.0) <= 1e-9).all():
+            raise ValueError("smoothing: %s holds probabilities, every row adding up to 1 (got %r)" % (name, p.tolist()))
+    return Q, R, Pi, mu0
+
+
+def imm_tracks(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, ctx=None):
+    """An interacting-multiple-model filter (Blom and Bar-Shalom 1988) over a batch of track histories: `filter_tracks`' float64 filter
+    run under r <= 4 noise levels at once, mode j carrying Q[j] [nx, nx] and R[j] [2, 2] in place of the model's Q(T) and R_RADAR()
+    (float64, symmetric; `imm_modes` makes scalings of the model's own), mixed through the Markov chain Pi [r, r] --
+    Pi[i, j] = P(mode j at node k | mode i at node k - 1), rows adding up to 1, zeros allowed -- from the probabilities mu0 [r] at node 0
+    (uniform by default).  `model` and `tracks` as for `filter_tracks`, with its checks and refusals; bad modes raise ValueError.
+    Returns (per track (mu [L, r], x [L, nx], P [L, nx, nx]), ll [n], nObs [n]) in the order of `tracks`: per node the posterior
+    probability of every mode -- a manoeuvre detector per track and scan -- and the combined state and covariance, in `filter_tracks`'
+    layout (what `evaluation.nees_nodes` takes); per track the log-likelihood of its plots under the mixture, comparable with
+    `score_tracks`' figure under one model, and their number.  Node 0 is (mu0, x_init, P_init).  With one mode (Pi = [[1.]]) x and P are
+    `filter_tracks`' bits and ll, nObs `score_tracks`'.  A mode that is no covariance (det S not positive at some plot) makes that
+    track's ll NaN, and no other's.  An empty list gives ([], shape (0,), shape (0,)).  One device launch (`mht_imm_tracks`), one
+    (track, mode) per lane, no host fallback."""
+    return _imm_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_model(model), False)
+
+
+def imm_tracks_ct(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, ctx=None):
+    """`imm_tracks` under the constant-turn model `filter_tracks_ct` filters with (anything else raises ValueError): nx = 6, every mode's
+    Phi(T, w) taken at the turn rate of its own mixed state."""
+    return _imm_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_ct_model(model), True)
+
+
+def _imm_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, nx, constant_turn):
+    Q, R, Pi, mu0 = _check_modes(Q, R, Pi, mu0, nx)
+    if len(tracks) == 0:
+        return [], np.zeros(0), np.zeros(0, dtype=np.int32)
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        return _imm(ctx, model, float(radarPeriod), tracks, Q, R, Pi, mu0, nx, constant_turn)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _imm(ctx, model, period, tracks, Q, R, Pi, mu0, nx, constant_turn):
+    n, r, ns = len(tracks), len(Q), nx * (nx + 1) // 2
+    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
+    dev, lib = ctx.device, ctx.lib
+    mu_d = torch.empty((L_max, r, n), dtype=torch.float64, device=dev)
+    xo_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
+    Po_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev)
+    ll_d = torch.empty(n, dtype=torch.float64, device=dev)
+    nobs_d = torch.empty(n, dtype=torch.int32, device=dev)
+    need = int(lib.mht_imm_work_bytes(nx, n, L_max, r))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mx, keep = _model_x(model, period, nx, constant_turn)
+    lens_sorted = np.ascontiguousarray(lens[order])
+    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
+    seam = lib.mht_imm_tracks_ct if constant_turn else lib.mht_imm_tracks
+    hostp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, hostp(lens_sorted), x_d.data_ptr(), P_d.data_ptr(), z_d.data_ptr(), h_d.data_ptr(), r,
+                    hostp(Q), hostp(R), hostp(Pi), hostp(mu0), mu_d.data_ptr(), xo_d.data_ptr(), Po_d.data_ptr(), ll_d.data_ptr(),
+                    nobs_d.data_ptr(), work.data_ptr(), need), lib)
+    mu = mu_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][mode]
+    xo = xo_d.permute(2, 0, 1).contiguous().cpu().numpy()
+    Po = Po_d.index_select(1, _unpack_index(nx, dev)).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
+    out = [None] * n
+    for j, t in enumerate(order):
+        L = int(lens[t])
+        out[t] = (mu[j, :L], xo[j, :L], Po[j, :L])
+    back = np.empty(n, dtype=np.int64)      # the callers' track t sits in packed column back[t]
+    back[order] = np.arange(n)
+    return out, ll_d.cpu().numpy()[back], nobs_d.cpu().numpy()[back]
+
+
+def imm_nodes(model, radarPeriod, nodes, Q, R, Pi, mu0=None, device=0, ctx=None, constantTurn=False):
+    """`imm_tracks` for many track nodes in one device call, built on `chain_inputs` like `filter_nodes`: (per node (mu [L, r], x [L, nx],
+    P [L, nx, nx]) of its chain, ll [n], nObs [n]).  A chain of fewer than two nodes was never filtered: mu0, its initial state and
+    covariance, ll = 0.0, nObs = 0, and no device is needed to say so.  constantTurn as for `filter_nodes`; the messages of an AIS-aided
+    tracker are not taken (there is no AIS-aware IMM)."""
+    run = imm_tracks_ct if constantTurn else imm_tracks
+    nx = (_check_ct_model if constantTurn else _check_model)(model)
+    Q, R, Pi, mu0 = _check_modes(Q, R, Pi, mu0, nx)
+    out, batch, where = [None] * len(nodes), [], []
+    ll, nobs = np.zeros(len(nodes)), np.zeros(len(nodes), dtype=np.int32)
+    for i, node in enumerate(nodes):
+        chain, inputs = chain_inputs(node, model.P0)
+        if len(chain) < 2:
+            out[i] = (mu0.reshape(1, -1).copy(), inputs[0].reshape(1, nx).copy(), inputs[1].reshape(1, nx, nx).copy())
+        else:
+            batch.append(inputs)
+            where.append(i)
+    res, ll[where], nobs[where] = run(model, radarPeriod, batch, Q, R, Pi, mu0, device=device, ctx=ctx)
+    for i, one in zip(where, res):
+        out[i] = one
+    return out, ll, nobs
 
 
 def consistency(traces, alpha=0.05):

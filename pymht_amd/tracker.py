@@ -1030,6 +1030,26 @@ class Tracker():
         return smoothing.filter_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
                                       ais=self._ais_lookup(constantTurn) if ais else None)
 
+    def getModeProbabilities(self, qScales=(1.0, 16.0), stay=0.95, terminated=False, constantTurn=False):
+        """WHERE along each track a louder model takes over: an interacting-multiple-model filter over every track history, one mode per
+        entry of qScales (up to four; mode j runs the tracker's model with qScales[j] times its Q, the chain between the modes keeps
+        a mode with probability `stay`: smoothing.imm_modes), in ONE device call (smoothing.imm_nodes / imm_tracks, which define the
+        figures).  One dict per live track, in the order of getSmoothTracks, with terminated=True followed by the terminated ones:
+        mu [L, r] the probability of every mode at every node -- a manoeuvre detector per track and scan --, x [L, nx] and P [L, nx, nx]
+        the combined state and covariance in getFilteredTracks' layout, logLikelihood and nObs as getTrackLikelihoods defines them,
+        under the mixture.  With qScales=(1.0,) they are getFilteredTracks' and getTrackLikelihoods' figures bit for bit.  The default
+        scales are a starting point, NOT tuned: getLikelihoodSurface says which single level fits, and a second level several times
+        louder is what a turn needs.  The refusals are getFilteredTracks': a constant-turn tracker raises NotImplementedError without
+        constantTurn=True, which raises ValueError for a tracker on a linear model; AIS messages are not taken."""
+        from . import smoothing
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        (smoothing._check_ct_model if constantTurn else smoothing._check_model)(self._model_mod)
+        Q, R, Pi, mu0 = smoothing.imm_modes(self._model_mod, self.radarPeriod, qScales, stay=stay)
+        per, ll, nobs = smoothing.imm_nodes(self._model_mod, self.radarPeriod, nodes, Q, R, Pi, mu0, ctx=self._ctx, constantTurn=constantTurn)
+        return [dict(mu=mu, x=x, P=P, logLikelihood=float(a), nObs=int(b)) for (mu, x, P), a, b in zip(per, ll, nobs)]
+
     def getTrackLikelihoods(self, terminated=False, constantTurn=False, ais=False):
         """How well the tracker's model explains each track's plots: (logLikelihood, nis, nObs) per live track, in the order of
         getSmoothTracks, with terminated=True followed by the terminated ones -- scored in ONE forward-only device call
