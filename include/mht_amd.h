@@ -455,6 +455,49 @@ int mht_imm_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, 
                       const double* Pi, const double* mu0, double* mu, double* x, double* P, double* ll, int32_t* nobs, void* work,
                       size_t work_bytes);
 
+/* mht_imm_smooth_tracks, mht_imm_smooth_tracks_ct: the FIXED-INTERVAL IMM SMOOTHER over a batch of track histories -- the filter of
+ * mht_imm_tracks / mht_imm_tracks_ct walked forward, then a mode-matched Rauch-Tung-Striebel pass walked backward (Nadarajah,
+ * Tharmarasa, McDonald and Kirubarajan 2012 for modes that share the state space, restated in csrc/mht_imm_smooth.h).  Per node it hands
+ * out the probability of every mode IN HINDSIGHT -- on time at the start and at the end of a manoeuvre, where the filter's is several
+ * scans late -- and one smoothed state and covariance that needs no choice of a single noise level.  The arguments up to mu0, their
+ * checks and the model checks are mht_imm_tracks' and mht_imm_tracks_ct's.  Then
+ *   mus      dev [L_max][n_modes][n_tracks] f64 out: the smoothed mode probabilities
+ *   xs       dev [L_max][nx][n_tracks] f64 out;  Ps dev [L_max][nx (nx + 1) / 2][n_tracks] f64 out, the upper triangle row by row: the
+ *            smoothed combined state and covariance, in mht_filter_tracks' layout (what mht_nees_nodes takes)
+ *   muf      dev [L_max][n_modes][n_tracks] f64 out, or NULL: the FILTERED mode probabilities, mht_imm_tracks' mu
+ *   ll       dev [n_tracks] f64 out and nobs dev [n_tracks] int32 out, or both NULL: mht_imm_tracks' figures
+ * Forward: mht_imm_tracks' recursion, every mode keeping per node its own state after its step, (xf_j, Pf_j), and its probability mu_j.
+ * Backward, last node: xs_j = xf_j, Ps_j = Pf_j, mus = mu, (xs, Ps) the filter's combined state.  Node k = L - 2 .. 0, sums over i ascending:
+ *   d_j = sum_i Pi[j][i] mus_i(k+1);  where d_j > 0 mode j goes back from the mixture b_i = Pi[j][i] mus_i(k+1) / d_j of the smoothed
+ *   states of node k + 1, x0_j = sum_i b_i xs_i, P0_j = sum_i b_i (Ps_i + (xs_i - x0_j)(xs_i - x0_j)'), else from its own;
+ *   A_j = A (constant turn: Phi(T, w) at xf_j(k)[4]), xp_j = A_j xf_j(k), M_j = A_j Pf_j(k) A_j';
+ *   lam_ji = -1/2 |L^-1 (xs_i(k+1) - xp_j)|^2 - sum_e ln L_ee, L L' = M_j + Q_i;  m_j = max of lam_ji over the i with Pi[j][i] > 0,
+ *   lnL_j = m_j + ln sum_i (Pi[j][i] > 0 ? Pi[j][i] exp(lam_ji - m_j) : 0);
+ *   mht_smooth_tracks' step under Q_j: Pp = M_j + Q_j, G = Pf_j A_j' Pp^-1, xs_j(k) = xf_j + G (x0_j - xp_j), Ps_j(k) = Pf_j + G (P0_j - Pp) G';
+ *   top = max of lnL_j over the j with mu_j(k) > 0, u_j = mu_j(k) > 0 ? mu_j(k) exp(lnL_j - top) : 0, mus_j(k) = u_j / sum_j u_j;
+ *   xs(k), Ps(k) the moments of the (xs_j(k), Ps_j(k)) under mus(k).
+ * The forward pass predicted mode j from its mixed state, the backward gain uses xf_j(k): that is the method's approximation.  No
+ * logarithm of Pi or of a probability is taken: zeros are legal.  muf, ll and nobs are mht_imm_tracks' bits, and at a track's last node
+ * so are mus, xs, Ps its mu, x, P.  With n_modes == 1 (Pi = [[1]]) xs and Ps are mht_smooth_tracks' (mht_smooth_tracks_ct's) bits and
+ * mus is exactly 1; with Pi = I and mu0 = (0, 1) they are that smoother's bits under mode 1's Q.  The rows len[t] <= k < L_max behind a
+ * track's end are written with a quiet NaN.
+ *   work dev, work_bytes >= mht_imm_smooth_work_bytes(nx, n_tracks, L_max, n_modes): mht_imm_work_bytes' figure plus per node and mode
+ *        the row [x | P packed | mu], L_max n_modes (nx + nx (nx + 1) / 2 + 1) n_tracks 8 bytes rounded up to 256 (0 where
+ *        mht_imm_work_bytes gives 0): MHT_E_INVALID if it is smaller.
+ * One launch, one (track, mode) per lane, forward and then backward; a lane reads back only the rows it stored itself; no track's
+ * figures depend on its place in the batch.  Synchronises.  Error codes and the rule that nothing is launched or written on
+ * MHT_E_INVALID are mht_imm_tracks' (ll without nobs, or nobs without ll, is a null array); n_tracks == 0 returns MHT_OK and writes
+ * nothing.  The AIS-aware model is not run.  Exported by both builds (nx at run time). */
+size_t mht_imm_smooth_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_max, int32_t n_modes);
+int mht_imm_smooth_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                          const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_modes,
+                          const double* Q, const double* R, const double* Pi, const double* mu0, double* mus, double* xs, double* Ps,
+                          double* muf, double* ll, int32_t* nobs, void* work, size_t work_bytes);
+int mht_imm_smooth_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
+                             const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_modes,
+                             const double* Q, const double* R, const double* Pi, const double* mu0, double* mus, double* xs, double* Ps,
+                             double* muf, double* ll, int32_t* nobs, void* work, size_t work_bytes);
+
 /* mht_nees_nodes: is the covariance a filter reports honest?  The estimation error e = x - truth and the normalised estimation error
  * squared e' P^-1 e of every node of a batch against ground truth -- the test that sees the unmeasured states, which the innovations
  * (mht_trace_tracks*) do not.  The inputs lie where mht_filter_tracks* (xf, Pf) or mht_smooth_tracks* (xs, Ps) wrote them:

@@ -156,6 +156,8 @@ def _declare(lib, nx=4):
         "mht_filter_tracks_ais": [vp, C.POINTER(MhtModelX), i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.c_size_t],
         "mht_imm_tracks": [vp, C.POINTER(MhtModelX), i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_imm_tracks_ct": [vp, C.POINTER(MhtModelX), i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
+        "mht_imm_smooth_tracks": [vp, C.POINTER(MhtModelX), i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
+        "mht_imm_smooth_tracks_ct": [vp, C.POINTER(MhtModelX), i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_nees_nodes": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
         "mht_gospa_steps": [vp, i32, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
         "mht_ospa2_windows": [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
@@ -222,6 +224,8 @@ def _declare(lib, nx=4):
     lib.mht_filter_work_bytes.restype = C.c_size_t
     lib.mht_imm_work_bytes.argtypes = [i32, i32, i32, i32]
     lib.mht_imm_work_bytes.restype = C.c_size_t
+    lib.mht_imm_smooth_work_bytes.argtypes = [i32, i32, i32, i32]
+    lib.mht_imm_smooth_work_bytes.restype = C.c_size_t
     lib.mht_gospa_work_bytes.argtypes = [i32, i32, i32]
     lib.mht_gospa_work_bytes.restype = C.c_size_t
     lib.mht_ospa2_work_bytes.argtypes = [i32, i32, i32, i32]

@@ -293,6 +293,24 @@ class Target:
                                             ctx=None if tracker is None else tracker._ctx, constantTurn=constantTurn)
         return dict(mu=per[0][0], x=per[0][1], P=per[0][2], logLikelihood=float(ll[0]), nObs=int(nobs[0]))
 
+    def getSmoothModeProbabilities(self, radarPeriod, model=None, device=0, qScales=(1.0, 16.0), stay=0.95, constantTurn=False):
+        """getModeProbabilities in hindsight: a dict mu [L, r] (smoothed), muFiltered [L, r], x [L, nx], P [L, nx, nx], logLikelihood,
+        nObs of the chain that ends in this node under the fixed-interval IMM smoother (pymht_amd.smoothing.imm_smooth_tracks defines
+        the figures; x and P are in getFilteredTrack's layout; the default scales are a starting point, not tuned; a chain of fewer
+        than two nodes gives mu0 and its initial state).  Arguments and refusals are getModeProbabilities'.  Many nodes at once:
+        Tracker.getSmoothModeProbabilities()."""
+        from . import smoothing
+        tracker = getattr(self, "_tracker", None)
+        if model is None:
+            if tracker is not None:
+                model = tracker._model_mod
+            else:
+                from .models import pv as model
+        (smoothing._check_ct_model if constantTurn else smoothing._check_model)(model)
+        Q, R, Pi, mu0 = smoothing.imm_modes(model, radarPeriod, qScales, stay=stay)
+        return smoothing.imm_smooth_nodes(model, radarPeriod, [self], Q, R, Pi, mu0, device=device,
+                                          ctx=None if tracker is None else tracker._ctx, constantTurn=constantTurn)[0]
+
     def getTrackLikelihood(self, radarPeriod, model=None, device=0, constantTurn=False, ais=False):
         """(logLikelihood, nis, nObs) of the chain that ends in this node under the model getSmoothTrack would smooth it with -- how well
         that model explains the chain's plots (pymht_amd.smoothing.score_tracks defines the figures; a chain of fewer than two nodes

@@ -46,7 +46,10 @@ One noise level rarely fits a whole track: a ship steams straight, turns for a f
 (and `imm_nodes`, `Tracker.getModeProbabilities`) run an interacting-multiple-model filter over the histories -- the same state under up
 to four (Q, R), mixed through a Markov chain over the modes (`mht_imm_tracks*`, one launch, one (track, mode) per lane) -- and hand out
 per node the probability of every mode and one combined state and covariance in `filter_tracks`' layout, per track the log-likelihood
-under the mixture, comparable with `score_tracks`'; `imm_modes` makes the modes of scalings of the model's own noise."""
+under the mixture, comparable with `score_tracks`'; `imm_modes` makes the modes of scalings of the model's own noise.
+`imm_smooth_tracks`, `imm_smooth_tracks_ct` (and `imm_smooth_nodes`, `Tracker.getSmoothModeProbabilities`, `getSmoothTracks(imm=..)`)
+walk the same filter forward and a mode-matched RTS pass backward (`mht_imm_smooth_tracks*`): the mode probabilities in hindsight and
+one smoothed state and covariance that needs no choice of a single noise level."""
 import ctypes as C
 
 import numpy as np
@@ -736,6 +739,93 @@ def imm_nodes(model, radarPeriod, nodes, Q, R, Pi, mu0=None, device=0, ctx=None,
     for i, one in zip(where, res):
         out[i] = one
     return out, ll, nobs
+
+
+def imm_smooth_tracks(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, ctx=None):
+    """The fixed-interval IMM smoother over a batch of track histories: `imm_tracks`' filter walked forward, then a mode-matched
+    Rauch-Tung-Striebel pass walked backward (Nadarajah, Tharmarasa, McDonald, Kirubarajan 2012, restated in csrc/mht_imm_smooth.h) --
+    the probability of every mode IN HINDSIGHT, which is on time at the start of a manoeuvre and at its end where the filter's is
+    several scans late, and one smoothed state and covariance that needs no choice of a single noise level.  Arguments, checks and
+    refusals are `imm_tracks`'.  Returns one dict per track, in the order of `tracks`:
+        mu [L, r] the smoothed mode probabilities, muFiltered [L, r] `imm_tracks`' own (its bits),
+        x [L, nx], P [L, nx, nx] the smoothed combined state and covariance in `filter_tracks`' layout -- `evaluation.nees_nodes`
+        takes them as they are --, logLikelihood and nObs as `imm_tracks` gives them (its bits).
+    At a track's last node mu, x, P are `imm_tracks`' bits.  With one mode (Pi = [[1.]]) x and P are `smooth_tracks`' bits and mu is
+    exactly 1.  An empty list gives [].  One device launch (`mht_imm_smooth_tracks`), one (track, mode) per lane, no host fallback."""
+    return _imm_smooth_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_model(model), False)
+
+
+def imm_smooth_tracks_ct(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, ctx=None):
+    """`imm_smooth_tracks` under the constant-turn model `smooth_tracks_ct` smooths with (anything else raises ValueError): nx = 6, going
+    backward every mode's Phi(T, w) is taken at the turn rate of its own filtered state."""
+    return _imm_smooth_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_ct_model(model), True)
+
+
+def _imm_smooth_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, nx, constant_turn):
+    Q, R, Pi, mu0 = _check_modes(Q, R, Pi, mu0, nx)
+    if len(tracks) == 0:
+        return []
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        return _imm_smooth(ctx, model, float(radarPeriod), tracks, Q, R, Pi, mu0, nx, constant_turn)
+    finally:
+        if own:
+            ctx.close()
+
+
+def _imm_smooth(ctx, model, period, tracks, Q, R, Pi, mu0, nx, constant_turn):
+    n, r, ns = len(tracks), len(Q), nx * (nx + 1) // 2
+    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
+    dev, lib = ctx.device, ctx.lib
+    mus_d = torch.empty((L_max, r, n), dtype=torch.float64, device=dev)
+    muf_d = torch.empty((L_max, r, n), dtype=torch.float64, device=dev)
+    xo_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
+    Po_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev)
+    ll_d = torch.empty(n, dtype=torch.float64, device=dev)
+    nobs_d = torch.empty(n, dtype=torch.int32, device=dev)
+    need = int(lib.mht_imm_smooth_work_bytes(nx, n, L_max, r))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mx, keep = _model_x(model, period, nx, constant_turn)
+    lens_sorted = np.ascontiguousarray(lens[order])
+    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
+    seam = lib.mht_imm_smooth_tracks_ct if constant_turn else lib.mht_imm_smooth_tracks
+    hostp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, hostp(lens_sorted), x_d.data_ptr(), P_d.data_ptr(), z_d.data_ptr(), h_d.data_ptr(), r,
+                    hostp(Q), hostp(R), hostp(Pi), hostp(mu0), mus_d.data_ptr(), xo_d.data_ptr(), Po_d.data_ptr(), muf_d.data_ptr(),
+                    ll_d.data_ptr(), nobs_d.data_ptr(), work.data_ptr(), need), lib)
+    mus = mus_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][mode]
+    muf = muf_d.permute(2, 0, 1).contiguous().cpu().numpy()
+    xo = xo_d.permute(2, 0, 1).contiguous().cpu().numpy()
+    Po = Po_d.index_select(1, _unpack_index(nx, dev)).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
+    ll, nobs = ll_d.cpu().numpy(), nobs_d.cpu().numpy()
+    out = [None] * n
+    for j, t in enumerate(order):
+        L = int(lens[t])
+        out[t] = dict(mu=mus[j, :L], muFiltered=muf[j, :L], x=xo[j, :L], P=Po[j, :L], logLikelihood=float(ll[j]), nObs=int(nobs[j]))
+    return out
+
+
+def imm_smooth_nodes(model, radarPeriod, nodes, Q, R, Pi, mu0=None, device=0, ctx=None, constantTurn=False):
+    """`imm_smooth_tracks` for many track nodes in one device call, built on `chain_inputs` like `imm_nodes`: one dict per node.  A chain
+    of fewer than two nodes was never filtered: mu0 twice, its initial state and covariance, logLikelihood 0.0, nObs 0, and no device
+    is needed to say so.  constantTurn as for `imm_nodes`; AIS messages are not taken."""
+    run = imm_smooth_tracks_ct if constantTurn else imm_smooth_tracks
+    nx = (_check_ct_model if constantTurn else _check_model)(model)
+    Q, R, Pi, mu0 = _check_modes(Q, R, Pi, mu0, nx)
+    out, batch, where = [None] * len(nodes), [], []
+    for i, node in enumerate(nodes):
+        chain, inputs = chain_inputs(node, model.P0)
+        if len(chain) < 2:
+            out[i] = dict(mu=mu0.reshape(1, -1).copy(), muFiltered=mu0.reshape(1, -1).copy(), x=inputs[0].reshape(1, nx).copy(),
+                          P=inputs[1].reshape(1, nx, nx).copy(), logLikelihood=0.0, nObs=0)
+        else:
+            batch.append(inputs)
+            where.append(i)
+    for i, one in zip(where, run(model, radarPeriod, batch, Q, R, Pi, mu0, device=device, ctx=ctx)):
+        out[i] = one
+    return out
 
 
 def consistency(traces, alpha=0.05):

@@ -997,7 +997,7 @@ class Tracker():
         return smoothing.smooth_nodes(self._model_mod, self.radarPeriod, nodes, ctx=self._ctx, constantTurn=constantTurn,
                                       ais=self._ais_lookup(constantTurn) if ais else None, em=em, emStart=emStart)
 
-    def getSmoothTracks(self, terminated=False, constantTurn=False, ais=False, em=0, emStart="model"):
+    def getSmoothTracks(self, terminated=False, constantTurn=False, ais=False, em=0, emStart="model", imm=None):
         """tracker.py: [track.getSmoothTrack(radarPeriod) for track in __trackNodes__] -- (positions, velocities, ok) per live track, with
         terminated=True followed by the terminated ones (__terminatedTargets__) -- smoothed in ONE batched device call
         (pymht_amd/smoothing.py: a Rauch-Tung-Striebel smoother with the tracker's own model, not pykalman).  A constant-turn tracker
@@ -1010,10 +1010,23 @@ class Tracker():
         em > 0 (linear models; not with constantTurn or ais: ValueError): Q, R and the initial state are learned per track by `em`
         EM iterations before the smoothing walk (smoothing.smooth_tracks_em); emStart="reference" starts them at the identity as the
         reference's pykalman call does, so that em=5, emStart="reference" is the reference's procedure, restated.  ok is False for a
-        track whose learned covariances stopped being positive definite (its output is NaN)."""
+        track whose learned covariances stopped being positive definite (its output is NaN).
+        imm: None, or a tuple of scales of Q (getSmoothModeProbabilities' qScales, with its default `stay`): positions and velocities
+        are then the IMM smoother's combined state (smoothing.imm_smooth_nodes), which needs no choice of a single noise level; not
+        together with ais=True or em > 0 (ValueError).  A chain of fewer than two nodes is answered as without imm."""
         nodes = list(self.__trackNodes__)
         if terminated:
             nodes += list(self.__terminatedTargets__)
+        if imm is not None:
+            if ais or em:
+                raise ValueError("imm smooths under several noise levels of the tracker's model: not together with ais=True or em > 0")
+            out = []
+            for node, d in zip(nodes, self._imm_smooth_nodes(nodes, imm, 0.95, constantTurn)):
+                if len(d["x"]) < 2:      # (nothing to smooth: its measurements, NaN velocities, False -- no device call)
+                    out.append(self._smooth_nodes([node], constantTurn=constantTurn)[0])
+                else:
+                    out.append((d["x"][:, 0:2], d["x"][:, 2:4], True))
+            return out
         return self._smooth_nodes(nodes, constantTurn=constantTurn, ais=ais, em=em, emStart=emStart)
 
     def getFilteredTracks(self, terminated=False, constantTurn=False, ais=False):
@@ -1049,6 +1062,25 @@ class Tracker():
         Q, R, Pi, mu0 = smoothing.imm_modes(self._model_mod, self.radarPeriod, qScales, stay=stay)
         per, ll, nobs = smoothing.imm_nodes(self._model_mod, self.radarPeriod, nodes, Q, R, Pi, mu0, ctx=self._ctx, constantTurn=constantTurn)
         return [dict(mu=mu, x=x, P=P, logLikelihood=float(a), nObs=int(b)) for (mu, x, P), a, b in zip(per, ll, nobs)]
+
+    def _imm_smooth_nodes(self, nodes, qScales, stay, constantTurn):
+        from . import smoothing
+        (smoothing._check_ct_model if constantTurn else smoothing._check_model)(self._model_mod)
+        Q, R, Pi, mu0 = smoothing.imm_modes(self._model_mod, self.radarPeriod, qScales, stay=stay)
+        return smoothing.imm_smooth_nodes(self._model_mod, self.radarPeriod, nodes, Q, R, Pi, mu0, ctx=self._ctx, constantTurn=constantTurn)
+
+    def getSmoothModeProbabilities(self, qScales=(1.0, 16.0), stay=0.95, terminated=False, constantTurn=False):
+        """getModeProbabilities IN HINDSIGHT: the fixed-interval IMM smoother over every track history (smoothing.imm_smooth_nodes /
+        imm_smooth_tracks, which define the figures), in ONE device call.  The filter says where a louder model takes over several
+        scans late, at the start of a turn and again at its end; the smoother has seen the scans behind.  One dict per track, in
+        getModeProbabilities' order and with its arguments and refusals: mu [L, r] the smoothed probability of every mode, muFiltered
+        [L, r] getModeProbabilities' own, x [L, nx] and P [L, nx, nx] the smoothed combined state and covariance in getFilteredTracks'
+        layout (what evaluation.nees_nodes takes as they are), logLikelihood and nObs as getModeProbabilities gives them.  With
+        qScales=(1.0,) x and P are the smoother's own (smoothing.smooth_tracks).  The default scales are a starting point, NOT tuned."""
+        nodes = list(self.__trackNodes__)
+        if terminated:
+            nodes += list(self.__terminatedTargets__)
+        return self._imm_smooth_nodes(nodes, qScales, stay, constantTurn)
 
     def getTrackLikelihoods(self, terminated=False, constantTurn=False, ais=False):
         """How well the tracker's model explains each track's plots: (logLikelihood, nis, nObs) per live track, in the order of
