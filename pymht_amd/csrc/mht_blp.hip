@@ -36,6 +36,40 @@ constexpr double DINF = 1.0e300;
 constexpr int BIG_MAXH = 2048, BIG_MAXR = 1024, BIG_MAXK = 256;      // default LDS tier: columns, rows, targets of a cluster solved out of LDS
 // (member tables hold cap_k + 4 entries: (cap_k + 4) * 4 and * 8 are multiples of 16 bytes when cap_k is a multiple of 4)
 
+// ---- the argument block as the device code sees it ---------------------------------------------------------------------------------
+// Every device function below takes the block as `AT* ap` (a pointer, NOT a reference: what a reference parameter promises -- the whole block
+// dereferenceable -- lets the compiler hoist every read of it to the top of the kernel again) and reads a.field where it needs it.  AT is
+//   (const) BlpArgs   a copy in registers (blp_kernel's by-value parameter, the batched kernels' load_args copy): as ever;
+//   KBlpArgs          blp_uf_kernel: the kernel's own argument segment, in the CONSTANT address space behind a pointer the compiler cannot
+//                     see through -- a.field is a scalar load at the point of use (hoisted out of the loops around it, never out of the
+//                     phase), so the ~130 pointers of the block are not loaded up front and kept alive -- spilled to VGPR lanes -- through
+//                     the whole kernel; what only the cold paths use (HBM scratch, branch-and-bound snapshots, teams, shards, tiers,
+//                     debugging) is read on those paths alone;
+//   KBlpArgsPlain     blp_uf_plain_kernel: the same segment, with the switches a plain forest never changes between scans compiled in --
+//                     the static members below HIDE the fields of the same name, so a.pds IS 8 and the code behind a.dbg is gone.
+//                     launch_blp checks the block against blp_is_plain() at every launch and picks the instance.
+typedef const __attribute__((address_space(4))) BlpArgs KBlpArgs;
+struct BlpArgsPlain : BlpArgs {
+    static constexpr int pds = 8, shard_n = 1, shard_i = 0, tier = 0, force_hbm = 0, no_enum = 0, no_reduce = 0, skip_dead = 0;
+    static constexpr int cap_h = BIG_MAXH, cap_r = BIG_MAXR, cap_k = BIG_MAXK;      // (tier 0 without MHT_BLP_CAPS)
+    static constexpr int32_t* shard_team = nullptr;
+    static constexpr int32_t* sel_rel = nullptr;
+    static constexpr const int32_t* cl_owner = nullptr;
+    static constexpr int32_t* big_list = nullptr;
+    static constexpr unsigned long long* dbg = nullptr;
+};
+static_assert(sizeof(BlpArgsPlain) == sizeof(BlpArgs), "the plain view adds no field");
+typedef const __attribute__((address_space(4))) BlpArgsPlain KBlpArgsPlain;
+template <typename AT> struct blp_plain { static constexpr bool value = false; };
+template <> struct blp_plain<KBlpArgsPlain> { static constexpr bool value = true; };
+// "is this optional table there?" -- the plain instance knows that a forest's are (blp_is_plain): no test, the pointer is read where it is used
+#define BLP_HAS(f) (blp_plain<AT>::value || a.f != nullptr)
+// what the plain instance takes for granted, checked by the host on the block it launches with (after blp_set_tier)
+static bool blp_is_plain(const BlpArgs& b) {
+    return b.pds == 8 && b.PD <= 8 && b.shard_n <= 1 && !b.shard_team && !b.sel_rel && !b.cl_owner && b.tier == 0 && !b.force_hbm && !b.no_enum &&
+           !b.no_reduce && !b.skip_dead && !b.dbg && b.t_alive && b.rec && b.status && b.rec0 && b.blp_done && b.begun && b.cap_h == BIG_MAXH && b.cap_r == BIG_MAXR && b.cap_k == BIG_MAXK;
+}
+
 struct Red {
     double d[BLP_THREADS / 64];
     double q[BLP_THREADS / 64][4];
@@ -145,7 +179,8 @@ __device__ __forceinline__ void block_min_pair(double& v, int& i, Red* r) {
 #define MHT_GS_CK 1
 #endif
 struct GStore {      // HBM: column = global child index, row = global measurement-node id, row set = LDS bitset
-    const BlpArgs* a; const int32_t* mem; const unsigned long long* uw; int UW, PD; size_t cap;
+    const int32_t *tchild, *tcend; const double* costp; const int32_t* path; int pds;      // (the five fields of the argument block the policy reads)
+    const int32_t* mem; const unsigned long long* uw; int UW, PD; size_t cap;
     double* pu; int32_t* pusage; int32_t* pmark;      // prices / usage / marks by measurement node: the workgroup's own copy (a team member's, or the shared one)
     int32_t *best_h, *ub_sel, *ch, *lix; double *best_rc, *cst, *uus, *lrc, *rest, *mn;
     // (r5) ck: the members' column ranges are cbL[k] .. ceL[k] (LDS, filled by solve_cluster for clusters of <= cap_k targets) instead of two
@@ -155,10 +190,10 @@ struct GStore {      // HBM: column = global child index, row = global measureme
     // accesses): G20 131 -> 155 ms, profiles/r05_ilp_tail.txt.)
     bool ck; const int32_t *cbL, *ceL;
     __device__ __forceinline__ int row(int m) const { return m; }
-    __device__ __forceinline__ int col_begin(int k) const { return (MHT_GS_CK && ck) ? cbL[k] : a->tchild[mem[k]]; }
-    __device__ __forceinline__ int col_end(int k) const { return (MHT_GS_CK && ck) ? ceL[k] : a->tcend[mem[k]]; }
-    __device__ __forceinline__ double cost(int h) const { return a->cost[h]; }
-    __device__ __forceinline__ int ent(int d, int h) const { return a->pds ? a->path[(size_t)h * a->pds + d] : a->path[(size_t)d * cap + h]; }
+    __device__ __forceinline__ int col_begin(int k) const { return (MHT_GS_CK && ck) ? cbL[k] : tchild[mem[k]]; }
+    __device__ __forceinline__ int col_end(int k) const { return (MHT_GS_CK && ck) ? ceL[k] : tcend[mem[k]]; }
+    __device__ __forceinline__ double cost(int h) const { return costp[h]; }
+    __device__ __forceinline__ int ent(int d, int h) const { return pds ? path[(size_t)h * pds + d] : path[(size_t)d * cap + h]; }
     __device__ __forceinline__ double& u(int m) const { return pu[row(m)]; }
     __device__ __forceinline__ int32_t& usage(int m) const { return pusage[row(m)]; }
     __device__ __forceinline__ int32_t& mark(int m) const { return pmark[row(m)]; }
@@ -223,8 +258,8 @@ struct LStore {      // LDS: column = dense local index, row = dense local id
 #define MHT_ROWS8 1
 #endif
 __device__ __forceinline__ void rows8(const GStore& s, int h, int (&e)[8]) {
-    if (s.a->pds == 8) {
-        const int4* p = reinterpret_cast<const int4*>(s.a->path + (size_t)h * 8);
+    if (s.pds == 8) {
+        const int4* p = reinterpret_cast<const int4*>(s.path + (size_t)h * 8);
         const int4 q0 = p[0], q1 = p[1];
         e[0] = q0.x; e[1] = q0.y; e[2] = q0.z; e[3] = q0.w; e[4] = q1.x; e[5] = q1.y; e[6] = q1.z; e[7] = q1.w;
     } else {
@@ -1088,8 +1123,8 @@ __device__ __forceinline__ bool enumerate_small(const LStore& s, int K, Red* r, 
 // solved there from scratch -- coordinate rounds, exact search or branch and bound at LDS speed -- which is exact: the survivors
 // contain every selection of cost <= UB, the incumbent itself included.
 constexpr int MHT_BLP_REDUCE = -2;      // solve_core(GStore): not solved, thresholds of the survivors in s.mn[], counts in s.lix[]
-__device__ __forceinline__ bool reducible(const BlpArgs&, const LStore&, int, double, Red*) { return false; }
-__device__ __forceinline__ bool reducible(const BlpArgs& a, const GStore& s, int K, double UB, Red* r) {
+template <typename AT> __device__ __forceinline__ bool reducible(AT*, const LStore&, int, double, Red*) { return false; }
+template <typename AT> __device__ __forceinline__ bool reducible(AT* ap, const GStore& s, int K, double UB, Red* r) { AT& a = *ap;
     if (a.force_hbm || a.no_reduce || K > a.cap_k || a.PD > 8 || !(UB < DINF)) return false;
     const int tid = threadIdx.x;
     compute_minimisers(s, K, r);      // best_rc[] at the prices the dual phase ended with
@@ -1158,8 +1193,8 @@ __device__ __forceinline__ unsigned team_hash(int c0, int c1) {      // (level-0
     h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
     return h;
 }
-template <typename S> __device__ __forceinline__ void solve_core(const BlpArgs& a, const S& s, int K, Red* r, int& status, int& iters, int& nodes, unsigned long long* stamp,
-                                                                 double& ub, const Team tm = Team(0, 1, nullptr)) {
+template <typename AT, typename S> __device__ __forceinline__ void solve_core(AT* ap, const S& s, int K, Red* r, int& status, int& iters, int& nodes, unsigned long long* stamp,
+                                                                 double& ub, const Team tm = Team(0, 1, nullptr)) { AT& a = *ap;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double& UB = ub;
     double best_LB = -DINF, theta = 1.0, utot = 0.0;
@@ -1194,7 +1229,7 @@ template <typename S> __device__ __forceinline__ void solve_core(const BlpArgs& 
         }
         // a cluster on HBM scratch that has a feasible point: do few enough columns survive reduced-cost fixing at these prices to
         // go on in LDS?  (asked a few times: every sweep over thousands of columns in HBM costs ~1 ms)
-        if ((it == 24 || it == 64 || it == 128) && UB < DINF && reducible(a, s, K, UB, r)) { status = MHT_BLP_REDUCE; return; }
+        if ((it == 24 || it == 64 || it == 128) && UB < DINF && reducible(&a, s, K, UB, r)) { status = MHT_BLP_REDUCE; return; }
         // A: per target the minimiser of the reduced cost (lowest column index wins ties)
         compute_minimisers(s, K, r);
         if (it == 0) stamp[1] = wall_clock64();
@@ -1349,7 +1384,7 @@ template <typename S> __device__ __forceinline__ void solve_core(const BlpArgs& 
         __threadfence_block();
         __syncthreads();
     }
-    if (reducible(a, s, K, UB, r)) { status = MHT_BLP_REDUCE; return; }      // (HBM policy only) solve_cluster rebuilds it in LDS
+    if (reducible(&a, s, K, UB, r)) { status = MHT_BLP_REDUCE; return; }      // (HBM policy only) solve_cluster rebuilds it in LDS
     int32_t* ord = reinterpret_cast<int32_t*>(s.best_rc);       // position -> member (best_rc is dead from here on)
     int32_t* bh = s.best_h;                                      // position -> minimiser column of the current node
     {   // hot-first order: minimisers and usage under the final prices
@@ -1645,7 +1680,7 @@ template <typename S> __device__ __forceinline__ void solve_core(const BlpArgs& 
 // survival is decided with ONE ancestor-table look-up per child (child descends from the new root <=> its ancestor at the
 // root's depth IS the new root) instead of comparing path prefixes.
 struct TgtPre { int j, rscan, rnode, id, lab, cb, ce; double rootc; uint8_t rootf; };
-__device__ __forceinline__ TgtPre load_target(const BlpArgs& a, int t) {
+template <typename AT> __device__ __forceinline__ TgtPre load_target(AT* ap, int t) { AT& a = *ap;
     TgtPre p;
     const int dg = a.t_depth[t] + 1, w = a.t_window[t] & 0xff;      // (bits 8..: mht_kernels.h WIN_REBUILT_*)
     p.j = dg > w ? dg - w : 0;             // layers the root advances (pyTarget.pruneDepth)
@@ -1662,12 +1697,12 @@ constexpr int KEY_DEAD = -1, KEY_ALL = -2;
 // new root (children whose ancestor table holds it at level j-1 survive).
 // (publication for an overlapping grow launch, BlpArgs::rec0: the new root's cumulative score is written through here, the record that
 // names it valid follows from whoever knows the surviving leaf range: blp_publish)
-__device__ __forceinline__ void blp_publish(const BlpArgs& a, int t, int key, int j, int rf, int count, int first) {
-    if (!a.rec0) return;
+template <typename AT> __device__ __forceinline__ void blp_publish(AT* ap, int t, int key, int j, int rf, int count, int first) { AT& a = *ap;
+    if (!BLP_HAS(rec0)) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the root score's store has left)
     __hip_atomic_store(&a.rec0[t], tgt_rec(a.pub_scan, key != -1, rf, j, count, count > 0 ? first : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ int finish_target(const BlpArgs& a, int t, int s, const TgtPre& p, bool store, int* rf_out = nullptr) {
+template <typename AT> __device__ __forceinline__ int finish_target(AT* ap, int t, int s, const TgtPre& p, bool store, int* rf_out = nullptr) { AT& a = *ap;
     const int kc = a.kc;
     const double cn = a.cnllr[s];
     const uint8_t fl = a.flags[s];
@@ -1711,7 +1746,7 @@ __device__ __forceinline__ int finish_target(const BlpArgs& a, int t, int s, con
         a.t_jdrop[t] = j;
         a.t_score[t] = score;
         a.w_root_scan[t] = rscan; a.w_root_node[t] = rnode; a.w_root_f32[t] = rf;
-        if (a.rec0) __hip_atomic_store(reinterpret_cast<unsigned long long*>(&a.w_root_cnllr[t]), (unsigned long long)__double_as_longlong(rc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (BLP_HAS(rec0)) __hip_atomic_store(reinterpret_cast<unsigned long long*>(&a.w_root_cnllr[t]), (unsigned long long)__double_as_longlong(rc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else a.w_root_cnllr[t] = rc;
         mht_target_report& r = a.rec[t];
         r.id = p.id;
@@ -1737,10 +1772,10 @@ __device__ __forceinline__ int finish_target(const BlpArgs& a, int t, int s, con
 // N-scan pruning, child side (pyTarget.pruneDepth -> _pruneAllHypothesisExceptThis, pyTarget.py:330-356).  Survivors of a
 // target are one contiguous DFS range: only (first, count) are recorded.  One wavefront per target; `va0` is the
 // ancestor entry of the lane's child in the first chunk, fetched by the caller before the key was known.
-__device__ __forceinline__ int sweep_prefetch(const BlpArgs& a, int j, int cb, int ce, int lane) {
+template <typename AT> __device__ __forceinline__ int sweep_prefetch(AT* ap, int j, int cb, int ce, int lane) { AT& a = *ap;
     return (j > 0 && cb + lane < ce) ? a.apath[(size_t)(cb + lane) * a.pds + (j - 1)] : -1;
 }
-__device__ __forceinline__ void sweep_survivors(const BlpArgs& a, int t, int j, int cb, int ce, int key, int va0, int lane, int rf = -1) {      // rf < 0: the target's root flag is read back
+template <typename AT> __device__ __forceinline__ void sweep_survivors(AT* ap, int t, int j, int cb, int ce, int key, int va0, int lane, int rf = -1) { AT& a = *ap;      // rf < 0: the target's root flag is read back
     int count = 0, first = 0x7fffffff;
     if (key == KEY_ALL) {
         count = ce - cb;
@@ -1756,36 +1791,36 @@ __device__ __forceinline__ void sweep_survivors(const BlpArgs& a, int t, int j, 
     }
     if (lane == 0) {
         a.t_count[t] = count; a.t_firstsurv[t] = first;
-        if (a.rec0) blp_publish(a, t, key, j, rf >= 0 ? rf : (int)a.w_root_f32[t], count, first);
+        if (BLP_HAS(rec0)) blp_publish(&a, t, key, j, rf >= 0 ? rf : (int)a.w_root_f32[t], count, first);
     }
 }
 
 // surviving leaf ranges of the members of a cluster: one wavefront per target; key[k] = survival key from finish_target
-__device__ __forceinline__ void prune_members(const BlpArgs& a, const int32_t* mem, int K, const int32_t* key) {
-    if (!a.t_alive) return;
+template <typename AT> __device__ __forceinline__ void prune_members(AT* ap, const int32_t* mem, int K, const int32_t* key) { AT& a = *ap;
+    if (!BLP_HAS(t_alive)) return;
     __threadfence_block();
     __syncthreads();
     const int lane = threadIdx.x & 63;
     for (int k = threadIdx.x >> 6; k < K; k += BLP_THREADS / 64) {
         const int t = mem[k];
         const int j = a.t_jdrop[t], cb = a.tchild[t], ce = a.tcend[t];
-        sweep_survivors(a, t, j, cb, ce, key[k], sweep_prefetch(a, j, cb, ce, lane), lane);
+        sweep_survivors(&a, t, j, cb, ce, key[k], sweep_prefetch(&a, j, cb, ce, lane), lane);
     }
 }
 
 // a cluster as the solver sees it: index among all clusters (by smallest member), offset of its (ascending) member list in cl_members,
 // size, smallest member (= its label; only filled in when the clusters come from the union-find)
 struct ClRef { int c, p0, K, root; };
-__device__ __forceinline__ ClRef cl_ref(const BlpArgs& a, int c) { const int p0 = a.cl_ptr[c]; return ClRef{c, p0, a.cl_ptr[c + 1] - p0, -1}; }
+template <typename AT> __device__ __forceinline__ ClRef cl_ref(AT* ap, int c) { AT& a = *ap; const int p0 = a.cl_ptr[c]; return ClRef{c, p0, a.cl_ptr[c + 1] - p0, -1}; }
 // (clusters from the union-find: t_label is written by ONE workgroup of the launch, for the host -- the label travels with the ClRef)
-__device__ __forceinline__ TgtPre load_target_cr(const BlpArgs& a, int t, const ClRef& cr) {
-    TgtPre p = load_target(a, t);
+template <typename AT> __device__ __forceinline__ TgtPre load_target_cr(AT* ap, int t, const ClRef& cr) { AT& a = *ap;
+    TgtPre p = load_target(&a, t);
     if (a.uf_epoch) p.lab = cr.root;
     return p;
 }
 // my_t: member `threadIdx.x` of the cluster if the caller has it at hand (-1: read from the member list), pre_in: its record if already fetched
-__device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, unsigned long long* uw, Red* r, unsigned char* lds,
-                                              const Team tm = Team(0, 1, nullptr), const int team_idx = -1, const int my_t = -1, const TgtPre* pre_in = nullptr, const int dbg_bx = -1) {
+template <typename AT> __device__ __forceinline__ void solve_cluster(AT* ap, const ClRef cr, unsigned long long* uw, Red* r, unsigned char* lds,
+                                              const Team tm = Team(0, 1, nullptr), const int team_idx = -1, const int my_t = -1, const TgtPre* pre_in = nullptr, const int dbg_bx = -1) { AT& a = *ap;
     const int tid = threadIdx.x;
     const int c = cr.c;
     const int K = cr.K;
@@ -1795,13 +1830,22 @@ __device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, 
     const unsigned long long t_begin = wall_clock64();
     const unsigned long long c_begin = clock64();
     TgtPre pre = {};      // per-member data of the prune epilogue, fetched now so that its latency hides behind the solve
-    const bool pre_ok = a.t_alive && K <= BLP_THREADS;
-    if (pre_ok && tid < K) { if (pre_in && my_t >= 0) pre = *pre_in; else pre = load_target_cr(a, my_t >= 0 ? my_t : mem[tid], cr); }
+    const bool pre_ok = BLP_HAS(t_alive) && K <= BLP_THREADS;
+    if (pre_ok && tid < K) { if (pre_in && my_t >= 0) pre = *pre_in; else pre = load_target_cr(&a, my_t >= 0 ? my_t : mem[tid], cr); }
     // LDS carve: every block below is a multiple of 16 bytes and the dynamic segment starts at offset 0 (the kernel has
     // no static __shared__), so the 16-byte column records stay aligned without integer round trips -- those would
     // make the compiler lose the LDS address space and emit slow flat accesses.
     LStore s;
-    unsigned char* q = lds;
+    // (the carve starts from an offset the compiler cannot see through -- zero: the ~30 table addresses are formed HERE, per cluster; as
+    // loop invariants of the launch's staged loop they were all formed at the kernel's entry, in front of the prologue's first load, and
+    // parked in VGPR lanes until a cluster came along)
+    // The plain instance takes the zero in a VECTOR register: its capacities are compile-time constants, so every table address is
+    // "this base + a literal" and the literal folds into the address arithmetic of the access (LDS addresses are formed per lane anyway).
+    // From a scalar base the compiler forms base + literal once per table, ~30 scalars that live through the whole solve and spill to VGPR
+    // lanes -- which is all the generic instance can do, its offsets being run-time values.
+    unsigned lz = 0;
+    if (blp_plain<AT>::value) asm volatile("" : "+v"(lz)); else asm volatile("" : "+s"(lz));
+    unsigned char* q = lds + lz;
     const int L_MAXH = a.cap_h, L_MAXR = a.cap_r, L_MAXK = a.cap_k, L_KPAD = a.cap_k + 4;      // this launch's LDS tier (BlpArgs)
     int* s_wbase = reinterpret_cast<int*>(q); q += (size_t)a.cap_uw * 4;
     int* s_scal = reinterpret_cast<int*>(q); q += 16;
@@ -1874,7 +1918,7 @@ __device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, 
     // the epilogue's survivor test needs ONE ancestor-table entry per child (level j - 1 of its target): fetched with the column, parked in gcolL (only a
     // REDUCED cluster uses that table for something else, and it sweeps its members' ranges generically): one global round trip less behind the solve
     // (+0.5 % over 400 scans, profiles/r06_experiments.txt; the new root's record fetched speculatively through the same entry: measured, -0.2 %, not kept)
-    const bool anc_pf = lds_cols && pre_ok && K <= 64 && a.t_alive && a.pds == 8;
+    const bool anc_pf = lds_cols && pre_ok && K <= 64 && BLP_HAS(t_alive) && a.pds == 8;
     s.nH = nH; s.PD = a.PD; s.K = K;
     // ---- measurement nodes of the cluster (union of the rows of its columns); in the LDS case the columns are
     //      copied in the same sweep: every thread issues the PD+1 loads of a column back to back (one round trip)
@@ -2032,7 +2076,7 @@ __device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, 
     if (!use_lds) {
         // ---- HBM scratch: the same solver, generic column access ----------------------------------------------------
         GStore gs;
-        gs.a = &a; gs.mem = mem; gs.uw = uw; gs.UW = UW; gs.PD = a.PD; gs.cap = (size_t)a.cap;
+        gs.tchild = a.tchild; gs.tcend = a.tcend; gs.costp = a.cost; gs.path = a.path; gs.pds = a.pds; gs.mem = mem; gs.uw = uw; gs.UW = UW; gs.PD = a.PD; gs.cap = (size_t)a.cap;
         const size_t om = team_hbm ? (size_t)tm.q * a.tm_sm : 0, os = (team_hbm ? (size_t)tm.q * a.tm_ss : 0) + (size_t)slot;      // this member's copies
         gs.pu = a.u + om; gs.pusage = a.usage + om; gs.pmark = a.mark + om;
         gs.ck = small_k;      // (colb / gbase were filled above)
@@ -2048,7 +2092,7 @@ __device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, 
         __threadfence_block();
         __syncthreads();
         double ub = DINF;
-        solve_core(a, gs, K, r, status, iters, nodes, stamp, ub, team_hbm ? tm : Team(0, 1, nullptr));
+        solve_core(&a, gs, K, r, status, iters, nodes, stamp, ub, team_hbm ? tm : Team(0, 1, nullptr));
         ub_reduced = ub;
 #ifdef MHT_BLP_TRACE
         if (tid == 0) printf("[blp] cluster %d K=%d nH=%d: HBM phase status %d iters %d nodes %d, %.2f ms (setup %.2f)\n", c, K, nH, status, iters, nodes,
@@ -2119,9 +2163,9 @@ __device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, 
                 const int h = final_sel ? __hip_atomic_load(const_cast<int32_t*>(final_sel) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : gs.ub_sel[k];
                 a.sel[mem[k]] = h;
                 if (a.sel_rel) a.sel_rel[mem[k]] = h - a.tchild[mem[k]];
-                if (a.t_alive) gs.ch[k] = finish_target(a, mem[k], h, pre_ok ? pre : load_target_cr(a, mem[k], cr), true);
+                if (BLP_HAS(t_alive)) gs.ch[k] = finish_target(&a, mem[k], h, pre_ok ? pre : load_target_cr(&a, mem[k], cr), true);
             }
-            if (!xteam) prune_members(a, mem, K, gs.ch);
+            if (!xteam) prune_members(&a, mem, K, gs.ch);
         }
     }
     if (use_lds) {
@@ -2144,7 +2188,7 @@ __device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, 
 #ifdef MHT_BLP_TRACE
         if (tid == 0 && s.reduced) printf("[blp] cluster %d: rebuilt with %d columns %d rows at %.2f ms\n", c, nHl, nR, 1e-5 * (double)(wall_clock64() - t_begin));
 #endif
-        solve_core(a, s, K, r, status, iters, nodes, stamp, ub, team ? tm : Team(0, 1, nullptr));
+        solve_core(&a, s, K, r, status, iters, nodes, stamp, ub, team ? tm : Team(0, 1, nullptr));
 #ifdef MHT_BLP_TRACE
         if (tid == 0 && s.reduced) printf("[blp] cluster %d: LDS phase status %d iters %d nodes %d at %.2f ms\n", c, status, iters, nodes, 1e-5 * (double)(wall_clock64() - t_begin));
 #endif
@@ -2163,18 +2207,18 @@ __device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, 
             const int h = final_sel ? __hip_atomic_load(const_cast<int32_t*>(final_sel) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : s.to_global(s.ub_sel[k]);
             a.sel[mem[k]] = h;
             if (a.sel_rel) a.sel_rel[mem[k]] = h - a.tchild[mem[k]];
-            if (a.t_alive) {
-                const TgtPre q = pre_ok ? pre : load_target_cr(a, mem[k], cr);
-                s.ch[k] = finish_target(a, mem[k], h, q, true, &rf_mine);      // (K <= BLP_THREADS in LDS: one member per thread)
+            if (BLP_HAS(t_alive)) {
+                const TgtPre q = pre_ok ? pre : load_target_cr(&a, mem[k], cr);
+                s.ch[k] = finish_target(&a, mem[k], h, q, true, &rf_mine);      // (K <= BLP_THREADS in LDS: one member per thread)
                 s.ub_sel[k] = q.j;             // the solver's tables are free now: prune depth, survivor count, first survivor
                 s.lix[k] = 0;
                 s.best_h[k] = 0x7fffffff;
             }
         }
-        if (a.t_alive && s.reduced) {      // (the LDS store holds a subset of the children: generic sweep over the members' ranges)
+        if (BLP_HAS(t_alive) && s.reduced) {      // (the LDS store holds a subset of the children: generic sweep over the members' ranges)
             __syncthreads();
-            prune_members(a, mem, K, s.ch);
-        } else if (a.t_alive) {
+            prune_members(&a, mem, K, s.ch);
+        } else if (BLP_HAS(t_alive)) {
             // surviving leaf ranges: one thread per column (= child), one ancestor look-up each, LDS counters per member
             __syncthreads();
             for (int h = tid; h < nH; h += BLP_THREADS) {
@@ -2189,7 +2233,7 @@ __device__ __forceinline__ void solve_cluster(const BlpArgs& a, const ClRef cr, 
             for (int k = tid; k < K; k += BLP_THREADS) {
                 a.t_count[mem[k]] = s.lix[k];
                 a.t_firstsurv[mem[k]] = s.best_h[k];
-                blp_publish(a, mem[k], s.ch[k], s.ub_sel[k], rf_mine, s.lix[k], s.best_h[k]);
+                blp_publish(&a, mem[k], s.ch[k], s.ub_sel[k], rf_mine, s.lix[k], s.best_h[k]);
             }
         }
     }
@@ -2241,10 +2285,10 @@ __host__ __device__ constexpr size_t uf_prologue_bytes(size_t T) { return ((T + 
 // members -- as cluster_kernel).  Same tables, same order as the clustering kernel's; workgroup `writer` files them in global memory
 // for the commit's statistics and the host.  Returns false for a void scan.
 // the prologue's one global round trip, issued at the very start of the kernel: status word, target count and -- speculatively, the first
-// UF_SPEC x 256 of them -- the parents (the solver's own scalar set-up, ~2 us of argument loads, runs while they are in flight)
+// UF_SPEC x 256 of them -- the parents (nothing else of the argument block is loaded in front of them: blp_uf_run)
 struct UfFetch { int s_over, nT; unsigned long long nif; unsigned long long pw[UF_SPEC]; };
-// what the prefetch needs of the argument block (the first arguments the kernel loads; everything else follows BEHIND the issue of these
-// loads, see blp_uf_kernel)
+// what the prefetch needs of the argument block (the first arguments the kernel loads; everything else is read where it is used,
+// see blp_uf_run)
 struct UfHead { const DevStatus* status; const int32_t* nT_dev; const unsigned long long* ni_flag; const unsigned long long* uf_parent; int uf_cap, uf_ovl; };
 // Every load is a VECTOR load through an index the compiler cannot see through (zero): a load it knows to be uniform becomes
 // global_load + s_waitcnt vmcnt(0) + v_readfirstlane on the spot -- three dependent round trips in front of the parents' one (seen in the ISA
@@ -2266,7 +2310,7 @@ __device__ __forceinline__ UfFetch uf_prefetch(const UfHead& a) {
     f.nif = a.uf_ovl ? nif : 0ull;
     return f;
 }
-__device__ __forceinline__ bool uf_prologue(const BlpArgs& a, const UfFetch& fe, unsigned char* lds, UfPersist* ps, const int bx, const int gx, int& my_t_out, TgtPre& pre_out) {
+template <typename AT> __device__ __forceinline__ bool uf_prologue(AT* ap, const UfFetch& fe, unsigned char* lds, UfPersist* ps, const int bx, const int gx, int& my_t_out, TgtPre& pre_out) { AT& a = *ap;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #define UF_STAMP(k) do { if (a.dbg && tid == 0 && bx < 3900) a.dbg[32 + (size_t)bx * 16 + (k)] = wall_clock64(); } while (0)
     UF_STAMP(0);
@@ -2423,7 +2467,7 @@ __device__ __forceinline__ bool uf_prologue(const BlpArgs& a, const UfFetch& fe,
                 // that word's commit: the next scan's grow launch may be running already)
             }
             // slots beyond the table: "nobody" for the next scan's grow launch, whose grid is sized by the host's upper bound
-            if (a.rec0) for (int t = nT + tid; t < a.pub_ub; t += BLP_THREADS) __hip_atomic_store(&a.rec0[t], tgt_rec(a.pub_scan, 0, 0, 0, 0, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (BLP_HAS(rec0)) for (int t = nT + tid; t < a.pub_ub; t += BLP_THREADS) __hip_atomic_store(&a.rec0[t], tgt_rec(a.pub_scan, 0, 0, 0, 0, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (a.alloc_reset && tid >= 64 && tid < 64 + FG_REGIONS) a.alloc_reset[(tid - 64) * 32] = 0u;
         }
         if (bx < nMulti && tid < own_K) my_t = ms[hp[own_root] + tid];
@@ -2443,7 +2487,7 @@ __device__ __forceinline__ bool uf_prologue(const BlpArgs& a, const UfFetch& fe,
         if (lane < own_K) { my_t = ms[p0 + lane]; gmem[p0 + lane] = my_t; }
     }
     // member `tid` of the workgroup's first cluster: its record is on its way while the solver sets itself up
-    if (my_t >= 0) { pre_out = load_target(a, my_t); pre_out.lab = own_root; }
+    if (my_t >= 0) { pre_out = load_target(&a, my_t); pre_out.lab = own_root; }
     __threadfence_block();
     __syncthreads();
     UF_STAMP(7);
@@ -2451,10 +2495,10 @@ __device__ __forceinline__ bool uf_prologue(const BlpArgs& a, const UfFetch& fe,
     return true;
 }
 
-template <bool UF> __device__ __forceinline__ void blp_singles(const BlpArgs& a, const int bx, const int gx, const int nSingle, const UfPersist* ps = nullptr);
-__device__ __forceinline__ void blp_stamp_begin(const BlpArgs& a, int bx);
-template <bool UF = false>
-__device__ __forceinline__ void blp_body(const BlpArgs& a, unsigned char* lds, const int bx, const int gx, UfPersist* ps = nullptr, const UfFetch* fe = nullptr) {      // workgroup bx of gx
+template <bool UF, typename AT> __device__ __forceinline__ void blp_singles(AT* ap, const int bx, const int gx, const int nSingle, const UfPersist* ps = nullptr);
+template <typename AT> __device__ __forceinline__ void blp_stamp_begin(AT* ap, int bx);
+template <bool UF = false, typename AT>
+__device__ __forceinline__ void blp_body(AT* ap, unsigned char* lds, const int bx, const int gx, UfPersist* ps = nullptr, const UfFetch* fe = nullptr) { AT& a = *ap;      // workgroup bx of gx
     unsigned long long* uw = reinterpret_cast<unsigned long long*>(lds);           // [cap_uw]
     Red* red = reinterpret_cast<Red*>(lds + (size_t)a.cap_uw * 8);                   // sizeof(Red) padded to RED_SLOT
     if (!UF && a.dbg && threadIdx.x == 0 && bx < 3900) a.dbg[32 + (size_t)bx * 16 + 12] = wall_clock64();
@@ -2487,10 +2531,10 @@ __device__ __forceinline__ void blp_body(const BlpArgs& a, unsigned char* lds, c
         Team tm = Team(0, 1, nullptr);
         if (UF && stage == -1) {
             // clusters from the grow launch's union-find: the tables first (INSIDE the staged loop: what the compiler hoists in front of the
-            // loop -- the solver's argument loads and address arithmetic, ~2 us -- then runs while the parents are on their way)
+            // loop -- the solver's loop-invariant arithmetic -- then runs while the parents are on their way)
             stage = 0;
-            if (!uf_prologue(a, *fe, lds, ps, bx, gx, my_t, my_pre_v)) return;      // (void scan)
-            blp_stamp_begin(a, bx);
+            if (!uf_prologue(&a, *fe, lds, ps, bx, gx, my_t, my_pre_v)) return;      // (void scan)
+            blp_stamp_begin(&a, bx);
             if (a.dbg && threadIdx.x == 0 && bx < 3900) a.dbg[32 + (size_t)bx * 16 + 12] = wall_clock64();
             nMulti = ps->nMulti; nSingle = ps->nSingle;
             teams_on = a.team_list && a.tier != 1 && (xteams || (a.shard_n <= 1 && gx > nMulti));
@@ -2500,7 +2544,7 @@ __device__ __forceinline__ void blp_body(const BlpArgs& a, unsigned char* lds, c
         } else if (stage == 0) {
             if (own_i >= nMulti) { stage = 1; continue; }
             if (UF) { cr = ps->own[own_q]; mt = own_q == 0 ? my_t : -1; ++own_q; }
-            else cr = cl_ref(a, work[own_i]);
+            else cr = cl_ref(&a, work[own_i]);
             own_i += gx;
             if (nTeam > 0 && cr.K >= TEAM_MIN_K)
                 for (int q = 0; q < nTeam; ++q) if ((UF ? ps->team[q].c : a.team_list[q]) == cr.c) ti = q;
@@ -2511,7 +2555,7 @@ __device__ __forceinline__ void blp_body(const BlpArgs& a, unsigned char* lds, c
             else ti = -1;
         } else if (stage == 1) {
             stage = 2;
-            blp_singles<UF>(a, bx, gx, nSingle, ps);
+            blp_singles<UF>(&a, bx, gx, nSingle, ps);
             continue;
         } else {
             stage = 3;
@@ -2520,17 +2564,17 @@ __device__ __forceinline__ void blp_body(const BlpArgs& a, unsigned char* lds, c
             ti = j % nTeam;
             if (q >= team_W(ti)) break;
             __syncthreads();      // (the wavefronts of this workgroup are done with the single-target clusters)
-            cr = UF ? ps->team[ti] : cl_ref(a, a.team_list[ti]);
+            cr = UF ? ps->team[ti] : cl_ref(&a, a.team_list[ti]);
             tm = (xteams && cr.K <= TEAM_SEL) ? Team(q, team_W(ti), &a.team_state[ti].gub, q * a.shard_n + a.shard_i, team_W(ti) * a.shard_n) : Team(q, team_W(ti), &a.team_state[ti].gub);
         }
         if (a.dbg && threadIdx.x == 0 && bx < 3900 && stage == 0) a.dbg[32 + (size_t)bx * 16 + 13] = wall_clock64();
-        solve_cluster(a, cr, uw, red, lds + (size_t)a.cap_uw * 8 + RED_SLOT, tm, ti, mt, mt >= 0 ? my_pre : nullptr, bx);
+        solve_cluster(&a, cr, uw, red, lds + (size_t)a.cap_uw * 8 + RED_SLOT, tm, ti, mt, mt >= 0 ? my_pre : nullptr, bx);
     }
 }
 
 // targets alone in their cluster: one wavefront each, dealt out from the END of the grid (the workgroups without an ILP)
-template <bool UF>
-__device__ __forceinline__ void blp_singles(const BlpArgs& a, const int bx, const int gx, const int nSingle, const UfPersist* ps) {
+template <bool UF, typename AT>
+__device__ __forceinline__ void blp_singles(AT* ap, const int bx, const int gx, const int nSingle, const UfPersist* ps) { AT& a = *ap;
     // targets alone in their cluster: min cumulativeNLLR, `<=` => the LAST minimal leaf wins (pyTarget.py:449)
     const int lane = threadIdx.x & 63;
     const int gw = (gx - 1 - bx) * (BLP_THREADS / 64) + (threadIdx.x >> 6);
@@ -2540,7 +2584,7 @@ __device__ __forceinline__ void blp_singles(const BlpArgs& a, const int bx, cons
         if (a.shard_n > 1 && t % a.shard_n != a.shard_i) continue;
         TgtPre pre = {};
         int cb, ce;
-        if (a.t_alive) { pre = load_target(a, t); if (UF) pre.lab = t; cb = pre.cb; ce = pre.ce; }
+        if (BLP_HAS(t_alive)) { pre = load_target(&a, t); if (UF) pre.lab = t; cb = pre.cb; ce = pre.ce; }
         else { cb = a.tchild[t]; ce = a.tcend[t]; }
         double bv = DINF;
         int bi = -1;
@@ -2549,7 +2593,7 @@ __device__ __forceinline__ void blp_singles(const BlpArgs& a, const int bx, cons
             if (a.skip_dead && (a.flags[h] & F_DEAD)) continue;      // (fused away by similar-state pruning)
             if (bi < 0 || v <= bv) { bv = v; bi = h; }
         }
-        const int va0 = a.t_alive ? sweep_prefetch(a, pre.j, cb, ce, lane) : -1;
+        const int va0 = BLP_HAS(t_alive) ? sweep_prefetch(&a, pre.j, cb, ce, lane) : -1;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const double ov = __shfl_xor(bv, o);
@@ -2557,10 +2601,10 @@ __device__ __forceinline__ void blp_singles(const BlpArgs& a, const int bx, cons
             if (oi >= 0 && (bi < 0 || ov < bv || (ov == bv && oi > bi))) { bv = ov; bi = oi; }
         }
         if (lane == 0) { a.sel[t] = bi; if (a.sel_rel) a.sel_rel[t] = bi - cb; }
-        if (a.t_alive) {      // wave-uniform: every lane evaluates the (broadcast) look-ups, lane 0 stores
+        if (BLP_HAS(t_alive)) {      // wave-uniform: every lane evaluates the (broadcast) look-ups, lane 0 stores
             int rf = 0;
-            const int key = finish_target(a, t, bi, pre, lane == 0, &rf);
-            sweep_survivors(a, t, pre.j, cb, ce, key, va0, lane, rf);
+            const int key = finish_target(&a, t, bi, pre, lane == 0, &rf);
+            sweep_survivors(&a, t, pre.j, cb, ce, key, va0, lane, rf);
         }
     }
 }
@@ -2574,7 +2618,7 @@ __device__ __forceinline__ void blp_singles(const BlpArgs& a, const int bx, cons
 // narrow launch (BlpArgs::big_list).  The 155 KB workgroups, one per CU, then carry the few clusters that need them instead of every
 // cluster of every sector.  Results are the full solver's: same minimisers, same tie-break, status CERTIFIED after 0 rounds.
 constexpr int LIGHT_MAXK = 8;
-__device__ __forceinline__ void blp_light(const BlpArgs& a, const int bx, const int gx, const int nMulti) {
+template <typename AT> __device__ __forceinline__ void blp_light(AT* ap, const int bx, const int gx, const int nMulti) { AT& a = *ap;
     const int lane = threadIdx.x & 63;
     const int gw = bx * (BLP_THREADS / 64) + (threadIdx.x >> 6), nw = gx * (BLP_THREADS / 64);
     for (int i = gw; i < nMulti; i += nw) {
@@ -2586,7 +2630,7 @@ __device__ __forceinline__ void blp_light(const BlpArgs& a, const int bx, const 
         }
         // lane k < K holds member k: its target record first (one round trip for all members) ...
         const int tk = a.cl_members[p0 + (lane < K ? lane : 0)];
-        const TgtPre pre = load_target(a, tk);
+        const TgtPre pre = load_target(&a, tk);
         // ... then every member's cheapest column: the first 64 columns of all members in ONE batch of loads (a member has ~55), the
         // rest in a loop; (value, lowest index) like compute_minimisers
         double v[LIGHT_MAXK];
@@ -2627,7 +2671,7 @@ __device__ __forceinline__ void blp_light(const BlpArgs& a, const int bx, const 
 #pragma unroll
         for (int k = 0; k < LIGHT_MAXK; ++k) {
             const int jk = __shfl(pre.j, k < K ? k : 0);
-            va[k] = (k < K) ? sweep_prefetch(a, jk, cbk[k], cek[k], lane) : -1;
+            va[k] = (k < K) ? sweep_prefetch(&a, jk, cbk[k], cek[k], lane) : -1;
         }
         bool clash = false;
         for (int q = 0; q < K * 8; ++q) {
@@ -2644,56 +2688,56 @@ __device__ __forceinline__ void blp_light(const BlpArgs& a, const int bx, const 
         if (lane < K) {
             a.sel[tk] = best;
             if (a.sel_rel) a.sel_rel[tk] = best - pre.cb;
-            key = finish_target(a, tk, best, pre, true);
+            key = finish_target(&a, tk, best, pre, true);
         }
 #pragma unroll
         for (int k = 0; k < LIGHT_MAXK; ++k) {
             if (k >= K) break;
-            sweep_survivors(a, __shfl(tk, k), __shfl(pre.j, k), cbk[k], cek[k], __shfl(key, k), va[k], lane);
+            sweep_survivors(&a, __shfl(tk, k), __shfl(pre.j, k), cbk[k], cek[k], __shfl(key, k), va[k], lane);
         }
         if (lane == 0) { a.cl_status[c] = MHT_BLP_CERTIFIED; a.cl_iters[c] = 0; a.cl_nodes[c] = 0; }
     }
 }
 
 // stage stamps of the scan (DevStatus::t, forest only): [2] = start of the first ILP launch, [4] = end of the last ILP workgroup
-__device__ __forceinline__ void blp_stamp_begin(const BlpArgs& a, int bx) {
-    if (a.status && bx == 0 && threadIdx.x == 0) {
+template <typename AT> __device__ __forceinline__ void blp_stamp_begin(AT* ap, int bx) { AT& a = *ap;
+    if (BLP_HAS(status) && bx == 0 && threadIdx.x == 0) {
         DevStatus* st = const_cast<DevStatus*>(a.status);
         if (st->t[2] == 0) st->t[2] = wall_clock64();
     }
 }
-__device__ __forceinline__ void blp_stamp_end(const BlpArgs& a) {
-    if (a.status && threadIdx.x == 0) atomicMax(&const_cast<DevStatus*>(a.status)->t[4], (unsigned long long)wall_clock64());
+template <typename AT> __device__ __forceinline__ void blp_stamp_end(AT* ap) { AT& a = *ap;
+    if (BLP_HAS(status) && threadIdx.x == 0) atomicMax(&const_cast<DevStatus*>(a.status)->t[4], (unsigned long long)wall_clock64());
 }
 
 __global__ __launch_bounds__(BLP_THREADS) void blp_kernel(const BlpArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     if (a.dbg && threadIdx.x == 0 && blockIdx.x < 3900) a.dbg[32 + (size_t)blockIdx.x * 16] = wall_clock64();
-    blp_stamp_begin(a, blockIdx.x);
-    blp_body(a, lds, blockIdx.x, gridDim.x);
-    blp_stamp_end(a);
+    blp_stamp_begin(&a, blockIdx.x);
+    blp_body(&a, lds, blockIdx.x, gridDim.x);
+    blp_stamp_end(&a);
     if (a.dbg && threadIdx.x == 0 && blockIdx.x < 3900) a.dbg[32 + (size_t)blockIdx.x * 16 + 15] = wall_clock64();
 }
 // clusters from the grow launch's union-find: every workgroup derives the cluster tables for itself first (uf_prologue); no cluster kernel
-__global__ __launch_bounds__(BLP_THREADS) void blp_uf_kernel(const BlpArgs a_in) {
+// AT = KBlpArgs (every caller) or KBlpArgsPlain (a plain forest's scans: launch_blp)
+template <typename AT> __device__ __forceinline__ void blp_uf_run(const UfHead& head) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    // The prologue's round trip leaves FIRST, on the six arguments it needs.  The other ~200 argument words (which the compiler loads in
-    // ~30 dependent rounds of s_load + spill to VGPR lanes at the kernel's entry, ~2-3 us) are read through a pointer it cannot see
-    // through, i.e. behind the issue of those loads: the two overlap instead of adding up.
-    const UfFetch fe = uf_prefetch(UfHead{a_in.status, a_in.nT_dev, a_in.ni_flag, a_in.uf_parent, a_in.uf_cap, a_in.uf_ovl});
-    typedef const __attribute__((address_space(4))) BlpArgs* KArgP;
-    KArgP kp = (KArgP)__builtin_amdgcn_kernarg_segment_ptr();      // (the argument block is the kernel's only argument: offset 0)
+    const unsigned long long t_first = wall_clock64();      // (development: the kernel's first instruction, kept in a register until the block's dbg pointer is read)
+    // The prologue's round trip leaves FIRST, on the six arguments it needs (the kernel's by-value parameter: loads at offsets the compiler
+    // knows).  Everything else is read from the argument segment where it is used, through a pointer the compiler cannot see through: no
+    // argument is loaded in front of the issue of those loads, none is carried from one phase of the solver into the next.
+    const UfFetch fe = uf_prefetch(head);
+    AT* kp = (AT*)__builtin_amdgcn_kernarg_segment_ptr();      // (the argument block is the kernel's only argument: offset 0)
     asm volatile("" : "+s"(kp) : : "memory");
-    BlpArgs a;
-    __builtin_memcpy(&a, kp, sizeof(BlpArgs));
+    AT& a = *kp;
     UfPersist* ps = reinterpret_cast<UfPersist*>(lds + a.uf_lds_off);
-    if (a.status && blockIdx.x == 0 && threadIdx.x == 0) const_cast<DevStatus*>(a.status)->t[1] = wall_clock64();      // stage stamp: clustering starts
+    if (BLP_HAS(status) && blockIdx.x == 0 && threadIdx.x == 0) const_cast<DevStatus*>(a.status)->t[1] = wall_clock64();      // stage stamp: clustering starts
     // (this launch is ordered behind the scan's grow launch: whoever reads this word -- the scan's initiator on its own queue -- knows that launch is complete)
-    if (a.begun && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.begun, (unsigned long long)a.pub_scan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (BLP_HAS(begun) && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.begun, (unsigned long long)a.pub_scan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int gx = (int)gridDim.x, pb = (int)blockIdx.x, bx = pb;
-    blp_body<true>(a, lds, bx, gx, ps, &fe);
-    if (!fe.s_over) blp_stamp_end(a);
-    if (a.blp_done) {
+    blp_body<true>(&a, lds, bx, gx, ps, &fe);
+    if (!fe.s_over) blp_stamp_end(&a);
+    if (BLP_HAS(blp_done)) {
         // the next scan's grow launch may be running: its commit waits until every workgroup of this launch has released what it wrote
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -2702,7 +2746,17 @@ __global__ __launch_bounds__(BLP_THREADS) void blp_uf_kernel(const BlpArgs a_in)
             atomicAdd(a.blp_done, 1ull);
         }
     }
-    if (a.dbg && threadIdx.x == 0 && bx < 3900) { a.dbg[32 + (size_t)bx * 16 + 15] = wall_clock64(); a.dbg[32 + (size_t)bx * 16 + 14] = ((unsigned long long)pb << 8) | (unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7); }
+    // [14]: the low 24 bits of the first instruction's time (10 ns ticks) | workgroup | XCC
+    if (a.dbg && threadIdx.x == 0 && bx < 3900) {
+        a.dbg[32 + (size_t)bx * 16 + 15] = wall_clock64();
+        a.dbg[32 + (size_t)bx * 16 + 14] = ((t_first & 0xffffffull) << 40) | ((unsigned long long)pb << 8) | (unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7);
+    }
+}
+__global__ __launch_bounds__(BLP_THREADS) void blp_uf_kernel(const BlpArgs a_in) {
+    blp_uf_run<KBlpArgs>(UfHead{a_in.status, a_in.nT_dev, a_in.ni_flag, a_in.uf_parent, a_in.uf_cap, a_in.uf_ovl});
+}
+__global__ __launch_bounds__(BLP_THREADS) void blp_uf_kernel_plain(const BlpArgs a_in) {
+    blp_uf_run<KBlpArgsPlain>(UfHead{a_in.status, a_in.nT_dev, a_in.ni_flag, a_in.uf_parent, a_in.uf_cap, a_in.uf_ovl});
 }
 // a group of sectors per launch, argument blocks read from HBM (written once, at group creation).  Workgroups are dealt out
 // sector-interleaved in dispatch order (blockIdx.x fastest): the first n * nMulti workgroups to reach the machine are the ones that
@@ -2714,9 +2768,9 @@ __global__ __launch_bounds__(BLP_THREADS) void blp_batch_kernel(const PBatch av)
     const int n = gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
     const int sector = lin % n, bx = lin / n;
     load_args(a, static_cast<const BlpArgs*>(av.p[sector]));
-    blp_stamp_begin(a, bx);
-    blp_body(a, lds, bx, gridDim.x);
-    blp_stamp_end(a);
+    blp_stamp_begin(&a, bx);
+    blp_body(&a, lds, bx, gridDim.x);
+    blp_stamp_end(&a);
 }
 
 // the light pass of a group of sectors (no dynamic LDS: many workgroups per CU), followed by blp_batch_kernel on tier-2 argument blocks
@@ -2725,12 +2779,12 @@ __global__ __launch_bounds__(BLP_THREADS) void blp_light_batch_kernel(const PBat
     const int n = gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
     const int sector = lin % n, bx = lin / n;
     load_args(a, static_cast<const BlpArgs*>(av.p[sector]));
-    blp_stamp_begin(a, bx);
+    blp_stamp_begin(&a, bx);
     if (!(a.status && a.status->overflow)) {
-        blp_light(a, bx, gridDim.x, a.counts[1]);
-        blp_singles<false>(a, bx, gridDim.x, a.counts[2]);
+        blp_light(&a, bx, gridDim.x, a.counts[1]);
+        blp_singles<false>(&a, bx, gridDim.x, a.counts[2]);
     }
-    blp_stamp_end(a);
+    blp_stamp_end(&a);
 }
 int launch_blp_light_batch(mht_ctx* ctx, const PBatch& av, int n_sectors, int grid_x) {
     return launch_kernel(ctx, K_BLP_LIGHT_BATCH, blp_light_batch_kernel, dim3(grid_x, n_sectors), dim3(BLP_THREADS), 0, false, av);
@@ -2748,7 +2802,7 @@ __global__ __launch_bounds__(TEAM_SEL) void shard_team_resolve_kernel(const BlpA
     if (a.status && a.status->overflow) return;
     const int ti = blockIdx.x;
     if (ti >= a.counts[5]) return;
-    const ClRef cr = cl_ref(a, a.team_list[ti]);
+    const ClRef cr = cl_ref(&a, a.team_list[ti]);
     int best = -1;
     unsigned long long bk = ~0ull;
     for (int d = 0; d < shard_n; ++d) {      // (uniform)
@@ -2772,14 +2826,14 @@ __global__ __launch_bounds__(BLP_THREADS) void blp_epilogue_kernel(const BlpArgs
     if (a.status && a.status->overflow) return;
     const int nT = *nT_dev, lane = threadIdx.x & 63;
     for (int t = blockIdx.x * (BLP_THREADS / 64) + (threadIdx.x >> 6); t < nT; t += gridDim.x * (BLP_THREADS / 64)) {
-        const TgtPre pre = load_target(a, t);
+        const TgtPre pre = load_target(&a, t);
         const int s = pre.cb + a.sel_rel[t];
         if (lane == 0) a.sel[t] = s;
-        const int va0 = sweep_prefetch(a, pre.j, pre.cb, pre.ce, lane);
-        const int key = finish_target(a, t, s, pre, lane == 0);
-        sweep_survivors(a, t, pre.j, pre.cb, pre.ce, key, va0, lane);
+        const int va0 = sweep_prefetch(&a, pre.j, pre.cb, pre.ce, lane);
+        const int key = finish_target(&a, t, s, pre, lane == 0);
+        sweep_survivors(&a, t, pre.j, pre.cb, pre.ce, key, va0, lane);
     }
-    blp_stamp_end(a);
+    blp_stamp_end(&a);
 }
 
 int launch_blp_epilogue(mht_ctx* ctx, const BlpArgs& a, const int32_t* nT_dev, int n_targets_ub) {
@@ -2820,7 +2874,9 @@ bool blp_uf_fits(int Tcap, int n_mnodes) {
     return Tcap <= 8192 && (((lds > pro ? lds : pro) + 15) & ~(size_t)15) + BLP_UF_PERSIST <= 158 * 1024;
 }
 
-int launch_blp(mht_ctx* ctx, const BlpArgs& a, int grid) {
+// force_generic: blp_uf_kernel also where the block would do for the plain instance (MHT_BLP_GENERIC=1); instance (or null): which one
+// the launch used -- BLP_INST_*
+int launch_blp(mht_ctx* ctx, const BlpArgs& a, int grid, bool force_generic, int* instance) {
     BlpArgs b = a;
     const size_t lds = blp_set_tier(b, 0);
     if (lds > 158 * 1024) {
@@ -2836,8 +2892,12 @@ int launch_blp(mht_ctx* ctx, const BlpArgs& a, int grid) {
             set_error("blp: the union-find prologue of %d targets does not fit the launch's LDS (%zu bytes)", b.uf_cap, lds_uf);
             return MHT_E_CAPACITY;
         }
+        const bool plain = !force_generic && blp_is_plain(b);
+        if (instance) *instance = plain ? BLP_INST_UF_PLAIN : BLP_INST_UF;
+        if (plain) return launch_kernel(ctx, K_BLP_UF_PLAIN, blp_uf_kernel_plain, dim3(grid), dim3(BLP_THREADS), lds_uf, false, b);
         return launch_kernel(ctx, K_BLP_UF, blp_uf_kernel, dim3(grid), dim3(BLP_THREADS), lds_uf, false, b);
     }
+    if (instance) *instance = BLP_INST_TABLES;
     return launch_kernel(ctx, K_BLP, blp_kernel, dim3(grid), dim3(BLP_THREADS), lds, false, b);
 }
 

@@ -95,7 +95,7 @@ struct Forest;
 // follow K_FGROW in table order.
 enum FgFamily : int { FG_PLAIN, FG_WAVE, FG_ADM, FG_AIS, FG_CT, FG_BATCH, FG_BATCH_WAVE, FG_FAMILIES };
 enum KernelSlot : int {
-    K_GATE, K_CLUSTER, K_CLUSTER_INIT, K_CLUSTER_BIG, K_CLUSTER_BATCH, K_BLP, K_BLP_UF, K_BLP_BATCH, K_BLP_LIGHT_BATCH,
+    K_GATE, K_CLUSTER, K_CLUSTER_INIT, K_CLUSTER_BIG, K_CLUSTER_BATCH, K_BLP, K_BLP_UF, K_BLP_UF_PLAIN, K_BLP_BATCH, K_BLP_LIGHT_BATCH,
     K_SMOOTH_EM4, K_SMOOTH_EM6,      // (no LDS: the slots only route mht_smooth_tracks_em through launch_kernel)
     K_SMOOTH_SCORE,                  // (no LDS either: every kernel of mht_smooth_score.hip goes through launch_kernel under this one)
     K_GOSPA,                         // gospa_kernel (mht_gospa.hip): the search tables of the launch's largest step, 56 KB at 2048 x 2048

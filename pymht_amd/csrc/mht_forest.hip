@@ -61,6 +61,7 @@ struct Switches {
     bool adm_fuse = env_flag("MHT_ADM_FUSE", true);               // 0: admission in a launch of its own behind every scan
     bool no_uf = env_flag("MHT_NO_UF", false);                    // 1: the clustering kernel on every scan (Forest::uf_ok)
     bool no_overlap = env_flag("MHT_NO_OVERLAP", false);          // 1: no any-order grow launches (Forest::ovl_ok)
+    bool blp_generic = env_flag("MHT_BLP_GENERIC", false);        // 1: every ILP launch as the generic blp_uf_kernel, also where the plain instance would do (launch_blp)
     // (rocprofv3 --pmc runs ONE kernel at a time across all queues, in the order the queues happen to be served: a launch that waits for a
     // launch on another queue never sees it start.  Under counter collection the initiator stays on the ctx stream.)
     bool serial_prof = env_flag("ROCPROF_COUNTER_COLLECTION", false);      // no launch may wait for a launch on another queue (the staging goes by event too)
@@ -377,7 +378,7 @@ struct Forest {
     unsigned long long z_tag_step = 0;      // != 0: the scan being stepped was staged without an event wait on the ctx stream (FDyn::z_tag); z_wait_slot: its slot
     int z_wait_slot = -1;
     int init_flag_scan = 0;      // last scan whose initiator posts FCounts::init_flag
-    unsigned long long* rec0 = nullptr; int pub_scan = 0; unsigned long long blp_done_total = 0; bool ovl_ok = true; int ovl_launches = 0;
+    unsigned long long* rec0 = nullptr; int pub_scan = 0; unsigned long long blp_done_total = 0; bool ovl_ok = true; int ovl_launches = 0; int blp_instance = 0;      // blp_instance: BlpInstance of the last ILP launch
     int32_t* cl_gtab = nullptr; bool cluster_big = false;      // the clustering tables in HBM when they do not fit LDS (mht_cluster.hip: cluster_big_kernel)
     int32_t* team_list; TeamState* team_state2[2]; TeamResult* team_res;      // (team_state2: by scan parity)      // branch-and-bound teams (mht_blp.hip; Switches::teams)
     double* u; int32_t* usage; int32_t* mark;
@@ -1479,7 +1480,7 @@ static int step_solve(mht_ctx* ctx, Forest* f, const StepPlan& pl, const float* 
         b.pub_ub = f->nT_ub_step < 1 ? 1 : (f->nT_ub_step < f->Tcap ? f->nT_ub_step : f->Tcap);      // (the next grow launch has one target workgroup at least)
     }
     hp_mark(6);
-    MHT_STEP_CHECK(launch_blp(ctx, b, grid));
+    MHT_STEP_CHECK(launch_blp(ctx, b, grid, f->sw.blp_generic, &f->blp_instance));
     hp_mark(7);
     if (pl.use_uf) { f->pub_scan = pl.s; f->blp_done_total += (unsigned long long)grid; }
     if (pl.use_uf && init) MHT_STEP_CHECK(step_initiator(ctx, f, pl, z, M, init, now));
@@ -1572,7 +1573,7 @@ static int sharded_begin_impl(mht_ctx* ctx, const float* z, int32_t M, int32_t s
             b.shard_team = sel_rel + f->Tcap;
             MHT_STEP_HIP(hipMemsetAsync(b.shard_team, 0xff, (size_t)shard_n * TEAM_MAX * XT_WORDS * sizeof(int32_t), ctx->stream));
         }
-        MHT_STEP_CHECK(launch_blp(ctx, b, blp_full_grid(f, 2)));
+        MHT_STEP_CHECK(launch_blp(ctx, b, blp_full_grid(f, 2), f->sw.blp_generic, &f->blp_instance));
     }
     f->shard_open = true; f->shard_plan_s = pl.s; f->shard_plan_W = pl.W; f->shard_M = M; f->shard_xn = (n_words > 0 && shard_n > 1) ? shard_n : 0;
     return MHT_OK;
@@ -2372,8 +2373,15 @@ extern "C" int mht_forest_debug_read(mht_ctx* ctx, const char* name, void* host,
         static_cast<int32_t*>(host)[0] = f->uf_scans; static_cast<int32_t*>(host)[1] = f->ovl_launches;
         return MHT_OK;
     }
+    if (!strcmp(name, "blp_instance")) {      // (host side: which kernel the last ILP launch ran as -- mht_kernels.h: BlpInstance)
+        MHT_REQUIRE(bytes == 4, "mht_forest_debug_read: 'blp_instance' is one int32");
+        *static_cast<int32_t*>(host) = f->blp_instance;
+        return MHT_OK;
+    }
     if (!strcmp(name, "status2")) { src = f->status2; avail = 2 * sizeof(DevStatus); }
     else if (!strcmp(name, "init_dbg")) { src = f->init_dbg; avail = 64; }
+    else if (!strcmp(name, "sel")) { src = f->sel; avail = T * 4; }                  // selected child per target of the last scan
+    else if (!strcmp(name, "t_label")) { src = f->t_label; avail = T * 4; }          // smallest member of every target's cluster
     else if (!strcmp(name, "cl_status")) { src = f->cl_status; avail = T * 4; }
     else if (!strcmp(name, "cl_iters")) { src = f->cl_iters; avail = T * 4; }
     else if (!strcmp(name, "cl_nodes")) { src = f->cl_nodes; avail = T * 4; }

@@ -367,7 +367,10 @@ size_t cluster_lds_bytes(int Tcap, int n_mnodes);
 int cluster_elds(int Tcap, int n_mnodes);
 bool cluster_fits_lds(int Tcap, int n_mnodes);
 size_t cluster_big_ints(int Tcap, int n_mnodes);
-int launch_blp(mht_ctx* ctx, const BlpArgs& a, int grid);
+// which kernel an ILP launch ran as: blp_kernel (cluster tables from the clustering kernel), blp_uf_kernel (generic), blp_uf_kernel_plain
+// (a plain forest's switches compiled in, mht_blp.hip: BlpArgsPlain)
+enum BlpInstance : int { BLP_INST_NONE = 0, BLP_INST_TABLES = 1, BLP_INST_UF = 2, BLP_INST_UF_PLAIN = 3 };
+int launch_blp(mht_ctx* ctx, const BlpArgs& a, int grid, bool force_generic = false, int* instance = nullptr);
 bool blp_uf_fits(int Tcap, int n_mnodes);
 int launch_blp_epilogue(mht_ctx* ctx, const BlpArgs& a, const int32_t* nT_dev, int n_targets_ub);
 int launch_shard_team_resolve(mht_ctx* ctx, const BlpArgs& a, int shard_n);
