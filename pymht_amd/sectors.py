@@ -14,7 +14,7 @@ from . import _lib
 
 class SectorGroup:
     """trackers: `pymht_amd.tracker.Tracker` objects on the same device; the radar-only ones (which share the batched launches) with
-    the same maxTargets / maxNodes / maxMeasurements / N."""
+    the same state dimension (ValueError otherwise) and the same maxTargets / maxNodes / maxMeasurements / N."""
 
     def __init__(self, trackers):
         self.trackers = list(trackers)
@@ -25,7 +25,12 @@ class SectorGroup:
         self._own = [bool(getattr(t, "_ais", False)) or getattr(getattr(t, "_model_mod", None), "transition", None) == "ct" for t in self.trackers]
         self._batched = [i for i, o in enumerate(self._own) if not o]
         n = len(self._batched)
-        self._lib = self.trackers[self._batched[0] if n else 0]._lib      # (four- and six-state members load different libraries)
+        # the batched launch set is one library's: a four-state and a six-state forest are objects of different builds (libmht_amd.so /
+        # libmht_amd6.so, other layouts behind the same handle type), and mht_group_create cannot tell them apart
+        if len({t.nx for t in (self.trackers[i] for i in self._batched)}) > 1:
+            raise ValueError("SectorGroup: the members that share the batched launches must have one state dimension (got nx = %s): "
+                             "make one group per state dimension" % sorted({self.trackers[i].nx for i in self._batched}))
+        self._lib =self.trackers[self._batched[0] if n else 0]._lib      # (four- and six-state members load different libraries)
         self._h = C.c_void_p()
         if n:
             handles = (C.c_void_p * n)(*[self.trackers[i]._ctx.handle for i in self._batched])

@@ -242,3 +242,229 @@ def run_case_ct(seed, max_leaves=2500, budget_s=15.0, similar=False):
         return True, desc, msg + ' L=%d ilp=%d %.1fs' % (st["L"], o.n_ilp, time.time() - t0)
     finally:
         trk.close()
+
+
+# ---- linear six-state forests (Tracker(pymht_amd.models.ca, ...)): the four-state forest's kernels at NX = 6 ------------------------------
+# The oracle runs FIRST and alone (oracle_run): it decides where a scene stops -- the leaf cap alone, no clock, so a scene is the same on
+# every host -- keeps what every scan has to look like, and counts what the scene exercises (its census).  tests/test_six_state_fuzz_cpu.py
+# asserts the census without a device; device_run steps a Tracker through the same scans against the record.
+CA_SEED0 = int(os.environ.get("MHT_FUZZ_SEED", "20000"))
+CA_PLAIN_SEEDS = [CA_SEED0 + 300000 + i for i in range(24)]
+CA_SIMILAR_SEEDS = [CA_SEED0 + 350000 + i for i in range(24)]
+CA_MAX_LEAVES = 1500
+SHARDED_SEED = 320017      # a plain-slice scene whose largest cluster has 34 targets
+VTAB_SCANS = 22        # the second switch of a 2 048-id table comes in front of scan 20; two more scans run on the third generation
+
+
+def ca_tails(seed, T):
+    """[ax, ay] per root from default_rng(seed + 4242): half of the targets exactly 0 (all G17 and cfg5 ever start from), the others N(0, 0.3) m/s^2."""
+    prng = np.random.default_rng(seed + 4242)
+    zero = prng.uniform(size=T) < 0.5
+    return np.where(zero[:, None], 0.0, prng.normal(0.0, 0.3, size=(T, 2)))
+
+
+def similar_draw(seed, similar, n_scans):
+    """pruneThreshold and the per-scan switch of similar-state pruning, drawn as run_case draws them."""
+    prng = np.random.default_rng(seed + 77)
+    thr = float(prng.choice([4.0, 6.0, 12.0])) if similar else 4
+    return thr, [bool(similar and prng.uniform() < 0.75) for _ in range(n_scans)]
+
+
+def scene_of(sc, N, eta2, thr, on, desc, model="ca", tails=None):
+    """A scene: scenario, window, gate, merge radius, the per-scan pruning switches and the roots of the model ([x4, ax, ay] for ca)."""
+    x0 = sc["x0"] if model == "pv" else np.concatenate([sc["x0"], np.zeros((len(sc["x0"]), 2)) if tails is None else tails], axis=1)
+    return dict(sc=sc, N=int(N), eta2=float(eta2), thr=thr, on=list(on), desc=desc, model=model, x0=x0)
+
+
+def ca_scene(seed, similar=False):
+    sc, N, eta2, desc = scenario_of(seed)
+    thr, on = similar_draw(seed, similar, len(sc["scans"]))
+    tails = ca_tails(seed, len(sc["x0"]))
+    return scene_of(sc, N, eta2, thr, on, desc + ' CA |a|max=%.2f' % float(np.abs(tails).max()) + (' similar thr=%.0f' % thr if similar else ''), tails=tails)
+
+
+# dense scenes that fuse large groups of hits (N, P_d, thr, lambda_phi, seed, T, radius): means over 3, 5, 6, 7 and more than 16 hits -- the
+# path of mht_similar.hip::fuse_group that inserts a covariance value, takes a pseudo-parent key and writes a gains row
+CRAFTED = {"A": (2, 0.95, 15.0, 1e-3, 23, 25, 250.0), "B": (3, 0.9, 25.0, 3e-3, 24, 12, 150.0), "C": (2, 0.9, 30.0, 4e-3, 25, 8, 120.0)}
+
+
+def crafted_scene(name, model="ca"):
+    """Zero acceleration tails, eta2 5.99, similar-state pruning on at EVERY scan (the runner's 0.75 draw would thin the large groups)."""
+    from pymht_amd.utils.scenario import make_scenario
+    N, P_d, thr, lam, seed, T, radius = CRAFTED[name]
+    sc = make_scenario(T=T, radius=radius, lambda_phi=lam, n_scans=10, P_d=P_d, seed=seed)
+    return scene_of(sc, N, 5.99, thr, [True] * 10, 'crafted %s (%s): T=%d r=%.0f lam=%.1e N=%d Pd=%.2f thr=%.0f' % (name, model, T, radius, lam, N, P_d, thr), model=model)
+
+
+LONG_WINDOWS = {8: dict(T=15, P_d=0.8, seed=31), 9: dict(T=10, P_d=0.85, seed=32)}
+
+
+def long_window_scene(N):
+    """Windows of 8 and 9 scans: path records of 16 ints, targets of more than 128 leaves."""
+    from pymht_amd.utils.scenario import make_scenario
+    p = LONG_WINDOWS[N]
+    sc = make_scenario(T=p["T"], radius=400.0, lambda_phi=1e-5, n_scans=12, P_d=p["P_d"], seed=p["seed"])
+    return scene_of(sc, N, 5.99, 4, [False] * 12, 'long window N=%d: T=%d Pd=%.2f' % (N, p["T"], p["P_d"]), tails=ca_tails(p["seed"], p["T"]))
+
+
+def vtab_scene(n_scans=VTAB_SCANS, T=12):
+    """A stream with cfg2's clutter density, detection probability and window (1e-4 per m^2, 0.9, N = 3) and pruning on six scans of seven.
+    It has 12 targets where cfg2 has 50: six-state covariances do not settle to a handful of float32 values as the four-state ones do (the
+    oracle meets ~120 new values per scan here, ~350 with 50 targets), and a generation of a 2 048-id table has to last R + 2 scans."""
+    from pymht_amd.utils.scenario import make_scenario
+    sc = make_scenario(T=T, radius=500.0, lambda_phi=1e-4, n_scans=n_scans, P_d=0.9, seed=5446)
+    return scene_of(sc, 3, 5.99, 4, [k % 7 != 5 for k in range(n_scans)], 'cfg2-like stream, %d targets, %d scans' % (T, n_scans), tails=ca_tails(5446, T))
+
+
+def sector_scenes():
+    """Two different scenes with one window (members of a group share the forest configuration): the first prunes on three scans of four."""
+    from pymht_amd.utils.scenario import make_scenario
+    a = make_scenario(T=40, radius=500.0, lambda_phi=6e-5, n_scans=10, P_d=0.85, seed=41)
+    b = make_scenario(T=30, radius=400.0, lambda_phi=4e-5, n_scans=10, P_d=0.9, seed=42)
+    return [scene_of(a, 3, 5.99, 7.5, [k % 4 != 1 for k in range(10)], 'sector 0', tails=ca_tails(41, 40)),
+            scene_of(b, 3, 5.99, 4, [False] * 10, 'sector 1', tails=ca_tails(42, 30))]
+
+
+def _model_of(scene):
+    from pymht_amd.models import pv, ca
+    return {"pv": pv, "ca": ca}[scene["model"]]
+
+
+def oracle_run(scene, max_leaves=None):
+    """The oracle alone over a scene.  Returns dict(accepted, scans=[per-scan record], census): the census holds the number of ILPs, the
+    largest cluster, the terminations, the largest L and the sizes of the fused groups (the number of hit children every call of
+    Node.prune_similar removed: the call is wrapped here and computes what it always does)."""
+    import mht_oracle as orc
+    from trace_util import oracle_rows
+    sc, model = scene["sc"], _model_of(scene)
+    nx = scene["x0"].shape[1]
+    o = orc.OracleTracker(sc["period"], sc["lambda_phi"], 1e-4, P_d=sc["P_d"], N=scene["N"], eta2=scene["eta2"], initiator=None,
+                          model=None if scene["model"] == "pv" else model)
+    acc = [o.initiate_target(sc["t0"], x.copy(), model.P0.copy(), status="preinitialized") for x in scene["x0"]]
+    groups, merged = [], []
+    plain = orc.Node.prune_similar
+
+    def counting(node, threshold):
+        before = len(node.kids)
+        plain(node, threshold)
+        if len(node.kids) != before:
+            groups.append(before - len(node.kids))
+            merged.append(node.kids[0])
+
+    census = dict(ilp=0, cluster=0, dead=0, L=0, groups=groups, scans=0, merged_leaves=0)
+    recs = []
+    orc.Node.prune_similar = counting
+    try:
+        for k, (z, t) in enumerate(zip(sc["scans"], sc["times"])):
+            if max_leaves is not None and k > 0 and recs[-1]["L"] > max_leaves:
+                break
+            del merged[:]
+            info = o.add_scan(float(t), z, prune_similar=scene["on"][k], prune_threshold=scene["thr"])
+            leaves = [l for r in o.targets for l in r.leaves()]
+            m_ids = set(id(n) for n in merged)
+            lb, sel = oracle_rows(leaves, nx), oracle_rows(o.track_nodes, nx)
+            recs.append(dict(L=info["L"], G=info["G"], unused=info["unused"].copy(), ids=[r.ID for r in o.targets], n_ilp=o.n_ilp,
+                             clusters=[np.asarray(c).copy() for c in o.clusters], sel=sel, leaves=lb,
+                             merged=np.array([id(l) in m_ids for l in leaves], dtype=bool)))
+            census["ilp"] += o.n_ilp
+            census["cluster"] = max([census["cluster"]] + [len(c) for c in o.clusters])
+            census["dead"] += len(info["dead"])
+            census["L"] = max(census["L"], info["L"])
+            census["merged_leaves"] += int(recs[-1]["merged"].sum())
+    finally:
+        orc.Node.prune_similar = plain
+    census["scans"] = len(recs)
+    census["groups"] = list(groups)
+    return dict(accepted=acc, scans=recs, census=census)
+
+
+def group_histogram(groups):
+    return {int(s): int(n) for s, n in zip(*np.unique(np.asarray(groups, dtype=np.int64), return_counts=True))}
+
+
+def _rows_close(a, b, rel):
+    """Every row within rel of its largest element (at least 1), as run_case_ct holds states and covariances; rel = 0: bit equality."""
+    from test_tracker_gpu import states_close
+    return states_close(a, np.asarray(b, dtype=np.float64), rel=rel)
+
+
+def device_run(scene, rec, streamed=False):
+    """A Tracker over the scans the oracle ran, against its record.  Looked at after every scan: L, G, unused measurements, target ids,
+    ILPs, selections, clusters member for member, leaf ids and measurement numbers exactly; states and covariances of ALL leaves (the
+    merged ones once more on their own) at FUZZ_REL, cumulative scores at SCORE_ATOL; no leaf carries flag 8.  streamed: nothing is looked
+    at in between -- the per-scan numbers come from the tracker's log, the rest is compared at the end.  Returns (ok, message)."""
+    from test_tracker_gpu import tracker_selected, SCORE_ATOL
+    from pymht_amd.tracker import Tracker
+    from pymht_amd.pyTarget import Target
+    from pymht_amd.utils.classDefinitions import MeasurementList
+    sc, model = scene["sc"], _model_of(scene)
+    nx = scene["x0"].shape[1]
+    trk = Tracker(model, sc["period"], sc["lambda_phi"], 1e-4, P_d=sc["P_d"], N=scene["N"], eta2=scene["eta2"], useInitiator=False, maxTargets=256,
+                  maxNodes=1 << 18, maxMeasurements=512, pruneThreshold=scene["thr"], logScanStats=streamed)
+    t0 = time.time()
+
+    def state_checks(r):
+        os_, ts = r["sel"], tracker_selected(trk, nx)
+        lb, tb = r["leaves"], trk.leafBatch()
+        same_leaves = np.array_equal(lb["ID"], tb["ID"]) and np.array_equal(lb["meas"], tb["meas"])
+        m = r["merged"]
+        return [("targets", r["ids"] == [q.ID for q in trk.__targetList__]),
+                ("selection", np.array_equal(os_["ID"], ts["ID"]) and np.array_equal(os_["meas"], ts["meas"])),
+                ("selected states", _rows_close(os_["x"], ts["x"], 1e-6) and np.allclose(os_["cnllr"], ts["cnllr"], rtol=0, atol=SCORE_ATOL)),
+                ("clusters", len(r["clusters"]) == len(trk.__clusterList__) and all(np.array_equal(a, np.asarray(b)) for a, b in zip(r["clusters"], trk.__clusterList__))),
+                ("leaves", same_leaves),
+                ("leaf states", same_leaves and _rows_close(lb["x"], tb["x"], FUZZ_REL)),
+                ("leaf covariances", same_leaves and _rows_close(lb["P"], tb["P"], FUZZ_REL)),
+                ("merged leaves' covariances", same_leaves and _rows_close(lb["P"][m], tb["P"][m], FUZZ_REL)),
+                ("leaf scores", same_leaves and np.allclose(lb["cnllr"], tb["cnllr"], rtol=0, atol=SCORE_ATOL)),
+                ("flag 8", not np.any(tb["flags"] & 8))]
+
+    try:
+        acc = []
+        for x in scene["x0"]:
+            n0 = trk.nTargets
+            trk.initiateTarget(Target(sc["t0"], None, x.copy(), model.P0, status="preinitialized"))
+            acc.append(trk.nTargets > n0)
+        if acc != rec["accepted"]:
+            return False, 'MISMATCH: the roots the device admits'
+        for k, r in enumerate(rec["scans"]):
+            trk.addMeasurementList(MeasurementList(float(sc["times"][k]), sc["scans"][k]), pruneSimilar=scene["on"][k])
+            if streamed:
+                continue
+            st = trk.lastScanStats
+            checks = [("gating", (st["L"], st["G"]) == (r["L"], r["G"])), ("unused", np.array_equal(st["unused"], r["unused"])),
+                      ("ilps", r["n_ilp"] == trk.nOptimSolved)] + state_checks(r)
+            if not all(c for _, c in checks):
+                return False, 'MISMATCH at scan %d: %s' % (k, ', '.join(n for n, c in checks if not c))
+        if streamed and rec["scans"]:
+            log = trk.scanStatsLog
+            checks = [("number of scans", len(log) == len(rec["scans"]))]
+            for k, (s, r) in enumerate(zip(log, rec["scans"])):
+                checks.append(("scan %d statistics" % k, (s["L"], s["G"], s["ilp"], s["nTargets"]) == (r["L"], r["G"], r["n_ilp"], len(r["ids"]))
+                               and np.array_equal(s["unused"], r["unused"])))
+            checks += state_checks(rec["scans"][-1])
+            if not all(c for _, c in checks):
+                return False, 'MISMATCH (streamed): %s' % ', '.join(n for n, c in checks if not c)
+        return True, '%s%d scans %.1fs' % ('streamed ' if streamed else '', len(rec["scans"]), time.time() - t0)
+    finally:
+        trk.close()
+
+
+def run_case_ca(seed, max_leaves=1500, similar=False, streamed=False):
+    """The linear six-state forest on scenario_of(seed) with random acceleration tails against the live oracle (oracle_run, device_run).
+    Returns (ok, description, message, census)."""
+    scene = ca_scene(seed, similar)
+    rec = oracle_run(scene, max_leaves)
+    ok, msg = device_run(scene, rec, streamed)
+    c = rec["census"]
+    return ok, scene["desc"], msg + ' L=%d ilp=%d cluster=%d dead=%d groups=%s' % (c["L"], c["ilp"], c["cluster"], c["dead"], group_histogram(c["groups"])), c
+
+
+def add_census(total, c):
+    """Census of a slice: sums of the ILPs and terminations, maxima of the cluster size and L, all group sizes."""
+    total["ilp"] = total.get("ilp", 0) + c["ilp"]
+    total["dead"] = total.get("dead", 0) + c["dead"]
+    total["cluster"] = max(total.get("cluster", 0), c["cluster"])
+    total["L"] = max(total.get("L", 0), c["L"])
+    total.setdefault("groups", []).extend(c["groups"])
+    return total
