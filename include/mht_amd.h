@@ -517,6 +517,34 @@ int mht_imm_smooth_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_t
 int mht_nees_nodes(mht_ctx* ctx, int32_t nx, int32_t n_tracks, int32_t L_max, int32_t D, const double* x, const double* P,
                    const double* truth, const uint8_t* present, double* out);
 
+/* mht_encounters: which tracks come close to each other, or to the own ship, within the next minutes, and how sure is that?  n entries
+ * at one common time -- one row of mht_filter_tracks' layout -- are propagated K steps of dt seconds with a linear model
+ * (x_k = Phi x_{k-1}, P_k = Phi P_{k-1} Phi' + Q, k = 0 the entries as they are), and for every pair (i, j) with i < first and
+ * i < j < n, the two taken as INDEPENDENT, d_k the difference of the positions and Sigma_k the sum of their 2 x 2 covariances:
+ *   tcpa, dcpa  the closest point of approach of the piecewise-linear path through d_0 .. d_K: its time (earliest) and distance.  The
+ *               exact CPA within the horizon for a constant-velocity model; the piecewise-linear figure for a constant-acceleration one
+ *   md2         min over k of d_k' Sigma_k^-1 d_k
+ *   pc, tpc     max over k of pc_k, the probability mass of N(d_k, Sigma_k) within the disc of radius R, and the time k dt of the
+ *               (earliest) maximum.  pc_k is DEFINED by a rule -- csrc/mht_encounter.h: the closed-form eigen-decomposition of Sigma_k,
+ *               a clip at 8 sigma along the narrow axis (beyond it pc_k is 0 exactly) and a 64-node Gauss-Legendre rule of exp and
+ *               erfc -- which is good to about 1e-6 absolute against the exact mass, not exact
+ *   nx     4 or 6, the state [x, y, vx, vy, ...];  K: 1 .. 64 steps;  dt > 0 seconds;  R > 0
+ *   n      entries;  first: 0 .. n.  first = n: all pairs;  first = 1 with the own ship as entry 0: the own ship against everyone
+ *   Phi, Q HOST [nx][nx] f64, row-major, for one step of dt (of Q the upper triangle is read)
+ *   x      dev [nx][n] f64;  P: dev [nx (nx + 1) / 2][n] f64, the packed upper triangle
+ *   out    dev [5][first][n] f64 out: tcpa, dcpa, md2, pc, tpc.  EVERY cell is written; the cells with j <= i are NaN
+ *   work   dev, at least mht_encounter_work_bytes(n, K) bytes (0 for n <= 0 or a K outside 1 .. 64): the propagated positions and
+ *          their covariances, 5 (K + 1) n doubles
+ * A NaN in an entry's x or P makes all five figures of its pairs NaN.  A Sigma_k that is not positive definite at some k makes pc, tpc
+ * and md2 of that pair NaN; tcpa and dcpa stay valid.  Cross-correlation between tracks is not modelled.
+ * Two launches (one entry per lane, then one cell per lane with j fastest).  Synchronises.
+ * MHT_E_INVALID: nx not 4 or 6, K outside 1 .. 64, R <= 0 or dt <= 0 (or NaN), first outside 0 .. n, a null array or a work buffer too
+ * small for a call that is not empty; nothing has then been launched or written.  n == 0 or first == 0 returns MHT_OK and launches
+ * nothing.  Exported by both builds. */
+size_t mht_encounter_work_bytes(int32_t n, int32_t K);
+int mht_encounters(mht_ctx* ctx, int32_t nx, int32_t n, int32_t first, int32_t K, double dt, double R, const double* Phi, const double* Q,
+                   const double* x, const double* P, double* out, void* work, size_t work_bytes);
+
 /* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
  * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);
  * with d_ij = sqrt(dx dx + dy dy) in float64 and only pairs with d_ij < c (strictly) assignable,

@@ -493,3 +493,97 @@ def nees_consistency(results, alpha=0.05):
                           "inside": np.array([None if not np.isfinite(v) else bool(a <= v <= b) for v, a, b in zip(m, slo, shi)], dtype=object)}
         out["dims"][dof] = fig
     return out
+
+
+# ---- encounters: who comes close to whom within the next minutes? ------------------------------------------------------------------
+ENCOUNTER_NAMES = ("tcpa", "dcpa", "md2", "pc", "tpc")      # the order of the seam's out [5][first][n]
+ENCOUNTER_MAX_STEPS = 64                                    # csrc/mht_encounter.h
+
+
+def encounter_model(model, dt):
+    """(nx, Phi(dt), Q(dt)) of a tracker's model module for `encounters`, in float64 -- the float32 matrices the model returns, widened.
+    A constant-turn model raises NotImplementedError: its transition depends on the state (models/ct.py), and it is not propagated
+    with Phi(T, 0) in its place."""
+    if getattr(model, "transition", None) == "ct":
+        raise NotImplementedError("encounters: the transition of model %r depends on the state (Phi(T, w) per hypothesis, models/ct.py); "
+                                  "the linear propagation does not apply" % getattr(model, "__name__", model))
+    nx = int(np.asarray(model.C_RADAR).shape[1])
+    if nx not in (4, 6):
+        raise ValueError("encounters: 4- or 6-state models (got %d states)" % nx)
+    widen = lambda m: np.ascontiguousarray(np.asarray(m, dtype=np.float32).astype(np.float64).reshape(nx, nx))
+    return nx, widen(model.Phi(float(dt))), widen(model.Q(float(dt)))
+
+
+def _encounter_empty(first, n):
+    return {k: np.full((first, n), np.nan) for k in ENCOUNTER_NAMES}
+
+
+def encounters(x, P, Phi, Q, steps, dt, radius, first=None, device=0, ctx=None):
+    """Which of n tracks come close to each other within the next steps * dt seconds, and how sure is that?
+
+    x, P       the entries at one common time: x [n, nx] (nx 4 or 6, the state [x, y, vx, vy, ...]) and P [n, nx, nx] symmetric (the
+               upper triangle is read) -- e.g. the last rows of `smoothing.filter_tracks`
+    Phi, Q     [nx, nx]: the linear model of ONE step of dt seconds (of Q the upper triangle is read)
+    steps, dt  1 .. 64 steps of dt > 0 seconds: the horizon is steps * dt
+    radius     the safety radius R > 0, in the units of the positions
+    first      None: all pairs.  Else 0 .. n: only the pairs (i, j) with i < first -- first=1 with the own ship as entry 0 gives the own
+               ship against everyone
+    device, ctx   the GPU ordinal, or an existing pymht_amd.device.Context (a Tracker's) to run on
+    ValueError for arguments that do not fit -- before any device is needed.  Fewer than two entries, or first=0, give empty
+    ([first, n], all NaN) arrays and no device call.
+    Returns a dict of float64 [first, n] arrays, NaN where j <= i; with d_k the difference of the two propagated positions
+    (x_k = Phi x_{k-1}, P_k = Phi P_{k-1} Phi' + Q) and Sigma_k the SUM of their position covariances -- the tracks are taken as
+    independent, cross-correlation between them is not modelled:
+        tcpa, dcpa   the closest point of approach of the piecewise-linear path through d_0 .. d_steps: its (earliest) time and its
+                     distance.  The exact CPA within the horizon for a constant-velocity model; for a constant-acceleration model the
+                     piecewise-linear figure
+        md2          the smallest d_k' Sigma_k^-1 d_k over the steps
+        pc, tpc      the largest probability over the steps that the two are within `radius` of each other, and the time k dt of the
+                     (earliest) largest.  pc_k is the mass of N(d_k, Sigma_k) inside the disc, BY A RULE (csrc/mht_encounter.h: closed-form
+                     eigen-decomposition, a clip at 8 sigma along the narrow axis beyond which pc_k is 0 exactly, a 64-node
+                     Gauss-Legendre rule): good to about 1e-6 absolute against the exact mass, not exact
+    A NaN in an entry makes the figures of its pairs NaN; a Sigma_k that is not positive definite makes pc, tpc and md2 of the pair NaN
+    and leaves tcpa and dcpa.  One upload, one call of `mht_encounters` (two launches), no host fallback."""
+    X, Pm = np.asarray(x, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    Phi, Q = np.asarray(Phi, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    nx = X.shape[1] if X.ndim == 2 else -1
+    if nx not in (4, 6):
+        raise ValueError("encounters: the states are an [n, 4] or [n, 6] array (got shape %r)" % (X.shape,))
+    n = len(X)
+    if Pm.shape != (n, nx, nx) or Phi.shape != (nx, nx) or Q.shape != (nx, nx):
+        raise ValueError("encounters: P, Phi and Q have shapes %r, %r and %r; [%d, %d, %d] and twice [%d, %d] are wanted"
+                         % (Pm.shape, Phi.shape, Q.shape, n, nx, nx, nx, nx))
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= ENCOUNTER_MAX_STEPS:
+        raise ValueError("encounters: steps is an integer in 1 .. %d (got %r)" % (ENCOUNTER_MAX_STEPS, steps))
+    for name, v in (("dt", dt), ("radius", radius)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+            raise ValueError("encounters: %s must be a finite positive number (got %r)" % (name, v))
+    if first is None:
+        first = n
+    if isinstance(first, bool) or not isinstance(first, (int, np.integer)) or not 0 <= first <= n:
+        raise ValueError("encounters: first is an integer in 0 .. n = %d (got %r)" % (n, first))
+    if not (np.isfinite(Phi).all() and np.isfinite(Q).all()):
+        raise ValueError("encounters: Phi and Q must be finite")
+    first, steps = int(first), int(steps)
+    if n < 2 or first == 0:
+        return _encounter_empty(first, n)
+    iu = np.triu_indices(nx)
+    xp, Pp = np.ascontiguousarray(X.T), np.ascontiguousarray(Pm[:, iu[0], iu[1]].T)
+    Phi, Q = np.ascontiguousarray(Phi), np.ascontiguousarray(Q)
+    own = ctx is None
+    if own:
+        ctx = Context(device, nx=nx)
+    try:
+        dev, lib = ctx.device, ctx.lib
+        x_d, P_d = torch.from_numpy(xp).to(dev), torch.from_numpy(Pp).to(dev)
+        need = int(lib.mht_encounter_work_bytes(n, steps))
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        out_d = torch.empty((len(ENCOUNTER_NAMES), first, n), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
+        _lib.check(lib.mht_encounters(ctx.handle, nx, n, first, steps, float(dt), float(radius), Phi.ctypes.data, Q.ctypes.data,
+                                      x_d.data_ptr(), P_d.data_ptr(), out_d.data_ptr(), work.data_ptr(), need), lib)
+        out = out_d.cpu().numpy()
+    finally:
+        if own:
+            ctx.close()
+    return {k: np.ascontiguousarray(out[f]) for f, k in enumerate(ENCOUNTER_NAMES)}

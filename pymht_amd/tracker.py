@@ -1269,6 +1269,69 @@ class Tracker():
         out["consistency"] = evaluation.nees_consistency(out["tracks"], alpha=alpha)
         return out
 
+    def getEncounters(self, horizon, radius, ownShip=None, ownCovariance=None, steps=None):
+        """Which of the live tracks come close to each other -- or to the own ship -- within the next `horizon` seconds, and how sure
+        is that?  What a collision-avoidance system asks of a tracker (evaluation.encounters defines the figures): per pair the closest
+        point of approach (tcpa, dcpa), the smallest Mahalanobis distance (md2) and the largest probability over the horizon of being
+        within `radius` of each other (pc, at time tpc, by the stated rule: good to about 1e-6, not exact).  Times count from the
+        current scan.
+
+        horizon, radius   seconds ahead (> 0) and the safety radius (> 0, metres)
+        steps       None: ceil(horizon / radarPeriod), at most 64; dt = horizon / steps.  Phi(dt) and Q(dt) are the model module's, in
+                    float64
+        ownShip     None: all pairs of live tracks.  Else the own ship's state of the model's length, or a position with velocity
+                    ([x, y] or [x, y, vx, vy]), padded with zeros: it becomes entry 0, with ownCovariance ([nx, nx], or smaller and
+                    padded with zeros; default: zeros, a known own state), and only the own ship against every track is computed
+        The entries are the last rows of getFilteredTracks() of every live track, all at the current scan: the states of the float64
+        filter over each history.  The AIS-aided filter's state is NOT used, as with getFilteredTracks() by default: an AIS-aided
+        tracker's entries are filtered from the radar plots alone.  The tracks are taken as independent (cross-correlation between
+        them is not modelled).  A constant-turn tracker raises NotImplementedError (model "ct": its transition depends on the state).
+        Returns evaluation.encounters' dict of [first, n] arrays (first = 1 with ownShip, else n) plus `ids`, the targets' ids in entry
+        order (None for the own ship).  Fewer than two entries: empty arrays (all NaN) and no device call."""
+        from . import evaluation
+        for name, v in (("horizon", horizon), ("radius", radius)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+                raise ValueError("getEncounters: %s must be a finite positive number (got %r)" % (name, v))
+        if steps is None:
+            steps = min(int(np.ceil(float(horizon) / float(self.radarPeriod))), evaluation.ENCOUNTER_MAX_STEPS)
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= evaluation.ENCOUNTER_MAX_STEPS:
+            raise ValueError("getEncounters: steps is an integer in 1 .. %d (got %r)" % (evaluation.ENCOUNTER_MAX_STEPS, steps))
+        steps = int(steps)
+        dt = float(horizon) / steps
+        nx, Phi, Q = evaluation.encounter_model(self._model_mod, dt)
+        x, P, ids = [], [], []
+        if ownShip is not None:
+            own = np.asarray(ownShip, dtype=np.float64).reshape(-1)
+            if len(own) not in (2, 4, nx):
+                raise ValueError("getEncounters: ownShip is [x, y], [x, y, vx, vy] or a state of %d components (got %d)" % (nx, len(own)))
+            cov = np.zeros((nx, nx)) if ownCovariance is None else np.asarray(ownCovariance, dtype=np.float64)
+            if cov.ndim != 2 or cov.shape[0] != cov.shape[1] or cov.shape[0] not in (2, 4, nx):
+                raise ValueError("getEncounters: ownCovariance is a square matrix of 2, 4 or %d rows (got shape %r)" % (nx, cov.shape))
+            xo, Po = np.zeros(nx), np.zeros((nx, nx))
+            xo[:len(own)] = own
+            Po[:cov.shape[0], :cov.shape[0]] = cov
+            x.append(xo)
+            P.append(Po)
+            ids.append(None)
+        elif ownCovariance is not None:
+            raise ValueError("getEncounters: ownCovariance without ownShip")
+        nodes = list(self.__trackNodes__)
+        if nodes:
+            from . import smoothing
+            chains = [smoothing.chain_inputs(node, self._model_mod.P0)[0] for node in nodes]
+            ids += [leaf.ID if leaf.ID is not None else ch[0].ID if ch[0].ID is not None else -(i + 1) for i, (leaf, ch) in enumerate(zip(nodes, chains))]
+            for xf, Pf in self.getFilteredTracks():
+                x.append(np.asarray(xf, dtype=np.float64)[-1])
+                P.append(np.asarray(Pf, dtype=np.float64)[-1])
+        n = len(x)
+        first = 1 if ownShip is not None else n
+        if n < 2:
+            out = evaluation._encounter_empty(min(first, n), n)
+        else:
+            out = evaluation.encounters(np.array(x), np.array(P), Phi, Q, steps, dt, float(radius), first=first, ctx=self._ctx)
+        out["ids"] = ids
+        return out
+
     def getOspa2(self, truth, c, p=2, window=None, every=1, terminated=True, smooth=False, constantTurn=False, ais=False, truthIds=None):
         """The track histories scored against the truth TRAJECTORIES: OSPA(2) over windows of steps (evaluation.ospa2_windows, which
         defines the figures).  Per-scan GOSPA assigns every scan on its own, so this is the figure that sees whether the targets were
