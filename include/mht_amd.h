@@ -545,6 +545,40 @@ size_t mht_encounter_work_bytes(int32_t n, int32_t K);
 int mht_encounters(mht_ctx* ctx, int32_t nx, int32_t n, int32_t first, int32_t K, double dt, double R, const double* Phi, const double* Q,
                    const double* x, const double* P, double* out, void* work, size_t work_bytes);
 
+/* mht_trial_manoeuvres: "and if I alter course by 40 degrees to starboard, or slow to half speed, in 30 s?" -- G candidate manoeuvres
+ * of the own ship, each held against every one of n tracks over the horizon, in one call: the tracks are propagated once (as
+ * mht_encounters propagates them), a cell (g, j) holds mht_encounters' five figures of candidate g against track j (d_k = own - track,
+ * Sigma_k = S_own + S_j,k, pc by the same rule), and per candidate the worst track is folded out.
+ * THE MANOEUVRE (csrc/mht_trial.h states the operations).  The own ship at the current scan is at p0 with velocity v0 and may carry a
+ * constant 2 x 2 position covariance S_own, which is its covariance at every step.  A candidate is (dpsi, f, t0): the course change in
+ * radians, positive counter-clockwise in the tracker's axes, |dpsi| <= pi; the speed factor f >= 0; the delay t0 >= 0 in seconds.  One
+ * turn rate w > 0 (rad/s) serves all candidates.  With sg = sign(dpsi), te = t0 + |dpsi| / w and Rot(a) the plane rotation by a:
+ *   t <= t0        p(t) = p0 + t v0
+ *   t0 < t <= te   tau = t - t0, sw = sin(w tau) / w, cw = (1 - cos(w tau)) / w:  p(t) = p(t0) + f [sw, -sg cw; sg cw, sw] v0
+ *                  (the arc of a constant turn at rate sg w and speed f |v0|; the speed changes at t0 at once, ARPA's convention)
+ *   t > te         p(t) = p(te) + (t - te) f Rot(dpsi) v0
+ * dpsi = 0 skips the arc, a t0 beyond the horizon is "stand on", a turn may end beyond the horizon.  Positions are evaluated in closed
+ * form at t = k dt, k = 0 .. K, never accumulated.  A NaN in a candidate, in own or in Sown makes that candidate's row NaN.
+ *   nx, n, K, dt, R, Phi, Q, x, P   as for mht_encounters; the n entries are the tracks (the own ship is not one of them)
+ *   G        1 .. MHT_TRIAL_MAX_CANDIDATES candidates
+ *   own      HOST [4] f64: p0 (x, y), v0 (x, y);  Sown: HOST [3] f64: xx, xy, yy;  w: the turn rate
+ *   cand     HOST [G][3] f64: dpsi, f, t0
+ *   out      dev [5][G][n] f64 out: tcpa, dcpa, md2, pc, tpc.  EVERY cell is written
+ *   summary  dev [4][G] f64 out: pcMax, pcArg, dcpaMin, dcpaArg -- the largest pc of the row and the smallest dcpa, each with its track
+ *            index as a double.  NaN cells do not take part, equal figures go to the lowest track; a row without a figure gives NaN, -1
+ *   work     dev, at least mht_trial_work_bytes(n, G, K) bytes (0 for n <= 0, a G or a K out of range): the trajectories
+ *            pos [K + 1][2][n + G] and S [K + 1][3][n + G] (tracks first), the per-tile partials, the staged entries and candidates
+ * Four launches (tracks, candidates, cells with a fold per tile of 256 tracks, one wavefront per candidate over the tiles); no atomic,
+ * the bits do not depend on the order workgroups run in.  Synchronises.
+ * MHT_E_INVALID: nx not 4 or 6, K outside 1 .. 64, G outside its range, n < 0, R, dt or w not positive and finite; and for a call that
+ * is not empty a null array, an infinite own or Sown, a candidate that is neither finite nor NaN or out of range, a work buffer too
+ * small; nothing has then been launched or written.  n == 0 returns MHT_OK and launches nothing.  Exported by both builds. */
+#define MHT_TRIAL_MAX_CANDIDATES 4096
+size_t mht_trial_work_bytes(int32_t n, int32_t G, int32_t K);
+int mht_trial_manoeuvres(mht_ctx* ctx, int32_t nx, int32_t n, int32_t G, int32_t K, double dt, double R, const double* Phi, const double* Q,
+                         const double* x, const double* P, const double* own, const double* Sown, double w, const double* cand, double* out,
+                         double* summary, void* work, size_t work_bytes);
+
 /* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
  * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);
  * with d_ij = sqrt(dx dx + dy dy) in float64 and only pairs with d_ij < c (strictly) assignable,

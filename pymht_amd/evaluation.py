@@ -587,3 +587,130 @@ def encounters(x, P, Phi, Q, steps, dt, radius, first=None, device=0, ctx=None):
         if own:
             ctx.close()
     return {k: np.ascontiguousarray(out[f]) for f, k in enumerate(ENCOUNTER_NAMES)}
+
+
+# ---- trial manoeuvres: and if the own ship alters course or speed? ------------------------------------------------------------------
+TRIAL_MAX_CANDIDATES = 4096                                    # MHT_TRIAL_MAX_CANDIDATES, include/mht_amd.h
+TRIAL_SUMMARY_NAMES = ("pcMax", "pcArg", "dcpaMin", "dcpaArg")      # the order of the seam's summary [4][G]
+
+
+def _trial_number(name, v, positive=True):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or (positive and not v > 0):
+        raise ValueError("trial_manoeuvres: %s must be a finite%s number (got %r)" % (name, " positive" if positive else "", v))
+    return float(v)
+
+
+def trial_candidates(candidates):
+    """The candidates as a contiguous float64 [G, 3] array of (dpsi, f, t0), checked: 1 .. TRIAL_MAX_CANDIDATES rows, every figure finite
+    or NaN, |dpsi| <= pi, f >= 0, t0 >= 0.  ValueError otherwise."""
+    try:
+        cand = np.ascontiguousarray(candidates, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("trial_manoeuvres: the candidates are a [G, 3] array of (dpsi, f, t0) (got %r)" % (candidates,))
+    if cand.ndim != 2 or cand.shape[1] != 3 or not 1 <= len(cand) <= TRIAL_MAX_CANDIDATES:
+        raise ValueError("trial_manoeuvres: the candidates are a [G, 3] array of (dpsi, f, t0), G in 1 .. %d (got shape %r)" % (TRIAL_MAX_CANDIDATES, cand.shape))
+    with np.errstate(invalid="ignore"):
+        if np.isinf(cand).any() or (np.abs(cand[:, 0]) > np.pi).any() or (cand[:, 1] < 0).any() or (cand[:, 2] < 0).any():
+            raise ValueError("trial_manoeuvres: a candidate is (dpsi, f, t0) with |dpsi| <= pi, f >= 0 and t0 >= 0, each finite or NaN")
+    return cand
+
+
+def _trial_empty(G, n):
+    out = {k: np.full((G, n), np.nan) for k in ENCOUNTER_NAMES}
+    out.update(pcMax=np.full(G, np.nan), pcArg=np.full(G, -1, dtype=np.int64), dcpaMin=np.full(G, np.nan), dcpaArg=np.full(G, -1, dtype=np.int64))
+    return out
+
+
+def trial_manoeuvres(x, P, Phi, Q, steps, dt, radius, own, candidates, turnRate, ownCovariance=None, device=0, ctx=None):
+    """And if the own ship alters course or speed?  G candidate manoeuvres, each held against every one of n tracks over the next
+    steps * dt seconds, in one device call: the tracks are propagated once, the table of candidates x tracks is filled in one launch
+    and folded to the worst track per candidate.
+
+    x, P, Phi, Q, steps, dt, radius   the tracks, the model of one step and the safety radius, as for `encounters`; the own ship is NOT
+               one of the entries
+    own        [x, y, vx, vy]: the own ship's position p0 and velocity v0 at the current scan
+    candidates [G, 3] rows (dpsi, f, t0), G in 1 .. 4096: the course change in radians, positive counter-clockwise in the tracker's axes,
+               |dpsi| <= pi; the speed factor f >= 0; the delay t0 >= 0 in seconds
+    turnRate   w > 0 in rad/s, for all candidates
+    ownCovariance   None (zeros: a known own position) or the own ship's 2 x 2 position covariance, constant over the horizon
+    device, ctx   the GPU ordinal, or an existing pymht_amd.device.Context (a Tracker's) to run on
+    The manoeuvre (csrc/mht_trial.h): the own ship stands on until t0, p(t) = p0 + t v0; then turns at rate sign(dpsi) w and speed
+    f |v0| -- the speed changes at t0 at once, ARPA's convention -- until te = t0 + |dpsi| / w,
+    p(t) = p(t0) + f [sw, -sg cw; sg cw, sw] v0 with sw = sin(w (t - t0)) / w and cw = (1 - cos(w (t - t0))) / w; then runs straight,
+    p(t) = p(te) + (t - te) f Rot(dpsi) v0.  dpsi = 0 skips the arc, a t0 beyond the horizon is "stand on", a turn may end beyond
+    the horizon.  Positions are closed forms at t = k dt.  A NaN in a candidate, in `own` or in the covariance makes that candidate's
+    row NaN.
+    ValueError for arguments that do not fit -- before any device is needed.  No track: empty [G, 0] arrays and no device call.
+    Returns a dict: `encounters`' five figures as float64 [G, n] arrays (cell (g, j): candidate g against track j, d_k = own - track,
+    pc by the same rule, good to about 1e-6, not exact; the two are taken as independent), and per candidate `pcMax` with `pcArg` -- the
+    largest pc of the row and its track -- and `dcpaMin` with `dcpaArg`, [G], the indices int64: NaN cells do not take part, equal
+    figures go to the lowest track, a row without a figure gives NaN and -1; and `candidates`, the [G, 3] array as it was used.  One
+    upload, one call of `mht_trial_manoeuvres` (four launches), no host fallback."""
+    X, Pm = np.asarray(x, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    Phi, Q = np.asarray(Phi, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    nx = X.shape[1] if X.ndim == 2 else -1
+    if nx not in (4, 6):
+        raise ValueError("trial_manoeuvres: the states are an [n, 4] or [n, 6] array (got shape %r)" % (X.shape,))
+    n = len(X)
+    if Pm.shape != (n, nx, nx) or Phi.shape != (nx, nx) or Q.shape != (nx, nx):
+        raise ValueError("trial_manoeuvres: P, Phi and Q have shapes %r, %r and %r; [%d, %d, %d] and twice [%d, %d] are wanted"
+                         % (Pm.shape, Phi.shape, Q.shape, n, nx, nx, nx, nx))
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= ENCOUNTER_MAX_STEPS:
+        raise ValueError("trial_manoeuvres: steps is an integer in 1 .. %d (got %r)" % (ENCOUNTER_MAX_STEPS, steps))
+    dt, radius, w = _trial_number("dt", dt), _trial_number("radius", radius), _trial_number("turnRate", turnRate)
+    if not (np.isfinite(Phi).all() and np.isfinite(Q).all()):
+        raise ValueError("trial_manoeuvres: Phi and Q must be finite")
+    try:
+        o = np.ascontiguousarray(own, dtype=np.float64)
+    except (TypeError, ValueError):
+        o = np.zeros(0)
+    if o.shape != (4,) or np.isinf(o).any():
+        raise ValueError("trial_manoeuvres: own is [x, y, vx, vy], finite or NaN (got %r)" % (own,))
+    cov = np.zeros((2, 2)) if ownCovariance is None else np.asarray(ownCovariance, dtype=np.float64)
+    if cov.shape != (2, 2) or np.isinf(cov).any() or not (cov[0, 1] == cov[1, 0] or np.isnan(cov).any()):
+        raise ValueError("trial_manoeuvres: ownCovariance is a symmetric 2 x 2 matrix, finite or NaN (got %r)" % (ownCovariance,))
+    so = np.array([cov[0, 0], cov[0, 1] if cov[1, 0] == cov[1, 0] else np.nan, cov[1, 1]])      # (a NaN below the diagonal counts as well)
+    cand = trial_candidates(candidates)
+    G, steps = len(cand), int(steps)
+    if n == 0:
+        out = _trial_empty(G, 0)
+        out["candidates"] = cand
+        return out
+    iu = np.triu_indices(nx)
+    xp, Pp = np.ascontiguousarray(X.T), np.ascontiguousarray(Pm[:, iu[0], iu[1]].T)
+    Phi, Q = np.ascontiguousarray(Phi), np.ascontiguousarray(Q)
+    mine = ctx is None
+    if mine:
+        ctx = Context(device, nx=nx)
+    try:
+        dev, lib = ctx.device, ctx.lib
+        x_d, P_d = torch.from_numpy(xp).to(dev), torch.from_numpy(Pp).to(dev)
+        need = int(lib.mht_trial_work_bytes(n, G, steps))
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        out_d = torch.empty((len(ENCOUNTER_NAMES), G, n), dtype=torch.float64, device=dev)
+        sum_d = torch.empty((len(TRIAL_SUMMARY_NAMES), G), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
+        _lib.check(lib.mht_trial_manoeuvres(ctx.handle, nx, n, G, steps, dt, radius, Phi.ctypes.data, Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(),
+                                            o.ctypes.data, so.ctypes.data, w, cand.ctypes.data, out_d.data_ptr(), sum_d.data_ptr(), work.data_ptr(), need), lib)
+        out, summary = out_d.cpu().numpy(), sum_d.cpu().numpy()
+    finally:
+        if mine:
+            ctx.close()
+    res = {k: np.ascontiguousarray(out[f]) for f, k in enumerate(ENCOUNTER_NAMES)}
+    res.update(pcMax=summary[0].copy(), pcArg=summary[1].astype(np.int64), dcpaMin=summary[2].copy(), dcpaArg=summary[3].astype(np.int64), candidates=cand)
+    return res
+
+
+def trial_best(pcMax, dcpaMin):
+    """The safest candidate of a summary: the smallest pcMax, then the largest dcpaMin, then the lowest index.  A candidate whose pcMax is
+    NaN -- no cell of its row has a pc -- is not eligible (nothing is known about it); among equal pcMax a NaN dcpaMin ranks last.
+    None if no candidate is eligible."""
+    pc, d = np.asarray(pcMax, dtype=np.float64), np.asarray(dcpaMin, dtype=np.float64)
+    best = None
+    for g in range(len(pc)):
+        if np.isnan(pc[g]):
+            continue
+        dg = -np.inf if np.isnan(d[g]) else d[g]
+        if best is None or pc[g] < best[0] or (pc[g] == best[0] and dg > best[1]):
+            best = (pc[g], dg, g)
+    return None if best is None else best[2]

@@ -1332,6 +1332,69 @@ class Tracker():
         out["ids"] = ids
         return out
 
+    def getTrialManoeuvres(self, horizon, radius, ownShip, courseChanges, turnRate, speedFactors=(1.0,), delay=0.0, ownCovariance=None, steps=None):
+        """And if the own ship alters course or speed?  The trial-manoeuvre question of a collision-avoidance system: a grid of candidate
+        manoeuvres of the own ship, each held against every live track over the next `horizon` seconds, in one device call
+        (evaluation.trial_manoeuvres defines the manoeuvre and the figures).  Times count from the current scan.
+
+        horizon, radius, steps   as for getEncounters: steps None is ceil(horizon / radarPeriod), at most 64; dt = horizon / steps
+        ownShip        [x, y, vx, vy]: the own ship's position and velocity at the current scan
+        courseChanges  the course changes in radians, positive counter-clockwise in the tracker's axes, |dpsi| <= pi; 0 is "keep the
+                       course"
+        speedFactors   the speed factors f >= 0 (0.5: half speed); the speed changes at `delay` at once
+        delay          seconds >= 0 until the manoeuvre begins, the same for all candidates
+        turnRate       the own ship's turn rate in rad/s, > 0.  There is no default: it is the ship's, not the tracker's
+        ownCovariance  None (a known own position) or the own ship's 2 x 2 position covariance, constant over the horizon
+        The candidates are the product courseChanges x speedFactors, the speed factor fastest: candidate c * len(speedFactors) + s.
+        The entries are getEncounters': the last rows of getFilteredTracks() of every live track, all at the current scan.  The
+        AIS-aided filter's state is NOT used: an AIS-aided tracker's entries are filtered from the radar plots alone.  The own ship and
+        the tracks are taken as independent.  A constant-turn tracker raises NotImplementedError (model "ct": its transition depends on
+        the state).
+        Returns evaluation.trial_manoeuvres' dict -- the five figures as [G, n] arrays, pcMax, pcArg, dcpaMin, dcpaArg [G] and
+        `candidates` [G, 3] -- plus `ids`, the targets' ids in track order, and `best`: the index of the candidate with the smallest
+        pcMax, then the largest dcpaMin, then the lowest index (evaluation.trial_best, on the host; None where no candidate has a pcMax).
+        No live track: empty [G, 0] arrays, no device call, best None."""
+        from . import evaluation
+        for name, v in (("horizon", horizon), ("radius", radius), ("turnRate", turnRate)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+                raise ValueError("getTrialManoeuvres: %s must be a finite positive number (got %r)" % (name, v))
+        if isinstance(delay, bool) or not isinstance(delay, (int, float, np.integer, np.floating)) or not np.isfinite(delay) or delay < 0:
+            raise ValueError("getTrialManoeuvres: delay must be a finite number >= 0 (got %r)" % (delay,))
+        if steps is None:
+            steps = min(int(np.ceil(float(horizon) / float(self.radarPeriod))), evaluation.ENCOUNTER_MAX_STEPS)
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= evaluation.ENCOUNTER_MAX_STEPS:
+            raise ValueError("getTrialManoeuvres: steps is an integer in 1 .. %d (got %r)" % (evaluation.ENCOUNTER_MAX_STEPS, steps))
+        steps = int(steps)
+        dt = float(horizon) / steps
+        nx, Phi, Q = evaluation.encounter_model(self._model_mod, dt)
+        own = np.asarray(ownShip, dtype=np.float64).reshape(-1)
+        if len(own) != 4:
+            raise ValueError("getTrialManoeuvres: ownShip is [x, y, vx, vy] (got %d components)" % len(own))
+        dpsi, fs = np.asarray(courseChanges, dtype=np.float64).reshape(-1), np.asarray(speedFactors, dtype=np.float64).reshape(-1)
+        if len(dpsi) == 0 or len(fs) == 0:
+            raise ValueError("getTrialManoeuvres: courseChanges and speedFactors need one value at least")
+        try:
+            cand = evaluation.trial_candidates([(a, f, float(delay)) for a in dpsi for f in fs])
+        except ValueError as exc:
+            raise ValueError("getTrialManoeuvres: " + str(exc))
+        x, P, ids = [], [], []
+        nodes = list(self.__trackNodes__)
+        if nodes:
+            from . import smoothing
+            chains = [smoothing.chain_inputs(node, self._model_mod.P0)[0] for node in nodes]
+            ids += [leaf.ID if leaf.ID is not None else ch[0].ID if ch[0].ID is not None else -(i + 1) for i, (leaf, ch) in enumerate(zip(nodes, chains))]
+            for xf, Pf in self.getFilteredTracks():
+                x.append(np.asarray(xf, dtype=np.float64)[-1])
+                P.append(np.asarray(Pf, dtype=np.float64)[-1])
+        try:
+            out = evaluation.trial_manoeuvres(np.array(x).reshape(len(x), nx), np.array(P).reshape(len(x), nx, nx), Phi, Q, steps, dt, float(radius), own, cand,
+                                              float(turnRate), ownCovariance=ownCovariance, ctx=self._ctx)
+        except ValueError as exc:
+            raise ValueError("getTrialManoeuvres: " + str(exc))
+        out["ids"] = ids
+        out["best"] = evaluation.trial_best(out["pcMax"], out["dcpaMin"])
+        return out
+
     def getOspa2(self, truth, c, p=2, window=None, every=1, terminated=True, smooth=False, constantTurn=False, ais=False, truthIds=None):
         """The track histories scored against the truth TRAJECTORIES: OSPA(2) over windows of steps (evaluation.ospa2_windows, which
         defines the figures).  Per-scan GOSPA assigns every scan on its own, so this is the figure that sees whether the targets were
