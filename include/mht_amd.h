@@ -579,6 +579,44 @@ int mht_trial_manoeuvres(mht_ctx* ctx, int32_t nx, int32_t n, int32_t G, int32_t
                          const double* x, const double* P, const double* own, const double* Sown, double w, const double* cand, double* out,
                          double* summary, void* work, size_t work_bytes);
 
+/* mht_trial_hypotheses: the trial manoeuvres held against EVERY LIVE HYPOTHESIS of every target, not only the selected one.  The
+ * entries are L leaves of the forest in target order (mht_forest_leaves*' order), the leaves of target t being seg[t] .. seg[t + 1] - 1;
+ * a cell (g, l) is mht_trial_manoeuvres' cell of candidate g against leaf l -- the same code, the same bits -- and per (candidate,
+ * target) the cells of the target's leaves are folded (csrc/mht_trial_hyp.h states the operations):
+ *   pcWorst, pcWorstLeaf   the largest pc over the target's leaves and its leaf, a GLOBAL leaf index as a double
+ *   dcpaMin, dcpaMinLeaf   the smallest dcpa and its leaf.  mht_trial_manoeuvres' fold: a NaN figure takes no part, equal figures go to
+ *                          the lowest leaf, no figure gives NaN and -1; bit for bit independent of the grouping
+ *   pcMean                 sum(w_l pc_l) / sum(w_l) over the leaves whose pc and cnllr are both not NaN, w_l = exp(-(cnllr_l - cmin_t)),
+ *                          cmin_t the smallest non-NaN cnllr of the target (a lower cumulative NLLR is the better hypothesis); NaN where
+ *                          there is no such leaf.  A target of one leaf has w = 1 and pcMean = pc bit for bit
+ *   pcSel, dcpaSel, tcpaSel   the cell of leaf sel[t]: what the best-hypothesis view reports.  NaN where sel[t] = -1
+ * THE APPROXIMATION.  The weights normalise INSIDE ONE TARGET: the hypotheses of a target are weighed against each other by their own
+ * cumulative scores, and the exclusion constraints BETWEEN targets, which the ILP enforces (two targets cannot take the same plot), are
+ * ignored.  This is the usual track-oriented approximation of the hypothesis probabilities; it is not the probability of a global
+ * hypothesis.
+ *   nx, K, dt, R, Phi, Q, own, Sown, w, cand, G   as for mht_trial_manoeuvres
+ *   L, T     leaves and targets, 1 <= T <= L for a call that is not empty
+ *   x        dev [nx][L] f64;  P: dev [nx (nx + 1) / 2][L] f64;  cnllr: dev [L] f64, the cumulative NLLR of every leaf (NaN: the leaf
+ *            has no weight and takes no part in pcMean; +inf: weight 0)
+ *   seg      HOST [T + 1] int32: seg[0] = 0, non-decreasing (an empty target is allowed), seg[T] = L
+ *   sel      HOST [T] int32: the GLOBAL index of the target's selected leaf, inside seg[t] .. seg[t + 1] - 1, or -1
+ *   table    dev [5][G][L] f64 out, or NULL: mht_trial_manoeuvres' table for n = L.  The figures below do not need it to exist
+ *   fig      dev [8][G][T] f64 out, in the order above.  EVERY cell is written (an empty target: NaN and -1)
+ *   weight   dev [L] f64 out: w_l / sum(w) over the target's leaves that have a cnllr, the sum taken in leaf order; NaN for a leaf
+ *            without one
+ *   work     dev, at least mht_trial_hyp_work_bytes(L, T, G, K) bytes (0 for sizes out of range)
+ * Five launches (weights, one target per lane; leaves; candidates; cells with a serial fold per piece of a target inside a tile of 256
+ * leaves; one lane per (candidate, target) over the pieces in tile order); no atomic, the bits do not depend on the order workgroups
+ * run in.  The small host arrays have been copied when the call returns.  Synchronises.
+ * MHT_E_INVALID: what mht_trial_manoeuvres refuses, and T outside 1 .. L, a seg that does not start at 0, decreases or does not end at
+ * L, a sel outside its segment; nothing has then been launched or written.  L == 0 returns MHT_OK and launches nothing.  Exported by
+ * both builds. */
+size_t mht_trial_hyp_work_bytes(int32_t n_leaves, int32_t n_targets, int32_t G, int32_t K);
+int mht_trial_hypotheses(mht_ctx* ctx, int32_t nx, int32_t L, int32_t T, int32_t G, int32_t K, double dt, double R, const double* Phi,
+                         const double* Q, const double* x, const double* P, const double* cnllr, const int32_t* seg, const int32_t* sel,
+                         const double* own, const double* Sown, double w, const double* cand, double* table, double* fig, double* weight,
+                         void* work, size_t work_bytes);
+
 /* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
  * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);
  * with d_ij = sqrt(dx dx + dy dy) in float64 and only pairs with d_ij < c (strictly) assignable,

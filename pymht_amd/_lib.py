@@ -161,6 +161,7 @@ def _declare(lib, nx=4):
         "mht_nees_nodes": [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
         "mht_encounters": [vp, i32, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_trial_manoeuvres": [vp, i32, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp, C.c_size_t],
+        "mht_trial_hypotheses": [vp, i32, i32, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_gospa_steps": [vp, i32, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
         "mht_ospa2_windows": [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
         "mht_forest_create_ex": [vp, vp, vp, C.c_uint32],
@@ -232,6 +233,8 @@ def _declare(lib, nx=4):
     lib.mht_encounter_work_bytes.restype = C.c_size_t
     lib.mht_trial_work_bytes.argtypes = [i32, i32, i32]
     lib.mht_trial_work_bytes.restype = C.c_size_t
+    lib.mht_trial_hyp_work_bytes.argtypes = [i32, i32, i32, i32]
+    lib.mht_trial_hyp_work_bytes.restype = C.c_size_t
     lib.mht_gospa_work_bytes.argtypes = [i32, i32, i32]
     lib.mht_gospa_work_bytes.restype = C.c_size_t
     lib.mht_ospa2_work_bytes.argtypes = [i32, i32, i32, i32]

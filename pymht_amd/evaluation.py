@@ -701,6 +701,129 @@ def trial_manoeuvres(x, P, Phi, Q, steps, dt, radius, own, candidates, turnRate,
     return res
 
 
+# ---- trial manoeuvres against every live hypothesis: the best hypothesis is not the only one -----------------------------------------
+TRIAL_HYP_NAMES = ("pcWorst", "pcWorstLeaf", "dcpaMin", "dcpaMinLeaf", "pcMean", "pcSel", "dcpaSel", "tcpaSel")      # the seam's fig [8][G][T]
+
+
+def _trial_hyp_empty(G, T, L, cand, leafTable):
+    out = {k: np.full((G, T), np.nan) for k in TRIAL_HYP_NAMES}
+    out["pcWorstLeaf"], out["dcpaMinLeaf"] = np.full((G, T), -1, dtype=np.int64), np.full((G, T), -1, dtype=np.int64)
+    out.update(weight=np.full(L, np.nan), nLeaves=np.zeros(T, dtype=np.int64), candidates=cand)
+    if leafTable:
+        out.update({k: np.full((G, L), np.nan) for k in ENCOUNTER_NAMES})
+    return out
+
+
+def trial_hypotheses(x, P, cnllr, target, Phi, Q, steps, dt, radius, own, candidates, turnRate, selected=None, ownCovariance=None, leafTable=False,
+                     device=0, ctx=None):
+    """`trial_manoeuvres` held against EVERY LIVE HYPOTHESIS of every target instead of one state per track: the entries are the L leaves
+    of the forest, and the candidates' rows are folded per target.  A multi-hypothesis tracker keeps, per target, the alternatives "that
+    plot was clutter" and "it took the other plot"; the best of them is not the only one, and a second leaf nearly as likely may give a
+    very different pc.
+
+    x, P, cnllr, target   the leaves in `Tracker.leafBatch()`'s layout: x [L, nx], P [L, nx, nx], the cumulative NLLR [L] (a LOWER one is
+               the better hypothesis; NaN: the leaf has no weight; +inf: weight 0; -inf is refused) and the NON-DECREASING target index
+               [L] of every leaf.  A target index that no leaf carries is an empty target
+    selected   None, or [T]: per target the index (into the L leaves) of its selected leaf, inside the target's leaves, or -1.  Given, it
+               also sets the number of targets T (otherwise T = target[-1] + 1)
+    leafTable  True: the five [G, L] tables of `trial_manoeuvres` are returned as well (5 G L doubles on the device and on the host);
+               the per-target figures do not need them to exist
+    Phi, Q, steps, dt, radius, own, candidates, turnRate, ownCovariance, device, ctx   as for `trial_manoeuvres`
+    ValueError for arguments that do not fit -- before any device is needed.  No leaf: empty arrays and no device call.
+    Returns a dict of [G, T] arrays (csrc/mht_trial_hyp.h states the operations), a cell (g, l) being `trial_manoeuvres`' cell of
+    candidate g against leaf l, bit for bit:
+        pcWorst, pcWorstLeaf   the largest pc over the target's leaves and its leaf (int64, an index into the L leaves)
+        dcpaMin, dcpaMinLeaf   the smallest dcpa and its leaf.  NaN cells take no part, equal figures go to the lowest leaf, no figure
+                               gives NaN and -1
+        pcMean                 sum(w_l pc_l) / sum(w_l) over the leaves with a pc and a cnllr, w_l = exp(-(cnllr_l - cmin_t)) with cmin_t
+                               the target's smallest cnllr; NaN where there is no such leaf.  A target of one leaf has pcMean = pc
+        pcSel, dcpaSel, tcpaSel   the cell of the selected leaf: what the best-hypothesis view reports, next to what it hides.  NaN
+                               where the target has none
+    and `weight` [L], w_l / sum(w) within the leaf's target (NaN without a cnllr), `nLeaves` [T] (int64) and `candidates` [G, 3].
+    THE WEIGHTS NORMALISE INSIDE ONE TARGET.  The exclusion constraints between targets, which the ILP enforces, are ignored: this is
+    the usual track-oriented approximation of the hypothesis probabilities, not the probability of a global hypothesis.  pc is by
+    `encounters`' rule, good to about 1e-6, not exact; the own ship and the leaves are taken as independent.
+    One upload, one call of `mht_trial_hypotheses` (five launches), no host fallback."""
+    X, Pm = np.asarray(x, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    Phi, Q = np.asarray(Phi, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    nx = X.shape[1] if X.ndim == 2 else -1
+    if nx not in (4, 6):
+        raise ValueError("trial_hypotheses: the states are an [L, 4] or [L, 6] array (got shape %r)" % (X.shape,))
+    L = len(X)
+    if Pm.shape != (L, nx, nx) or Phi.shape != (nx, nx) or Q.shape != (nx, nx):
+        raise ValueError("trial_hypotheses: P, Phi and Q have shapes %r, %r and %r; [%d, %d, %d] and twice [%d, %d] are wanted"
+                         % (Pm.shape, Phi.shape, Q.shape, L, nx, nx, nx, nx))
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= ENCOUNTER_MAX_STEPS:
+        raise ValueError("trial_hypotheses: steps is an integer in 1 .. %d (got %r)" % (ENCOUNTER_MAX_STEPS, steps))
+    try:
+        dt, radius, w = _trial_number("dt", dt), _trial_number("radius", radius), _trial_number("turnRate", turnRate)
+        cand = trial_candidates(candidates)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("trial_manoeuvres", "trial_hypotheses", 1))
+    if not (np.isfinite(Phi).all() and np.isfinite(Q).all()):
+        raise ValueError("trial_hypotheses: Phi and Q must be finite")
+    try:
+        o = np.ascontiguousarray(own, dtype=np.float64)
+    except (TypeError, ValueError):
+        o = np.zeros(0)
+    if o.shape != (4,) or np.isinf(o).any():
+        raise ValueError("trial_hypotheses: own is [x, y, vx, vy], finite or NaN (got %r)" % (own,))
+    cov = np.zeros((2, 2)) if ownCovariance is None else np.asarray(ownCovariance, dtype=np.float64)
+    if cov.shape != (2, 2) or np.isinf(cov).any() or not (cov[0, 1] == cov[1, 0] or np.isnan(cov).any()):
+        raise ValueError("trial_hypotheses: ownCovariance is a symmetric 2 x 2 matrix, finite or NaN (got %r)" % (ownCovariance,))
+    so = np.array([cov[0, 0], cov[0, 1] if cov[1, 0] == cov[1, 0] else np.nan, cov[1, 1]])      # (a NaN below the diagonal counts as well)
+    cn = np.ascontiguousarray(cnllr, dtype=np.float64)
+    if cn.shape != (L,) or (cn == -np.inf).any():
+        raise ValueError("trial_hypotheses: cnllr is an [L] = [%d] array without -inf (got shape %r)" % (L, cn.shape))
+    tg = np.asarray(target)
+    if tg.shape != (L,) or not np.issubdtype(tg.dtype, np.integer) or (L and (tg[0] < 0 or (np.diff(tg) < 0).any())):
+        raise ValueError("trial_hypotheses: target is a non-decreasing [L] = [%d] array of target indices >= 0 (got %r)" % (L, target))
+    T = int(tg[-1]) + 1 if L else 0
+    if selected is not None:
+        sl = np.asarray(selected)
+        if sl.ndim != 1 or not np.issubdtype(sl.dtype, np.integer) or len(sl) < T:
+            raise ValueError("trial_hypotheses: selected is an integer array with one entry per target, %d at least (got %r)" % (T, selected))
+        T = len(sl)
+    else:
+        sl = np.full(T, -1)
+    seg = np.searchsorted(tg, np.arange(T + 1)).astype(np.int32)      # the leaves of target t: seg[t] .. seg[t + 1] - 1
+    sl = np.ascontiguousarray(sl, dtype=np.int32)
+    if ((sl != -1) & ((sl < seg[:-1]) | (sl >= seg[1:]))).any():
+        raise ValueError("trial_hypotheses: selected[t] is -1 or the index of a leaf of target t (got %r)" % (selected,))
+    G, steps = len(cand), int(steps)
+    if L == 0:
+        return _trial_hyp_empty(G, T, 0, cand, leafTable)
+    iu = np.triu_indices(nx)
+    xp, Pp = np.ascontiguousarray(X.T), np.ascontiguousarray(Pm[:, iu[0], iu[1]].T)
+    Phi, Q = np.ascontiguousarray(Phi), np.ascontiguousarray(Q)
+    mine = ctx is None
+    if mine:
+        ctx = Context(device, nx=nx)
+    try:
+        dev, lib = ctx.device, ctx.lib
+        x_d, P_d, c_d = torch.from_numpy(xp).to(dev), torch.from_numpy(Pp).to(dev), torch.from_numpy(cn).to(dev)
+        need = int(lib.mht_trial_hyp_work_bytes(L, T, G, steps))
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        tab_d = torch.empty((len(ENCOUNTER_NAMES), G, L), dtype=torch.float64, device=dev) if leafTable else None
+        fig_d = torch.empty((len(TRIAL_HYP_NAMES), G, T), dtype=torch.float64, device=dev)
+        wgt_d = torch.empty(L, dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
+        _lib.check(lib.mht_trial_hypotheses(ctx.handle, nx, L, T, G, steps, dt, radius, Phi.ctypes.data, Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(),
+                                            c_d.data_ptr(), seg.ctypes.data, sl.ctypes.data, o.ctypes.data, so.ctypes.data, w, cand.ctypes.data,
+                                            tab_d.data_ptr() if leafTable else None, fig_d.data_ptr(), wgt_d.data_ptr(), work.data_ptr(), need), lib)
+        fig, weight = fig_d.cpu().numpy(), wgt_d.cpu().numpy()
+        table = tab_d.cpu().numpy() if leafTable else None
+    finally:
+        if mine:
+            ctx.close()
+    res = {k: np.ascontiguousarray(fig[f]) for f, k in enumerate(TRIAL_HYP_NAMES)}
+    res["pcWorstLeaf"], res["dcpaMinLeaf"] = res["pcWorstLeaf"].astype(np.int64), res["dcpaMinLeaf"].astype(np.int64)
+    res.update(weight=weight, nLeaves=np.diff(seg).astype(np.int64), candidates=cand)
+    if leafTable:
+        res.update({k: np.ascontiguousarray(table[f]) for f, k in enumerate(ENCOUNTER_NAMES)})
+    return res
+
+
 def trial_best(pcMax, dcpaMin):
     """The safest candidate of a summary: the smallest pcMax, then the largest dcpaMin, then the lowest index.  A candidate whose pcMax is
     NaN -- no cell of its row has a pc -- is not eligible (nothing is known about it); among equal pcMax a NaN dcpaMin ranks last.

@@ -1395,6 +1395,95 @@ class Tracker():
         out["best"] = evaluation.trial_best(out["pcMax"], out["dcpaMin"])
         return out
 
+    def getHypothesisEncounters(self, horizon, radius, ownShip, courseChanges=(0.0,), turnRate=None, speedFactors=(1.0,), delay=0.0, ownCovariance=None,
+                                steps=None, leafTable=False):
+        """getTrialManoeuvres held against EVERY LIVE HYPOTHESIS of every target, not only the selected one.  This is a multi-hypothesis
+        tracker: per target the forest keeps the alternatives "that plot was clutter" and "it took the other plot", each with a state, a
+        covariance and a cumulative score.  getEncounters and getTrialManoeuvres report the selected hypothesis alone; a second leaf of
+        the same target, nearly as likely, may give a very different pc, and this is where it shows
+        (evaluation.trial_hypotheses defines the figures).  Times count from the current scan.
+
+        horizon, radius, ownShip, speedFactors, delay, ownCovariance, steps   as for getTrialManoeuvres
+        courseChanges  as for getTrialManoeuvres; the default (0.0,) is "the own ship standing on"
+        turnRate       the own ship's turn rate in rad/s, > 0.  Not needed while every course change is 0; required (ValueError) as soon
+                       as one is not
+        leafTable      True: the five [G, L] tables of the cells (candidate, leaf) are returned too
+        The entries are leafBatch()'s leaves at the current scan: the forest's OWN states and covariances, nothing is re-filtered and no
+        history is walked.  For an AIS-aided tracker they include the AIS updates (float64 covariances): the AIS gap of getEncounters
+        and getTrialManoeuvres is closed for this output.  The selected leaf of a target is the one whose node is the live track node's
+        (a target born since the last scan is its own only leaf).
+        The hypothesis weights normalise INSIDE ONE TARGET, exp(-(cnllr - the target's smallest cnllr)); the exclusion constraints between
+        targets, which the ILP enforces, are ignored -- the usual track-oriented approximation, not global-hypothesis probabilities.  The
+        own ship and the leaves are taken as independent.  A constant-turn tracker raises NotImplementedError (model "ct": its transition
+        depends on the state).
+        Returns evaluation.trial_hypotheses' dict -- pcWorst, pcWorstLeaf, dcpaMin, dcpaMinLeaf, pcMean, pcSel, dcpaSel, tcpaSel [G, T],
+        weight [L], nLeaves [T], candidates [G, 3] -- plus `ids` (the targets' ids in target order), `leafIds` (the target id of every
+        leaf), and per candidate, folded over the targets on the host: `pcMeanMax` with `pcMeanMaxTarget`, `pcWorstMax` with
+        `pcWorstMaxTarget` and `dcpaMinAll` with `dcpaMinAllTarget` [G] (NaN and -1 without a figure); `best`, evaluation.trial_best of
+        (pcMeanMax, dcpaMinAll), and `bestWorstCase`, the same on pcWorstMax.  No live track: empty [G, 0] arrays, no device call."""
+        from . import evaluation
+        for name, v in (("horizon", horizon), ("radius", radius)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+                raise ValueError("getHypothesisEncounters: %s must be a finite positive number (got %r)" % (name, v))
+        if isinstance(delay, bool) or not isinstance(delay, (int, float, np.integer, np.floating)) or not np.isfinite(delay) or delay < 0:
+            raise ValueError("getHypothesisEncounters: delay must be a finite number >= 0 (got %r)" % (delay,))
+        if steps is None:
+            steps = min(int(np.ceil(float(horizon) / float(self.radarPeriod))), evaluation.ENCOUNTER_MAX_STEPS)
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= evaluation.ENCOUNTER_MAX_STEPS:
+            raise ValueError("getHypothesisEncounters: steps is an integer in 1 .. %d (got %r)" % (evaluation.ENCOUNTER_MAX_STEPS, steps))
+        steps = int(steps)
+        dt = float(horizon) / steps
+        nx, Phi, Q = evaluation.encounter_model(self._model_mod, dt)
+        own = np.asarray(ownShip, dtype=np.float64).reshape(-1)
+        if len(own) != 4:
+            raise ValueError("getHypothesisEncounters: ownShip is [x, y, vx, vy] (got %d components)" % len(own))
+        dpsi, fs = np.asarray(courseChanges, dtype=np.float64).reshape(-1), np.asarray(speedFactors, dtype=np.float64).reshape(-1)
+        if len(dpsi) == 0 or len(fs) == 0:
+            raise ValueError("getHypothesisEncounters: courseChanges and speedFactors need one value at least")
+        if turnRate is None:
+            if np.any(dpsi != 0):
+                raise ValueError("getHypothesisEncounters: turnRate is required with a course change that is not 0")
+            turnRate = 1.0      # (no candidate turns: the rate enters no figure)
+        try:
+            cand = evaluation.trial_candidates([(a, f, float(delay)) for a in dpsi for f in fs])
+        except ValueError as exc:
+            raise ValueError("getHypothesisEncounters: " + str(exc))
+        nodes = list(self.__trackNodes__)
+        T = len(nodes)
+        ids = [int(i) for i in self._tbl_["id"]]
+        if T:
+            snap = self.leafBatch()
+            sel = np.full(T, -1, dtype=np.int64)
+            for t, nd in enumerate(nodes):
+                own_leaves = snap["target"] == t
+                if nd._node < 0:      # (born after the last scan: the track node is the root itself, the target's only leaf)
+                    hit = np.flatnonzero(own_leaves) if own_leaves.sum() == 1 else ()
+                else:
+                    hit = np.flatnonzero(own_leaves & (snap["node"] == nd._node))
+                if len(hit):
+                    sel[t] = hit[0]
+            x, P, cn, tg, leaf_ids = snap["x"], np.asarray(snap["P"], dtype=np.float64), snap["cnllr"], snap["target"], snap["ID"].astype(np.int64)
+        else:
+            x, P, cn, tg, sel, leaf_ids = np.zeros((0, nx)), np.zeros((0, nx, nx)), np.zeros(0), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+        try:
+            out = evaluation.trial_hypotheses(x, P, cn, tg, Phi, Q, steps, dt, float(radius), own, cand, turnRate, selected=sel, ownCovariance=ownCovariance,
+                                              leafTable=leafTable, ctx=self._ctx)
+        except ValueError as exc:
+            raise ValueError("getHypothesisEncounters: " + str(exc))
+        out["ids"], out["leafIds"] = ids, leaf_ids
+        G = len(cand)
+        for name, src, largest in (("pcMeanMax", "pcMean", True), ("pcWorstMax", "pcWorst", True), ("dcpaMinAll", "dcpaMin", False)):
+            val, arg = np.full(G, np.nan), np.full(G, -1, dtype=np.int64)
+            for g in range(G):
+                row = out[src][g]
+                if not np.isnan(row).all():
+                    val[g] = np.nanmax(row) if largest else np.nanmin(row)
+                    arg[g] = int(np.flatnonzero(row == val[g])[0])
+            out[name], out[name + "Target"] = val, arg
+        out["best"] = evaluation.trial_best(out["pcMeanMax"], out["dcpaMinAll"])
+        out["bestWorstCase"] = evaluation.trial_best(out["pcWorstMax"], out["dcpaMinAll"])
+        return out
+
     def getOspa2(self, truth, c, p=2, window=None, every=1, terminated=True, smooth=False, constantTurn=False, ais=False, truthIds=None):
         """The track histories scored against the truth TRAJECTORIES: OSPA(2) over windows of steps (evaluation.ospa2_windows, which
         defines the figures).  Per-scan GOSPA assigns every scan on its own, so this is the figure that sees whether the targets were
