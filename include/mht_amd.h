@@ -893,7 +893,7 @@ int mht_forest_set_timing(mht_ctx* ctx, int32_t enable);
 int mht_forest_stage_times(mht_ctx* ctx, float* ms5, int32_t* n_steps);
 /* Tooling: copy a named internal per-cluster array of the last step to the host ("cl_status", "cl_iters",
  * "cl_nodes", "cl_time" [2 int32 per cluster: setup / total in 10 ns ticks], "cl_ptr", "cl_members", "multi_list",
- * "cl_counts", "cl_owner", "team_list", "tchild").  Synchronises. */
+ * "single_list", "cl_counts", "cl_owner", "team_list", "tchild").  Synchronises. */
 int mht_forest_debug_read(mht_ctx* ctx, const char* name, void* host, int64_t bytes);
 /* Ancestor chain of one node: walks parents from (scan, node) towards the root of time, at most max_len steps
  * (bounded by the ring of n_scan + 4 layers: with k scans queued behind `scan`, n_scan + 4 - k layers are left).  Outputs host arrays

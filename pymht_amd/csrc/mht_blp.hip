@@ -94,6 +94,21 @@ __device__ __forceinline__ double wave_sum(double v) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
+// wave64 INCLUSIVE prefix sum of a 32-bit value, the same row shifts / row broadcasts: six VALU adds where a __shfl_up scan pays an
+// LDS-crossbar permute per step (two for a 64-bit value).  Every lane of the wavefront must be active.
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ unsigned dpp_u32(unsigned v) {
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ unsigned wave_scan_u32(unsigned v) {
+    v += dpp_u32<0x111, 0xf>(v);      // row_shr:1
+    v += dpp_u32<0x112, 0xf>(v);      // row_shr:2
+    v += dpp_u32<0x114, 0xf>(v);      // row_shr:4
+    v += dpp_u32<0x118, 0xf>(v);      // row_shr:8   -> inclusive within every row of 16
+    v += dpp_u32<0x142, 0xa>(v);      // row_bcast:15: the sum of row 0 into row 1, of row 2 into row 3
+    v += dpp_u32<0x143, 0xc>(v);      // row_bcast:31: the sum of rows 0 and 1 into rows 2 and 3
+    return v;
+}
+
 __device__ __forceinline__ double block_sum(double v, Red* r) {
     v = wave_sum(v);
     __syncthreads();
@@ -1889,14 +1904,9 @@ template <typename AT> __device__ __forceinline__ void solve_cluster(AT* ap, con
                     if (pre_ok && K <= 64) { gb = pre.cb; n = pre.ce - gb; }      // (k = tid: the member's record is at hand)
                     else { const int t = mem[k]; gb = a.tchild[t]; n = a.tcend[t] - gb; }
                 }
-                int incl = n;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int v = __shfl_up(incl, o);
-                    if (tid >= o) incl += v;
-                }
+                const int incl = (int)wave_scan_u32((unsigned)n);
                 if (k < K) { s.colb[k] = carry + incl - n; s.gbase[k] = gb; if (pre_ok && K <= 64) s.lix[k] = pre.j; }      // (lix: the member's prune depth until the solver takes the table -- the copy below prefetches the survivors' sweep with it)
-                carry += __shfl(incl, 63);
+                carry += __builtin_amdgcn_readlane(incl, 63);
             }
             if (tid == 0) { s.colb[K] = carry; s_nH = carry; }
         }
@@ -1990,14 +2000,9 @@ template <typename AT> __device__ __forceinline__ void solve_cluster(AT* ap, con
             for (int base = 0; base < UW; base += 64) {
                 const int w = base + tid;
                 const int pc = (w < UW) ? __popcll(uw[w]) : 0;
-                int incl = pc;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int v = __shfl_up(incl, o);
-                    if (tid >= o) incl += v;
-                }
+                const int incl = (int)wave_scan_u32((unsigned)pc);
                 if (w < UW) s_wbase[w] = carry + incl - pc;
-                carry += __shfl(incl, 63);
+                carry += __builtin_amdgcn_readlane(incl, 63);
             }
             if (tid == 0) s_nR = carry;
         }
@@ -2355,42 +2360,42 @@ template <typename AT> __device__ __forceinline__ bool uf_prologue(AT* ap, const
     __syncthreads();
     UF_STAMP(2);
     // ONE block scan over the targets in index order (thread = a run of E consecutive targets): heads -> cluster index, their sizes ->
-    // member offset, ranks among the multi-target / single-target / team-sized clusters, packed 14 + 13 + 14 + 14 + 9 bits (max_targets 8 192:
-    // at most 8 192 clusters, 4 096 of them with two or more targets, 341 with TEAM_MIN_K or more -- no field can wrap)
+    // member offset, ranks among the multi-target / team-sized clusters, in two 32-bit words that no field's carry crosses -- lo: clusters
+    // (14 bits) | multi-target ones << 14 (13 bits), hi: members (14 bits) | team-sized ones << 14 (9 bits) (max_targets 8 192: at most 8 192
+    // clusters, 4 096 of them with two or more targets, 341 with TEAM_MIN_K or more -- no field can wrap).  A cluster has one target or
+    // several: the rank among the single-target clusters is the cluster index minus the rank among the multi-target ones.
     const int E = (nT + BLP_THREADS - 1) / BLP_THREADS;
-    auto pack_of = [&](int t) -> unsigned long long {
-        if (t >= nT || lab[t] != t) return 0ull;
-        const unsigned long long K = (unsigned long long)cnt[t];
-        return 1ull | ((K >= 2 ? 1ull : 0ull) << 14) | ((K == 1 ? 1ull : 0ull) << 27) | (K << 41) | ((K >= (unsigned long long)TEAM_MIN_K ? 1ull : 0ull) << 55);
+    auto pack_of = [&](int t) -> uint2 {
+        if (t >= nT || lab[t] != t) return make_uint2(0u, 0u);
+        const unsigned K = (unsigned)cnt[t];
+        return make_uint2(1u | ((K >= 2u ? 1u : 0u) << 14), K | ((K >= (unsigned)TEAM_MIN_K ? 1u : 0u) << 14));
     };
-    unsigned long long mine = 0ull;
-    for (int e = 0; e < E; ++e) mine += pack_of(tid * E + e);
-    unsigned long long incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-    }
-    if (lane == 63) s_w[wave] = incl;
+    uint2 mine = make_uint2(0u, 0u);
+    for (int e = 0; e < E; ++e) { const uint2 v = pack_of(tid * E + e); mine.x += v.x; mine.y += v.y; }
+    const uint2 incl = make_uint2(wave_scan_u32(mine.x), wave_scan_u32(mine.y));
+    if (lane == 63) s_w[wave] = (unsigned long long)incl.x | ((unsigned long long)incl.y << 32);
     __syncthreads();
     UF_STAMP(3);
-    unsigned long long run = incl - mine, total = 0ull;
+    uint2 run = make_uint2(incl.x - mine.x, incl.y - mine.y), total = make_uint2(0u, 0u);
 #pragma unroll
-    for (int w = 0; w < BLP_THREADS / 64; ++w) { const unsigned long long v = s_w[w]; if (w < wave) run += v; total += v; }
-    const int nC = (int)(total & 0x3fffu), nMulti = (int)((total >> 14) & 0x1fffu), nSingle = (int)((total >> 27) & 0x3fffu);
-    const int nTeamAll = (int)(total >> 55), nTeam = (a.team_list && nTeamAll > 0) ? (nTeamAll < TEAM_MAX ? nTeamAll : TEAM_MAX) : 0;
+    for (int w = 0; w < BLP_THREADS / 64; ++w) {
+        const unsigned long long v = s_w[w];
+        if (w < wave) { run.x += (unsigned)v; run.y += (unsigned)(v >> 32); }
+        total.x += (unsigned)v; total.y += (unsigned)(v >> 32);
+    }
+    const int nC = (int)(total.x & 0x3fffu), nMulti = (int)(total.x >> 14), nSingle = nC - nMulti;
+    const int nTeamAll = (int)(total.y >> 14), nTeam = (a.team_list && nTeamAll > 0) ? (nTeamAll < TEAM_MAX ? nTeamAll : TEAM_MAX) : 0;
     for (int e = 0; e < E; ++e) {
         const int t = tid * E + e;
-        const unsigned long long pk = pack_of(t);
-        if (pk) {
-            const int c = (int)(run & 0x3fffu), mr = (int)((run >> 14) & 0x1fffu), sr = (int)((run >> 27) & 0x3fffu), p0 = (int)((run >> 41) & 0x3fffu), tr = (int)(run >> 55);
-            const int K = cnt[t];
-            par[t] = (unsigned short)c;       // (the parents are dead: cluster index by head)
-            hp[t] = (unsigned short)p0;
-            if (K >= 2) ml[mr] = (unsigned short)t; else sl[sr] = (unsigned short)t;
-            if (K >= TEAM_MIN_K && tr < TEAM_MAX) s_tl[tr] = t;
-            run += pk;
-        }
+        const uint2 v = pack_of(t);
+        if (!v.x) continue;
+        const int c = (int)(run.x & 0x3fffu), mr = (int)(run.x >> 14), p0 = (int)(run.y & 0x3fffu), tr = (int)(run.y >> 14);
+        const int K = (int)(v.y & 0x3fffu);
+        par[t] = (unsigned short)c;       // (the parents are dead: cluster index by head)
+        hp[t] = (unsigned short)p0;
+        if (K >= 2) ml[mr] = (unsigned short)t; else sl[c - mr] = (unsigned short)t;
+        if (K >= TEAM_MIN_K && tr < TEAM_MAX) s_tl[tr] = t;
+        run.x += v.x; run.y += v.y;
     }
     __syncthreads();
     UF_STAMP(4);

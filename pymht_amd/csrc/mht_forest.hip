@@ -54,6 +54,7 @@ struct Switches {
     bool debug = getenv("MHT_GROW_DEBUG") != nullptr;             // set (to anything, as mht_gate.hip reads it): phase stamps (with -DMHT_GROW_STAMPS), forced storage policies
     bool ct_spill = env_flag("MHT_CT_SPILL", false);              // testing: fgrow_ct_kernel keeps every target's hit masks in the global spill block
     bool grid_by_hint = env_flag("MHT_BLP_GRID_HINT", true);      // 0: the ILP launch sized by the target count alone, as until round 5
+    int blp_grid = (int)env_int("MHT_BLP_GRID", 0);               // testing: at most this many workgroups in a union-find ILP launch (never fewer than its tables need)
     bool force_hbm = env_flag("MHT_BLP_FORCE_HBM", false);        // testing: every ILP through the HBM storage policy
     bool no_enum = env_flag("MHT_BLP_NO_ENUM", false);            // testing: no exact search for small clusters (branch and bound instead)
     bool no_reduce = env_flag("MHT_BLP_NO_REDUCE", false);        // (BlpArgs::no_reduce)
@@ -1359,6 +1360,10 @@ static int blp_hint_grid(const Forest* f, int s, bool use_uf, int grid) {
         if (gh < g_min) gh = g_min;
         if (gh < grid) grid = gh;
     }
+    if (f->sw.blp_grid > 0 && f->sw.blp_grid < grid) {      // (testing: workgroups with several clusters; the same floor as above)
+        const int g_min = f->nT_ub_step / 8 + 1;
+        grid = f->sw.blp_grid > g_min ? f->sw.blp_grid : g_min;
+    }
     return grid;
 }
 // The initiator's arguments for scan s.  used_words: the scan's committed used-measurement mask (the initiator runs behind the commit:
@@ -2389,6 +2394,7 @@ extern "C" int mht_forest_debug_read(mht_ctx* ctx, const char* name, void* host,
     else if (!strcmp(name, "cl_ptr")) { src = f->cl_ptr; avail = (T + 1) * 4; }
     else if (!strcmp(name, "cl_members")) { src = f->cl_members; avail = T * 4; }
     else if (!strcmp(name, "multi_list")) { src = f->multi_list; avail = T * 4; }
+    else if (!strcmp(name, "single_list")) { src = f->single_list; avail = T * 4; }
     else if (!strcmp(name, "cl_counts")) { src = f->cl_counts; avail = 8 * 4; }
     else if (!strcmp(name, "cl_owner")) { src = f->cl_owner; avail = T * 4; }
     else if (!strcmp(name, "team_list")) { src = f->team_list; avail = TEAM_MAX * 4; }
