@@ -14,33 +14,22 @@ mht_forest_add_targets without its neighbour test, which turns away a target wit
 keeps in registers across the scan (1 024 against 1 025), a cluster beyond the 64 members wavefront 0 ranks in registers, a team-sized
 cluster (the writer's path in every workgroup), more multi-target clusters than workgroups."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
+
+from group_blp_util import N_SCANS, _rd, _runs_mixed, _scene, _tracker
 
 pytestmark = pytest.mark.gpu
 
 INST_TABLES, INST_UF, INST_UF_PLAIN = 1, 2, 3      # mht_kernels.h: BlpInstance
 TEAM_MIN_K = 24                                    # mht_kernels.h
-PERIOD, P_D, LAMBDA_PHI, N_SCANS = 2.5, 0.9, 1.0e-5, 3
-SPACING, GAP, ROW, WIDTH = 12.0, 60.0, 80.0, 1500.0
 TABLES = ("cl_ptr", "cl_members", "multi_list", "single_list", "t_label")
 # cluster_kernel hands out the slots of these two lists by atomic counter (mht_cluster.hip: "the (atomic) order of multi_list"): beyond one
 # wavefront its order changes from run to run.  The prologue's lists are ascending; the clustering kernel's must hold the same entries, so
 # they are compared sorted -- against the prologue's own order, which is thereby asserted ascending.  The two prologue instances are
 # compared entry for entry.
 ATOMIC_ORDER = ("multi_list", "single_list")
-
-
-def _runs_mixed(nT):
-    """mostly lone targets, pairs and triples between them, cut off at nT targets"""
-    pattern, out, k = (1, 1, 2, 1, 3, 1, 1, 2, 1, 1, 1, 4), [], 0
-    while sum(out) < nT:
-        out.append(min(pattern[k % len(pattern)], nT - sum(out)))
-        k += 1
-    return out
-
 
 # name -> (runs, environment of every tracker of the scene)
 SCENES = {("nT%d" % n): (_runs_mixed(n), {}) for n in (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025)}
@@ -51,61 +40,6 @@ SCENES.update({
     "team_min_k": ([2, TEAM_MIN_K, 1, 3], {}),
     "clusters_beyond_grid": ([3] * 80, {"MHT_BLP_GRID": "1"}),      # 80 multi-target clusters, 240 / 8 + 1 = 31 workgroups
 })
-
-
-def _scene(runs, seed=5446):
-    rng = np.random.default_rng(seed)
-    pos, links, x, y = [], [], 0.0, 0.0
-    for K in runs:
-        if x + K * SPACING > WIDTH:
-            x, y = 0.0, y + ROW
-        for m in range(K):
-            pos.append((x, y))
-            if m:
-                links.append((x - 0.5 * SPACING, y))
-            x += SPACING
-        x += GAP - SPACING
-    pos, links = np.array(pos, dtype=np.float64).reshape(-1, 2), np.array(links, dtype=np.float64).reshape(-1, 2)
-    x0 = np.concatenate([pos, np.zeros_like(pos)], axis=1)
-    scans = []
-    for _ in range(N_SCANS):
-        z = np.concatenate([pos + rng.normal(0.0, 0.3, size=pos.shape), links + rng.normal(0.0, 0.3, size=links.shape)], axis=0)
-        rng.shuffle(z, axis=0)
-        scans.append(np.ascontiguousarray(z, dtype=np.float32).reshape(-1, 2))
-    return x0, scans
-
-
-def _tracker(x0, env):
-    from pymht_amd import _lib
-    from pymht_amd.tracker import Tracker
-    from pymht_amd.models import pv
-    names = ("MHT_BLP_GENERIC", "MHT_NO_UF", "MHT_BLP_GRID")
-    old = {n: os.environ.pop(n, None) for n in names}
-    os.environ.update(env)      # (read when the forest is created)
-    try:
-        trk = Tracker(pv, PERIOD, LAMBDA_PHI, 1e-4, P_d=P_D, N=3, eta2=5.99, useInitiator=False, maxTargets=2048, maxNodes=1 << 18,
-                      maxMeasurements=2048)
-        n = len(x0)
-        xs = np.ascontiguousarray(x0, dtype=np.float64)
-        P0 = np.ascontiguousarray(np.tile(np.asarray(pv.P0, dtype=np.float32).reshape(1, 16), (n, 1)))
-        flags, pd, meas = np.zeros(n, dtype=np.uint8), np.full(n, P_D, dtype=np.float64), np.zeros(n, dtype=np.int32)
-        acc, ids = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        _lib.check(trk._lib.mht_forest_add_targets(trk._ctx.handle, n, p(xs), p(P0), p(flags), p(pd), p(meas), 0, p(acc), p(ids)))
-        assert acc.all()
-    finally:
-        for n in names:
-            os.environ.pop(n, None)
-            if old[n] is not None:
-                os.environ[n] = old[n]
-    return trk
-
-
-def _rd(trk, name, n):
-    from pymht_amd import _lib
-    a = np.zeros(max(int(n), 1), dtype=np.int32)
-    _lib.check(trk._lib.mht_forest_debug_read(trk._ctx.handle, name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes))
-    return a[:int(n)]
 
 
 def _scan_results(trk, k):
