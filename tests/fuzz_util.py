@@ -270,10 +270,12 @@ def similar_draw(seed, similar, n_scans):
     return thr, [bool(similar and prng.uniform() < 0.75) for _ in range(n_scans)]
 
 
-def scene_of(sc, N, eta2, thr, on, desc, model="ca", tails=None):
-    """A scene: scenario, window, gate, merge radius, the per-scan pruning switches and the roots of the model ([x4, ax, ay] for ca)."""
+def scene_of(sc, N, eta2, thr, on, desc, model="ca", tails=None, P0s=None, kinds=None, max_meas=512):
+    """A scene: scenario, window, gate, merge radius, the per-scan pruning switches and the roots of the model ([x4, ax, ay] for ca,
+    [x4, w, a] for ct).  P0s: one covariance per root (None: the model's P0 for every root); kinds: the turn-rate kinds of ct roots
+    (ct_draw); max_meas: the forest's maxMeasurements."""
     x0 = sc["x0"] if model == "pv" else np.concatenate([sc["x0"], np.zeros((len(sc["x0"]), 2)) if tails is None else tails], axis=1)
-    return dict(sc=sc, N=int(N), eta2=float(eta2), thr=thr, on=list(on), desc=desc, model=model, x0=x0)
+    return dict(sc=sc, N=int(N), eta2=float(eta2), thr=thr, on=list(on), desc=desc, model=model, x0=x0, P0s=P0s, kinds=kinds, max_meas=int(max_meas))
 
 
 def ca_scene(seed, similar=False):
@@ -299,9 +301,11 @@ def crafted_scene(name, model="ca"):
 LONG_WINDOWS = {8: dict(T=15, P_d=0.8, seed=31), 9: dict(T=10, P_d=0.85, seed=32)}
 
 
-def long_window_scene(N):
-    """Windows of 8 and 9 scans: path records of 16 ints, targets of more than 128 leaves."""
+def long_window_scene(N, model="ca"):
+    """Windows of 8 and 9 scans: path records of 16 ints, targets of more than 128 leaves.  model="ct": ct_long_window_scene."""
     from pymht_amd.utils.scenario import make_scenario
+    if model == "ct":
+        return ct_long_window_scene(N)
     p = LONG_WINDOWS[N]
     sc = make_scenario(T=p["T"], radius=400.0, lambda_phi=1e-5, n_scans=12, P_d=p["P_d"], seed=p["seed"])
     return scene_of(sc, N, 5.99, 4, [False] * 12, 'long window N=%d: T=%d Pd=%.2f' % (N, p["T"], p["P_d"]), tails=ca_tails(p["seed"], p["T"]))
@@ -325,9 +329,107 @@ def sector_scenes():
             scene_of(b, 3, 5.99, 4, [False] * 10, 'sector 1', tails=ca_tails(42, 30))]
 
 
+# ---- constant-turn forests (Tracker(pymht_amd.models.ct, ...)) in the same deterministic runner ---------------------------------------------
+# run_case_ct above stops on a clock; these scenes stop on the leaf cap alone, and oracle_run counts for them what fgrow_ct_kernel's own
+# paths depend on (ct_grow_census).  tests/test_ct_fuzz_cpu.py asserts that census without a device.
+# (twelve seeds each out of the ranges of test_fuzz_slice_constant_turn and test_constant_turn_forest_similar_state_pruning, picked with the
+# census: windows of 1 .. 7 scans, candidate lists of more than 64 measurements (5, 12, 51), targets of more than 128 leaves, groups of three hits)
+CT_PLAIN_SEEDS = [CA_SEED0 + 700000 + i for i in (0, 2, 5, 6, 8, 9, 12, 20, 26, 51, 59, 69)]
+CT_SIMILAR_SEEDS = [880000 + i for i in (0, 6, 9, 10, 11, 13, 19, 22, 23, 24, 29, 30)]
+CT_KINDS = 5      # turn-rate kinds of a root: 0 exactly zero, 1 |w| < 1e-9 (below the model's straight-line threshold), 2 N(0, 0.02), 3 U(-0.6, 0.6), 4 N(0, 0.15)
+CT_CHUNK = 128    # leaves of a chunk of fgrow_ct_kernel (FG_CAP)
+
+
+def ct_draw(seed, T):
+    """(kind, [w, a]) per root from default_rng(seed + 4242), draw for draw as run_case_ct: the five kinds of turn rate (CT_KINDS), a exactly 0
+    for half of the roots and N(0, 1e-3) for the others."""
+    prng = np.random.default_rng(seed + 4242)
+    kind = prng.integers(0, 5, size=T)
+    w = np.where(kind == 0, 0.0, np.where(kind == 1, prng.uniform(-1e-9, 1e-9, size=T), np.where(kind == 2, prng.normal(0.0, 0.02, size=T),
+                 np.where(kind == 3, prng.uniform(-0.6, 0.6, size=T), prng.normal(0.0, 0.15, size=T)))))
+    a = np.where(prng.uniform(size=T) < 0.5, 0.0, prng.normal(0.0, 1e-3, size=T))
+    return kind, np.stack([w, a], axis=1)
+
+
+def ct_tails(seed, T):
+    """[w, a] per root, exactly as run_case_ct draws them."""
+    return ct_draw(seed, T)[1]
+
+
+def ct_scene(seed, similar=False):
+    sc, N, eta2, desc = scenario_of(seed)
+    thr, on = similar_draw(seed, similar, len(sc["scans"]))
+    kinds, tails = ct_draw(seed, len(sc["x0"]))
+    return scene_of(sc, N, eta2, thr, on, desc + ' CT |w|max=%.3f' % float(np.abs(tails[:, 0]).max()) + (' similar thr=%.0f' % thr if similar else ''),
+                    model="ct", tails=tails, kinds=kinds)
+
+
+def ct_long_window_scene(N):
+    """long_window_scene's streams under models.ct: turn rates N(0, 0.05) from default_rng(seed + 4242), turn-rate derivatives 0."""
+    from pymht_amd.utils.scenario import make_scenario
+    p = LONG_WINDOWS[N]
+    sc = make_scenario(T=p["T"], radius=400.0, lambda_phi=1e-5, n_scans=12, P_d=p["P_d"], seed=p["seed"])
+    w = np.random.default_rng(p["seed"] + 4242).normal(0.0, 0.05, size=p["T"])
+    return scene_of(sc, N, 5.99, 4, [False] * 12, 'long window N=%d (ct): T=%d Pd=%.2f' % (N, p["T"], p["P_d"]), model="ct",
+                    tails=np.stack([w, np.zeros(p["T"])], axis=1))
+
+
+CT_LONG_CAP = {8: None, 9: 4000}      # leaf cap of the long-window scenes (N = 9 grows past what a test of a few seconds holds)
+
+# two-scan streams of dense clutter in which root 0 starts with a position variance of sigma^2 (the others with ct.P0): its gate box holds
+# hundreds of measurements -- the widths of fgrow_ct_kernel's hit masks over the candidate list (2 .. FG_HWC = 6 words per leaf in LDS) and,
+# past 384 candidates, the full-width masks in global memory beside targets that stay in LDS.  (T, radius, lambda_phi, N, seed, sigma)
+WIDE_GATE = {"a": (4, 150.0, 2e-2, 1, 61, 30.0), "b": (4, 200.0, 1e-2, 2, 62, 40.0), "c": (4, 150.0, 2e-2, 1, 64, 25.0), "d": (4, 200.0, 1e-2, 2, 64, 45.0),
+             "e": (4, 200.0, 1e-2, 1, 63, 45.0)}
+
+
+def wide_gate_scene(name):
+    """Zero tails, eta2 5.99, P_d 0.9, no similar-state pruning, two scans; the forest takes 2 048 measurements per scan."""
+    from pymht_amd.utils.scenario import make_scenario
+    from pymht_amd.models import ct
+    T, radius, lam, N, seed, sigma = WIDE_GATE[name]
+    sc = make_scenario(T=T, radius=radius, lambda_phi=lam, n_scans=2, P_d=0.9, seed=seed)
+    wide = np.array(ct.P0, copy=True)
+    wide[0, 0] = wide[1, 1] = sigma * sigma
+    return scene_of(sc, N, 5.99, 4, [False] * 2, 'wide gate %s: T=%d r=%.0f lam=%.1e N=%d sigma=%.0f' % (name, T, radius, lam, N, sigma), model="ct",
+                    P0s=[wide] + [ct.P0] * (T - 1), max_meas=2048)
+
+
+def ct_grow_census(r, C, eta2, z):
+    """What one call of process_leaves_ct (one target, one scan) asks of fgrow_ct_kernel, from the oracle's own x_bar, S and gate indices in
+    float64:
+      cand      measurements inside the union over the target's leaves of z_hat +- sqrt(eta2 diag S), the bounding box of the leaf's exact
+                gate.  A LOWER bound on the device's candidate list: the device takes the measurements inside one box around all of its
+                leaves' boxes, and every leaf's box there is widened (conservative in float32) -- its list is never shorter;
+      leaves    the leaf count;
+      children  the sum over the leaves of 1 + hits;
+      chunk     the largest such sum over CT_CHUNK consecutive leaves (the children of one chunk of the kernel)."""
+    x_bar, S = np.asarray(r["x_bar"], dtype=np.float64), np.asarray(r["S"], dtype=np.float64)
+    z_hat = x_bar.dot(np.asarray(C, dtype=np.float64).T)
+    half = np.sqrt(float(eta2) * np.stack([S[:, 0, 0], S[:, 1, 1]], axis=1))
+    zz = np.asarray(z, dtype=np.float64).reshape(-1, 2)
+    inside = np.zeros(len(zz), dtype=bool)
+    for i in range(len(z_hat)):
+        inside |= np.all(np.abs(zz - z_hat[i]) <= half[i], axis=1)
+    kids = 1 + np.array([len(i) for i in r["idx"]], dtype=np.int64)
+    return dict(cand=int(inside.sum()), leaves=len(kids), children=int(kids.sum()),
+                chunk=int(max(kids[c:c + CT_CHUNK].sum() for c in range(0, len(kids), CT_CHUNK))))
+
+
+def ct_grow_rows(census):
+    """The (scan, target, figures) rows of a constant-turn census."""
+    return [(k, ti, g) for k, scan in enumerate(census["grow"]) for ti, g in enumerate(scan)]
+
+
 def _model_of(scene):
-    from pymht_amd.models import pv, ca
-    return {"pv": pv, "ca": ca}[scene["model"]]
+    from pymht_amd.models import pv, ca, ct
+    return {"pv": pv, "ca": ca, "ct": ct}[scene["model"]]
+
+
+def _root_covariances(scene):
+    """One covariance per root: scene["P0s"], or the model's P0 for every root."""
+    P0 = _model_of(scene).P0
+    return [P0] * len(scene["x0"]) if scene.get("P0s") is None else list(scene["P0s"])
 
 
 def oracle_run(scene, max_leaves=None):
@@ -340,9 +442,9 @@ def oracle_run(scene, max_leaves=None):
     nx = scene["x0"].shape[1]
     o = orc.OracleTracker(sc["period"], sc["lambda_phi"], 1e-4, P_d=sc["P_d"], N=scene["N"], eta2=scene["eta2"], initiator=None,
                           model=None if scene["model"] == "pv" else model)
-    acc = [o.initiate_target(sc["t0"], x.copy(), model.P0.copy(), status="preinitialized") for x in scene["x0"]]
-    groups, merged = [], []
-    plain = orc.Node.prune_similar
+    acc = [o.initiate_target(sc["t0"], x.copy(), np.array(P0, copy=True), status="preinitialized") for x, P0 in zip(scene["x0"], _root_covariances(scene))]
+    groups, merged, grown = [], [], []
+    plain, plain_ct = orc.Node.prune_similar, orc.process_leaves_ct
 
     def counting(node, threshold):
         before = len(node.kids)
@@ -351,15 +453,25 @@ def oracle_run(scene, max_leaves=None):
             groups.append(before - len(node.kids))
             merged.append(node.kids[0])
 
+    def counting_ct(phi, T, Q, C, R, eta2, lambda_ex, x, P, P_d, z):
+        r = plain_ct(phi, T, Q, C, R, eta2, lambda_ex, x, P, P_d, z)
+        grown.append(ct_grow_census(r, C, eta2, z))
+        return r
+
     census = dict(ilp=0, cluster=0, dead=0, L=0, groups=groups, scans=0, merged_leaves=0)
+    if scene["model"] == "ct":
+        census.update(grow=[], kinds=[] if scene.get("kinds") is None else sorted(set(int(q) for q in scene["kinds"])))
     recs = []
-    orc.Node.prune_similar = counting
+    orc.Node.prune_similar, orc.process_leaves_ct = counting, counting_ct
     try:
         for k, (z, t) in enumerate(zip(sc["scans"], sc["times"])):
             if max_leaves is not None and k > 0 and recs[-1]["L"] > max_leaves:
                 break
             del merged[:]
+            del grown[:]
             info = o.add_scan(float(t), z, prune_similar=scene["on"][k], prune_threshold=scene["thr"])
+            if scene["model"] == "ct":
+                census["grow"].append(list(grown))      # (one entry per target, in the order of the target list in front of the scan)
             leaves = [l for r in o.targets for l in r.leaves()]
             m_ids = set(id(n) for n in merged)
             lb, sel = oracle_rows(leaves, nx), oracle_rows(o.track_nodes, nx)
@@ -372,7 +484,7 @@ def oracle_run(scene, max_leaves=None):
             census["L"] = max(census["L"], info["L"])
             census["merged_leaves"] += int(recs[-1]["merged"].sum())
     finally:
-        orc.Node.prune_similar = plain
+        orc.Node.prune_similar, orc.process_leaves_ct = plain, plain_ct
     census["scans"] = len(recs)
     census["groups"] = list(groups)
     return dict(accepted=acc, scans=recs, census=census)
@@ -388,19 +500,33 @@ def _rows_close(a, b, rel):
     return states_close(a, np.asarray(b, dtype=np.float64), rel=rel)
 
 
-def device_run(scene, rec, streamed=False):
+def device_run(scene, rec, streamed=False, spill=False):
     """A Tracker over the scans the oracle ran, against its record.  Looked at after every scan: L, G, unused measurements, target ids,
     ILPs, selections, clusters member for member, leaf ids and measurement numbers exactly; states and covariances of ALL leaves (the
-    merged ones once more on their own) at FUZZ_REL, cumulative scores at SCORE_ATOL; no leaf carries flag 8.  streamed: nothing is looked
-    at in between -- the per-scan numbers come from the tracker's log, the rest is compared at the end.  Returns (ok, message)."""
+    merged ones once more on their own) at FUZZ_REL -- in a constant-turn scene at the 1e-6 run_case_ct holds them to, whatever FUZZ_REL
+    says: the device's sin / cos may round an entry of Phi(T, w) one ulp away from NumPy's --, cumulative scores at SCORE_ATOL; no leaf
+    carries flag 8.  streamed: nothing is looked at in between -- the per-scan numbers come from the tracker's log, the rest is compared
+    at the end.  spill: MHT_CT_SPILL=1 while the Tracker is made (fgrow_ct_kernel then keeps every target's hit masks in the global
+    block).  Returns (ok, message)."""
     from test_tracker_gpu import tracker_selected, SCORE_ATOL
     from pymht_amd.tracker import Tracker
     from pymht_amd.pyTarget import Target
     from pymht_amd.utils.classDefinitions import MeasurementList
     sc, model = scene["sc"], _model_of(scene)
     nx = scene["x0"].shape[1]
-    trk = Tracker(model, sc["period"], sc["lambda_phi"], 1e-4, P_d=sc["P_d"], N=scene["N"], eta2=scene["eta2"], useInitiator=False, maxTargets=256,
-                  maxNodes=1 << 18, maxMeasurements=512, pruneThreshold=scene["thr"], logScanStats=streamed)
+    rel = 1e-6 if scene["model"] == "ct" else FUZZ_REL
+    before = os.environ.get("MHT_CT_SPILL")
+    if spill:
+        os.environ["MHT_CT_SPILL"] = "1"
+    try:
+        trk = Tracker(model, sc["period"], sc["lambda_phi"], 1e-4, P_d=sc["P_d"], N=scene["N"], eta2=scene["eta2"], useInitiator=False, maxTargets=256,
+                      maxNodes=1 << 18, maxMeasurements=scene.get("max_meas", 512), pruneThreshold=scene["thr"], logScanStats=streamed)
+    finally:
+        if spill:
+            if before is None:
+                del os.environ["MHT_CT_SPILL"]
+            else:
+                os.environ["MHT_CT_SPILL"] = before
     t0 = time.time()
 
     def state_checks(r):
@@ -413,17 +539,17 @@ def device_run(scene, rec, streamed=False):
                 ("selected states", _rows_close(os_["x"], ts["x"], 1e-6) and np.allclose(os_["cnllr"], ts["cnllr"], rtol=0, atol=SCORE_ATOL)),
                 ("clusters", len(r["clusters"]) == len(trk.__clusterList__) and all(np.array_equal(a, np.asarray(b)) for a, b in zip(r["clusters"], trk.__clusterList__))),
                 ("leaves", same_leaves),
-                ("leaf states", same_leaves and _rows_close(lb["x"], tb["x"], FUZZ_REL)),
-                ("leaf covariances", same_leaves and _rows_close(lb["P"], tb["P"], FUZZ_REL)),
-                ("merged leaves' covariances", same_leaves and _rows_close(lb["P"][m], tb["P"][m], FUZZ_REL)),
+                ("leaf states", same_leaves and _rows_close(lb["x"], tb["x"], rel)),
+                ("leaf covariances", same_leaves and _rows_close(lb["P"], tb["P"], rel)),
+                ("merged leaves' covariances", same_leaves and _rows_close(lb["P"][m], tb["P"][m], rel)),
                 ("leaf scores", same_leaves and np.allclose(lb["cnllr"], tb["cnllr"], rtol=0, atol=SCORE_ATOL)),
                 ("flag 8", not np.any(tb["flags"] & 8))]
 
     try:
         acc = []
-        for x in scene["x0"]:
+        for x, P0 in zip(scene["x0"], _root_covariances(scene)):
             n0 = trk.nTargets
-            trk.initiateTarget(Target(sc["t0"], None, x.copy(), model.P0, status="preinitialized"))
+            trk.initiateTarget(Target(sc["t0"], None, x.copy(), P0, status="preinitialized"))
             acc.append(trk.nTargets > n0)
         if acc != rec["accepted"]:
             return False, 'MISMATCH: the roots the device admits'
@@ -445,7 +571,7 @@ def device_run(scene, rec, streamed=False):
             checks += state_checks(rec["scans"][-1])
             if not all(c for _, c in checks):
                 return False, 'MISMATCH (streamed): %s' % ', '.join(n for n, c in checks if not c)
-        return True, '%s%d scans %.1fs' % ('streamed ' if streamed else '', len(rec["scans"]), time.time() - t0)
+        return True, '%s%s%d scans %.1fs' % ('streamed ' if streamed else '', 'spill ' if spill else '', len(rec["scans"]), time.time() - t0)
     finally:
         trk.close()
 
@@ -467,4 +593,17 @@ def add_census(total, c):
     total["cluster"] = max(total.get("cluster", 0), c["cluster"])
     total["L"] = max(total.get("L", 0), c["L"])
     total.setdefault("groups", []).extend(c["groups"])
+    if "grow" in c:      # (constant-turn scenes: every (target, scan) figure, the turn-rate kinds met)
+        total.setdefault("grow", []).extend(g for _, _, g in ct_grow_rows(c))
+        total["kinds"] = sorted(set(total.get("kinds", [])) | set(c["kinds"]))
     return total
+
+
+def run_case_ct_scene(seed, max_leaves=CA_MAX_LEAVES, similar=False, streamed=False, spill=False):
+    """The constant-turn forest on scenario_of(seed) with run_case_ct's random turn rates, the leaf cap alone deciding where it stops
+    (oracle_run, device_run).  Returns (ok, description, message, census)."""
+    scene = ct_scene(seed, similar)
+    rec = oracle_run(scene, max_leaves)
+    ok, msg = device_run(scene, rec, streamed, spill)
+    c = rec["census"]
+    return ok, scene["desc"], msg + ' L=%d ilp=%d cluster=%d dead=%d groups=%s' % (c["L"], c["ilp"], c["cluster"], c["dead"], group_histogram(c["groups"])), c

@@ -96,11 +96,26 @@ def test_constant_turn_forest_similar_state_pruning():
     """Similar-state pruning (tracker.py:1233-1239, pyTarget.py:358-412 are model-agnostic) in a constant-turn forest: the merged node takes the
     missed-detection child's slot and key, and a mean covariance that is not the hit children's own is written over the parent's P_bar entry
     (csrc/mht_similar.hip).  Random scenarios with the switch toggled per scan against the live oracle: decisions exact, states AND covariances of
-    all leaves 1e-6 (fuzz_util.run_case_ct(similar=True))."""
+    all leaves 1e-6 (fuzz_util.run_case_ct(similar=True)).  merged_seen counts the groups the oracle merged on the way (its Node.prune_similar is
+    wrapped and does what it always does): a slice in which nothing is ever merged would hold nothing to this path."""
+    import mht_oracle as orc
     from fuzz_util import run_case_ct
-    bad, merged_seen = [], 0
-    for case in range(40):
-        ok, desc, msg = run_case_ct(880000 + case, max_leaves=1500, budget_s=6.0, similar=True)
-        if not ok:
-            bad.append(desc + ' ' + msg)
+    bad, merged_seen = [], [0]
+    plain = orc.Node.prune_similar
+
+    def counting(node, threshold):
+        before = len(node.kids)
+        plain(node, threshold)
+        merged_seen[0] += len(node.kids) != before
+
+    orc.Node.prune_similar = counting
+    try:
+        for case in range(40):
+            ok, desc, msg = run_case_ct(880000 + case, max_leaves=1500, budget_s=6.0, similar=True)
+            if not ok:
+                bad.append(desc + ' ' + msg)
+    finally:
+        orc.Node.prune_similar = plain
     assert not bad, "\n".join(bad)
+    print("merged groups", merged_seen[0])
+    assert merged_seen[0] > 0
