@@ -57,6 +57,7 @@ struct BlpArgsPlain : BlpArgs {
     static constexpr const int32_t* cl_owner = nullptr;
     static constexpr int32_t* big_list = nullptr;
     static constexpr unsigned long long* dbg = nullptr;
+    static constexpr bool phase_clocks = false;      // (no clock read but the report's stage stamps, a cluster's start and end, the time limit)
 };
 static_assert(sizeof(BlpArgsPlain) == sizeof(BlpArgs), "the plain view adds no field");
 typedef const __attribute__((address_space(4))) BlpArgsPlain KBlpArgsPlain;
@@ -64,6 +65,9 @@ template <typename AT> struct blp_plain { static constexpr bool value = false; }
 template <> struct blp_plain<KBlpArgsPlain> { static constexpr bool value = true; };
 // "is this optional table there?" -- the plain instance knows that a forest's are (blp_is_plain): no test, the pointer is read where it is used
 #define BLP_HAS(f) (blp_plain<AT>::value || a.f != nullptr)
+// a stamp of the phase statistics (cl_time columns 0 and 2..7): no instruction where the block's type says there are none -- a clock read
+// is scalar memory, which returns out of order: the wavefront's next LDS or scalar wait drains it, clock latency included
+#define BLP_PHASE_CLOCK(on) ((on) ? wall_clock64() : 0ull)
 // what the plain instance takes for granted, checked by the host on the block it launches with (after blp_set_tier)
 static bool blp_is_plain(const BlpArgs& b) {
     return b.pds == 8 && b.PD <= 8 && b.shard_n <= 1 && !b.shard_team && !b.sel_rel && !b.cl_owner && b.tier == 0 && !b.force_hbm && !b.no_enum &&
@@ -892,12 +896,12 @@ __device__ __forceinline__ double enum_val(unsigned long long k) {
     const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
     return __longlong_as_double((long long)b);
 }
-__device__ __forceinline__ bool enumerate_small(const GStore&, int, Red*, int&, unsigned long long*, double&) { return false; }
+template <bool PH> __device__ __forceinline__ bool enumerate_small(const GStore&, int, Red*, int&, unsigned long long*, double&) { return false; }
 constexpr int ENUM_W = BLP_THREADS / 64;
 constexpr size_t ENUM_LDS = BLP_THREADS <= 256 ? 768 : 768 * (BLP_THREADS / 256);             // search state of the wavefronts + scalars (see the carve in enumerate_small)
 struct alignas(16) EnumEnt { double rc; unsigned long long sig; };      // reduced cost and contested-row signature of a ranked column
 template <typename S> __device__ __forceinline__ double greedy_dive(const S& s, int K, int32_t* out_sel, Red* r);
-__device__ __forceinline__ bool enumerate_small(const LStore& s, int K, Red* r, int& nodes_out, unsigned long long* stamp, double& ub_known) {
+template <bool PH> __device__ __forceinline__ bool enumerate_small(const LStore& s, int K, Red* r, int& nodes_out, unsigned long long* stamp, double& ub_known) {
     if (K > ENUM_MAXK || K < 2) return false;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nH = s.nH, nR = s.nR;
     EnumEnt* xL = s.xL;
@@ -917,7 +921,7 @@ __device__ __forceinline__ bool enumerate_small(const LStore& s, int K, Red* r, 
     // 0. a feasible point (the dive leaves the marks at zero)
     double ub0 = greedy_dive(s, K, s.ch, r);
     if (ub_known < ub0) ub0 = ub_known;      // (the caller's incumbent in s.ub_sel[]: it passes every test below and is found again)
-    stamp[1] = wall_clock64();
+    stamp[1] = BLP_PHASE_CLOCK(PH);
     // 1. which members use a row (the usage / nomination counters are zero between iterations: borrowed, zeroed again below);
     //    reduced costs at the current prices (the last sweep's values predate the last price step)
     if (tid == 0) { *s_cnt = 0; *s_abort = 0; *s_ub = enum_key(ub0); }
@@ -940,7 +944,7 @@ __device__ __forceinline__ bool enumerate_small(const LStore& s, int K, Red* r, 
     for (int m = tid; m < nR; m += BLP_THREADS) s.usageL[m] = (__popc(s.markL[m]) >= 2) ? atomicAdd(s_cnt, 1) : -1;
     __syncthreads();
     bool ok = *s_cnt <= 64;      // (a dive that ran into a dead end gives ub0 = DINF: nothing is fixed then, the search finds its own incumbent)
-    stamp[2] = wall_clock64();
+    stamp[2] = BLP_PHASE_CLOCK(PH);
     auto slack = [](double ub) { return ub + 1e-9 * fmax(1.0, fabs(ub)); };
     if (ok) {
         // 2. reduced-cost fixing: the survivors of every member, in any order ...
@@ -1004,7 +1008,7 @@ __device__ __forceinline__ bool enumerate_small(const LStore& s, int K, Red* r, 
         }
         __syncthreads();
     }
-    stamp[3] = wall_clock64();
+    stamp[3] = BLP_PHASE_CLOCK(PH);
     if (ok) {
         // 3. the search.  A level's state is its position in the member's list; the mask and the sums above it are rebuilt from
         //    the positions when the search comes back up (same order of additions: the same floating-point sums as on the way down).
@@ -1229,9 +1233,9 @@ template <typename AT, typename S> __device__ __forceinline__ void solve_core(AT
     for (int it = 0; it <= it_cap; ++it) {
         iters = it;
         if (it == enum_at && !a.no_enum) {      // small cluster the first rounds did not certify: exact search
-            const unsigned long long e0 = wall_clock64();
-            const bool solved = enumerate_small(s, K, r, nodes, stamp, UB);
-            stamp[5] = wall_clock64() - e0;
+            const unsigned long long e0 = BLP_PHASE_CLOCK(a.phase_clocks);
+            const bool solved = enumerate_small<AT::phase_clocks>(s, K, r, nodes, stamp, UB);
+            stamp[5] = BLP_PHASE_CLOCK(a.phase_clocks) - e0;
             if (solved) { status = MHT_BLP_BRANCHED; return; }
         }
         if (it == ca_end && ca_end > 0 && !bb_after_rounds(s, K)) {
@@ -1247,7 +1251,7 @@ template <typename AT, typename S> __device__ __forceinline__ void solve_core(AT
         if ((it == 24 || it == 64 || it == 128) && UB < DINF && reducible(&a, s, K, UB, r)) { status = MHT_BLP_REDUCE; return; }
         // A: per target the minimiser of the reduced cost (lowest column index wins ties)
         compute_minimisers(s, K, r);
-        if (it == 0) stamp[1] = wall_clock64();
+        if (it == 0) stamp[1] = BLP_PHASE_CLOCK(a.phase_clocks);
         // B: how often each measurement node is used by the minimisers
         if (!usage_counted_by_minimisers(s, K)) {
             for (int idx = tid; idx < K * s.PD; idx += BLP_THREADS) {
@@ -1257,7 +1261,7 @@ template <typename AT, typename S> __device__ __forceinline__ void solve_core(AT
             __threadfence_block();
             __syncthreads();
         }
-        if (it == 0) stamp[2] = wall_clock64();
+        if (it == 0) stamp[2] = BLP_PHASE_CLOCK(a.phase_clocks);
         // C: certificate flags; the subgradient rounds also need the dual value and the subgradient norm
         const bool coord = it < ca_end;
         double nrm = 0.0, usum = 0.0, LB = 0.0;
@@ -1280,7 +1284,7 @@ template <typename AT, typename S> __device__ __forceinline__ void solve_core(AT
             for (int w = 0; w < BLP_THREADS / 64; ++w) ff |= r->i[w];
             conflict = ff & 1;
             slack = (ff >> 1) & 1;
-            if (it == 0) stamp[3] = wall_clock64();
+            if (it == 0) stamp[3] = BLP_PHASE_CLOCK(a.phase_clocks);
             if (!conflict) {        // the minimisers are a feasible selection (and optimal if no priced row is unused)
                 bool take = true;
                 if (UB < DINF) {      // (only a cluster rebuilt from an HBM phase arrives with an incumbent: keep the better of the two)
@@ -1322,7 +1326,7 @@ template <typename AT, typename S> __device__ __forceinline__ void solve_core(AT
                 conflict = f & 1;
                 slack = (f >> 1) & 1;
             }
-            if (it == 0) stamp[3] = wall_clock64();
+            if (it == 0) stamp[3] = BLP_PHASE_CLOCK(a.phase_clocks);
             LB = src - utot;
             if (!conflict && sc < UB) {
                 UB = sc;
@@ -1843,7 +1847,7 @@ template <typename AT> __device__ __forceinline__ void solve_cluster(AT* ap, con
     const int slot = cr.p0 + c;
     const int UW = (a.n_mnodes + 63) >> 6;
     const unsigned long long t_begin = wall_clock64();
-    const unsigned long long c_begin = clock64();
+    const unsigned long long c_begin = a.phase_clocks ? clock64() : 0ull;
     TgtPre pre = {};      // per-member data of the prune epilogue, fetched now so that its latency hides behind the solve
     const bool pre_ok = BLP_HAS(t_alive) && K <= BLP_THREADS;
     if (pre_ok && tid < K) { if (pre_in && my_t >= 0) pre = *pre_in; else pre = load_target_cr(&a, my_t >= 0 ? my_t : mem[tid], cr); }
@@ -2012,7 +2016,7 @@ template <typename AT> __device__ __forceinline__ void solve_cluster(AT* ap, con
     int nR = s_nR;
     int status, iters, nodes;
     unsigned long long stamp[6] = {t_begin, 0, 0, 0, 0, 0};      // [0]: start of the cluster (the time limit counts from here)
-    const unsigned long long t_setup = wall_clock64();
+    const unsigned long long t_setup = BLP_PHASE_CLOCK(a.phase_clocks);
     bool use_lds = lds_cols && nR < L_MAXR;
     // a team searches a cluster that is solved out of LDS from the start (every member holds its own copy); a cluster on HBM scratch
     // (shared) is its owner's alone
@@ -2159,7 +2163,7 @@ template <typename AT> __device__ __forceinline__ void solve_cluster(AT* ap, con
             } else if (team_hbm) {
                 if (!team_file(tm, team_idx, K, [&](int k) { return gs.ub_sel[k]; }, ub, status, iters, nodes, final_sel)) return;
             }
-            stamp[4] = wall_clock64();
+            stamp[4] = BLP_PHASE_CLOCK(a.phase_clocks);
             if (xteam) {
                 xteam_out([&](int k) { return final_sel ? __hip_atomic_load(const_cast<int32_t*>(final_sel) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : gs.ub_sel[k]; },
                           final_sel ? best_io : ub);
@@ -2202,7 +2206,7 @@ template <typename AT> __device__ __forceinline__ void solve_cluster(AT* ap, con
         } else if (team) {
             if (!team_file(tm, team_idx, K, [&](int k) { return s.to_global(s.ub_sel[k]); }, ub, status, iters, nodes, final_sel)) return;
         }
-        stamp[4] = wall_clock64();
+        stamp[4] = BLP_PHASE_CLOCK(a.phase_clocks);
         int rf_mine = -1;
         if (xteam) {      // (a sharded step solves only: t_alive is null, the per-target end of the scan follows the exchange)
             xteam_out([&](int k) { return final_sel ? __hip_atomic_load(const_cast<int32_t*>(final_sel) + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : s.to_global(s.ub_sel[k]); },
@@ -2251,10 +2255,11 @@ template <typename AT> __device__ __forceinline__ void solve_cluster(AT* ap, con
         a.cl_iters[c] = iters;
         a.cl_nodes[c] = nodes;
         if (a.cl_time) {
-            a.cl_time[8 * c] = (int)(t_setup - t_begin);
+            // (without the phase statistics -- the plain instance -- every column but the total is 0)
+            a.cl_time[8 * c] = a.phase_clocks ? (int)(t_setup - t_begin) : 0;
             a.cl_time[8 * c + 1] = (int)(wall_clock64() - t_begin);
-            for (int q = 1; q <= 4; ++q) a.cl_time[8 * c + 1 + q] = (int)(stamp[q] - t_begin);
-            a.cl_time[8 * c + 6] = (int)(clock64() - c_begin);
+            for (int q = 1; q <= 4; ++q) a.cl_time[8 * c + 1 + q] = a.phase_clocks ? (int)(stamp[q] - t_begin) : 0;
+            a.cl_time[8 * c + 6] = a.phase_clocks ? (int)(clock64() - c_begin) : 0;
             a.cl_time[8 * c + 7] = (int)stamp[5];      // ticks spent in enumerate_small
         }
     }
@@ -2370,8 +2375,14 @@ template <typename AT> __device__ __forceinline__ bool uf_prologue(AT* ap, const
         const unsigned K = (unsigned)cnt[t];
         return make_uint2(1u | ((K >= 2u ? 1u : 0u) << 14), K | ((K >= (unsigned)TEAM_MIN_K ? 1u : 0u) << 14));
     };
-    uint2 mine = make_uint2(0u, 0u);
-    for (int e = 0; e < E; ++e) { const uint2 v = pack_of(tid * E + e); mine.x += v.x; mine.y += v.y; }
+    // (up to four targets per thread -- 1 024 targets -- keep their words in registers across the scan: the tables pass below does not read
+    // lab / cnt again)
+    uint2 mine = make_uint2(0u, 0u), pk[4];
+    if (E <= 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { pk[e] = e < E ? pack_of(tid * E + e) : make_uint2(0u, 0u); mine.x += pk[e].x; mine.y += pk[e].y; }
+    } else
+        for (int e = 0; e < E; ++e) { const uint2 v = pack_of(tid * E + e); mine.x += v.x; mine.y += v.y; }
     const uint2 incl = make_uint2(wave_scan_u32(mine.x), wave_scan_u32(mine.y));
     if (lane == 63) s_w[wave] = (unsigned long long)incl.x | ((unsigned long long)incl.y << 32);
     __syncthreads();
@@ -2385,10 +2396,8 @@ template <typename AT> __device__ __forceinline__ bool uf_prologue(AT* ap, const
     }
     const int nC = (int)(total.x & 0x3fffu), nMulti = (int)(total.x >> 14), nSingle = nC - nMulti;
     const int nTeamAll = (int)(total.y >> 14), nTeam = (a.team_list && nTeamAll > 0) ? (nTeamAll < TEAM_MAX ? nTeamAll : TEAM_MAX) : 0;
-    for (int e = 0; e < E; ++e) {
-        const int t = tid * E + e;
-        const uint2 v = pack_of(t);
-        if (!v.x) continue;
+    auto file_head = [&](const int t, const uint2 v) {
+        if (!v.x) return;
         const int c = (int)(run.x & 0x3fffu), mr = (int)(run.x >> 14), p0 = (int)(run.y & 0x3fffu), tr = (int)(run.y >> 14);
         const int K = (int)(v.y & 0x3fffu);
         par[t] = (unsigned short)c;       // (the parents are dead: cluster index by head)
@@ -2396,13 +2405,20 @@ template <typename AT> __device__ __forceinline__ bool uf_prologue(AT* ap, const
         if (K >= 2) ml[mr] = (unsigned short)t; else sl[c - mr] = (unsigned short)t;
         if (K >= TEAM_MIN_K && tr < TEAM_MAX) s_tl[tr] = t;
         run.x += v.x; run.y += v.y;
-    }
+    };
+    if (E <= 4) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) file_head(tid * E + e, pk[e]);
+    } else
+        for (int e = 0; e < E; ++e) file_head(tid * E + e, pack_of(tid * E + e));
     __syncthreads();
     UF_STAMP(4);
-    // Member lists.  A workgroup usually needs ONE: that of its own cluster -- wavefront 0 collects it in ascending order with ballots, no
-    // barrier, while the others file the single-target clusters.  All lists at once (a slot by LDS atomic, then the ascending rank by
-    // counting the smaller members, as cluster_kernel) only where they are needed: the workgroup that files the tables in global
-    // memory, teams (every member needs the team clusters' lists), several clusters per workgroup, a cluster of more than 64 targets.
+    // Member lists.  A workgroup usually needs ONE: that of its own cluster, at most 64 targets -- the four wavefronts walk the targets
+    // in stripes of 64 (stripe i: wavefront i % 4, its pass i / 4), a ballot per stripe, a non-empty stripe's slots by ONE LDS atomic on
+    // the head's counter; the unordered list waits in UfPersist::team (no teams on this path) and wavefront 0 ranks it in registers behind
+    // the closing barrier.  All lists at once (a slot by LDS atomic, then the ascending rank by counting the smaller members, as
+    // cluster_kernel) only where they are needed: the workgroup that files the tables in global memory, teams (every member needs the
+    // team clusters' lists), several clusters per workgroup, a cluster of more than 64 targets.
     const int writer = nMulti < gx - 1 ? nMulti : gx - 1;      // (the first workgroup without an ILP of its own)
     const int own_root = bx < nMulti ? (int)ml[bx] : 0;
     const int own_K = bx < nMulti ? (cnt[own_root] & 0xffff) : 0;
@@ -2416,6 +2432,10 @@ template <typename AT> __device__ __forceinline__ bool uf_prologue(AT* ap, const
         ps->single[w][j] = (i < nSingle) ? sl[i] : (unsigned short)0xffff;
     }
     int my_t = -1;
+    const bool spread = !full && bx < nMulti;      // (uniform in the workgroup; own_K <= 64, nTeam == 0)
+    const int own_p0 = spread ? (int)hp[own_root] : 0;      // (read HERE: behind the closing barrier the solver's tables overlay hp)
+    static_assert(sizeof(ps->team) >= 64 * sizeof(unsigned short), "the unordered member list borrows the team table");
+    unsigned short* ul = reinterpret_cast<unsigned short*>(ps->team);
     if (full) {
         for (int t = tid; t < nT; t += BLP_THREADS) {
             const int h = lab[t];
@@ -2476,26 +2496,46 @@ template <typename AT> __device__ __forceinline__ bool uf_prologue(AT* ap, const
             if (a.alloc_reset && tid >= 64 && tid < 64 + FG_REGIONS) a.alloc_reset[(tid - 64) * 32] = 0u;
         }
         if (bx < nMulti && tid < own_K) my_t = ms[hp[own_root] + tid];
-    } else if (wave == 0 && bx < nMulti) {
-        const int p0 = hp[own_root];
-        int n = 0;
-        for (int t0 = 0; t0 < nT && n < own_K; t0 += 64) {
+    } else if (spread) {
+        for (int t0 = wave * 64; t0 < nT; t0 += BLP_THREADS) {
             const int t = t0 + lane;
             const bool m = t < nT && lab[t] == own_root;
             const unsigned long long bal = __ballot(m);
-            if (m) ms[p0 + n + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)t;
-            n += __popcll(bal);
+            if (bal == 0ull) continue;
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&cnt[own_root], __popcll(bal) << 16) >> 16;      // (all stripes together hand out own_K <= 64 slots)
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (m) ul[base + __popcll(bal & ((1ull << lane) - 1ull))] = (unsigned short)t;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) ps->own[0] = ref_of(own_root);
-        if (lane < own_K) { my_t = ms[p0 + lane]; gmem[p0 + lane] = my_t; }
+        if (tid == 0) ps->own[0] = ref_of(own_root);
     }
     // member `tid` of the workgroup's first cluster: its record is on its way while the solver sets itself up
     if (my_t >= 0) { pre_out = load_target(&a, my_t); pre_out.lab = own_root; }
     __threadfence_block();
     __syncthreads();
     UF_STAMP(7);
+    if (spread && wave == 0) {
+        // Lane k holds entry k of the unordered list and asks for ITS record at once -- the solver's set-up starts with the members' column
+        // ranges, so the records' round trip is what the workgroup waits for next: it leaves before the ranking, not behind it.  The rank
+        // (the number of smaller entries) is counted meanwhile, and entry and record move to the lane of their rank with one permute per
+        // word: lane k holds member k, ascending, as the solver expects.  (Lanes beyond the list keep their own place: a permutation.)
+        // Nothing of the prologue's LDS is read here -- the other wavefronts are in the solver already and its tables overlay it; the
+        // list is in UfPersist, everything else in registers.
+        const bool in = lane < own_K;
+        const int e = in ? (int)ul[lane] : 0xffff;
+        TgtPre p = {};
+        if (in) p = load_target(&a, e);
+        int rank = 0;
+        for (int i = 0; i < own_K; ++i) rank += (__builtin_amdgcn_readlane(e, i) < e) ? 1 : 0;
+        const int to = (in ? rank : lane) << 2;
+        auto mv = [&](int v) { return __builtin_amdgcn_ds_permute(to, v); };
+        const int t = mv(e);
+        p.j = mv(p.j); p.rscan = mv(p.rscan); p.rnode = mv(p.rnode); p.id = mv(p.id); p.cb = mv(p.cb); p.ce = mv(p.ce);
+        p.rootc = __hiloint2double(mv(__double2hiint(p.rootc)), mv(__double2loint(p.rootc)));
+        p.rootf = (uint8_t)mv((int)p.rootf);
+        p.lab = own_root;
+        if (in) { my_t = t; gmem[own_p0 + lane] = t; pre_out = p; }
+    }
     my_t_out = my_t;
     return true;
 }
@@ -2727,7 +2767,7 @@ __global__ __launch_bounds__(BLP_THREADS) void blp_kernel(const BlpArgs a) {
 // AT = KBlpArgs (every caller) or KBlpArgsPlain (a plain forest's scans: launch_blp)
 template <typename AT> __device__ __forceinline__ void blp_uf_run(const UfHead& head) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const unsigned long long t_first = wall_clock64();      // (development: the kernel's first instruction, kept in a register until the block's dbg pointer is read)
+    const unsigned long long t_first = BLP_PHASE_CLOCK(AT::phase_clocks);      // (development: the kernel's first instruction, kept in a register until the block's dbg pointer is read)
     // The prologue's round trip leaves FIRST, on the six arguments it needs (the kernel's by-value parameter: loads at offsets the compiler
     // knows).  Everything else is read from the argument segment where it is used, through a pointer the compiler cannot see through: no
     // argument is loaded in front of the issue of those loads, none is carried from one phase of the solver into the next.

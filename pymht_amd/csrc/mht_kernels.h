@@ -307,6 +307,9 @@ struct BlpArgs {
     const unsigned long long* ni_flag; int uf_ovl;      // uf_ovl: the scan's grow launch overlapped the previous ILP launch -- if ni_flag says that a
                                                         // target died in the previous scan, the union-find was redone under epoch | 1
     unsigned uf_lds_off;           // offset of the workgroup's UfPersist block in the dynamic LDS (behind the solver's tables; set by launch_blp)
+    // phase statistics (no field: a constant of the type): the clock reads behind cl_time's columns 0 and 2..7 and the workgroup's first
+    // instruction.  blp_uf_kernel_plain's view of the block hides it with `false` (mht_blp.hip: BlpArgsPlain) and reads none of them.
+    static constexpr bool phase_clocks = true;
 };
 
 // prune_similar_kernel (mht_similar.hip): similar-state pruning of the targets that are alone in their cluster, between the

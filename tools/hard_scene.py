@@ -1,7 +1,10 @@
 """Development: one fuzz scenario (tests/fuzz_util.scenario_of) through the drop-in Tracker, per-scan ILP stage time from the device stamps.
-usage: hard_scene.py SEED"""
+usage: hard_scene.py SEED
+(The set-up column and the stamps of cl_time are phase statistics, which the plain instance of the ILP launch writes as 0: the tracker
+runs the generic instance.)"""
 import os
 import sys
+os.environ["MHT_BLP_GENERIC"] = "1"      # (read when the forest is created)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle')); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import numpy as np

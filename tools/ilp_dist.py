@@ -1,8 +1,11 @@
 """Development aid: what the ILP launch's clusters look like on a stream -- sizes (targets, columns), dual rounds, device time per
 cluster (BlpArgs::cl_time) -- and which cluster each scan's launch ends with.  Reads the forest's tables after every scan of an
 untimed replay (every read synchronises).
-    python tools/ilp_dist.py [cfg3|cfg2|cfg5] [n_scans]"""
+    python tools/ilp_dist.py [cfg3|cfg2|cfg5] [n_scans]
+(cl_time's set-up and "solved at" columns are phase statistics: the plain instance of the launch writes them as 0, so the replay runs as
+the generic instance.)"""
 import ctypes as C, os, sys
+os.environ["MHT_BLP_GENERIC"] = "1"      # (read when the forest is created)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import bench
