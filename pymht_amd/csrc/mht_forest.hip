@@ -1400,8 +1400,11 @@ static int step_grow(mht_ctx* ctx, Forest* f, StepPlan& pl, const float* z, int 
     d.dbg = f->sw.debug ? f->grow_dbg : nullptr;
     d.uf_epoch = pl.use_uf ? 2u * (unsigned)pl.s : 0u;      // (2 x scan: the odd value in between is the epoch of a union-find that had to be redone, mht_fgrow.hip)
     // the previous scan's ILP launch published per-target records and its commit rides here: this launch takes what it needs of that
-    // launch target by target -- and may start while it is still running
-    d.ovl = (pl.fused && f->pub_scan == pl.s - 1 && f->pending_dyn.scan == pl.s - 1) ? 1 : 0;
+    // launch target by target -- and may start while it is still running.
+    // Only a scan that is itself clustered by the union-find: an overlapping target workgroup does not know its compacted index until its
+    // end (target_tail), and the edge list of the clustering kernel is filed under that index next to the emission -- a scan with
+    // similar-state pruning behind one without filed every target's edges under index 0 and its clusters fell apart
+    d.ovl = (pl.fused && pl.use_uf && f->pub_scan == pl.s - 1 && f->pending_dyn.scan == pl.s - 1) ? 1 : 0;
     d.c_wait = f->blp_done_total;
     pl.grow_ovl = d.ovl != 0;
     d.ct_spill = f->sw.ct_spill ? 1 : 0;
