@@ -687,6 +687,45 @@ int mht_ospa2_windows(mht_ctx* ctx, int32_t n_steps, int32_t n_trk, const double
 void mht_ospa2_set_timing(int32_t on);
 void mht_ospa2_stage_times(float* ms);
 
+/* mht_kbest_hypotheses: the K best GLOBAL hypotheses of every cluster -- the figure of a multi-hypothesis tracker that says how
+ * ambiguous a cluster is, what the second-best joint explanation is, and how probable a leaf is once the other targets have had
+ * their say.  The instance is mht_solve_blp's sparse form: nT targets, target t owning the columns group_ptr[t] .. group_ptr[t + 1] - 1
+ * (a column is a leaf), every column a cost and up to `depth` row ids (rows dev [depth][nHyp], -1 = none).  Clusters: cluster c has the
+ * targets cluster_targets[cluster_ptr[c] .. cluster_ptr[c + 1] - 1], ascending; row ids are LOCAL to the cluster, in
+ * [0, MHT_KBEST_MAX_ROWS).  A global hypothesis of a cluster picks one column per target so that no two picked columns share a row
+ * id; its cost is the float64 sum of the picked costs from 0.0, left to right in the cluster's target order.  Listed per cluster are
+ * the K cheapest under the total order (cost, then the tuple of column indices in target order): the list is unique, ties are decided.
+ * A column whose cost is not finite is never picked.
+ *   count [nC]       hypotheses listed;  status [nC] MHT_KBEST_*;  nodes [nC] sibling tests the search made (<= node_limit)
+ *   hyp_cost [K][nC] ascending; hyp_prob [K][nC] = exp(-(cost[r] - cost[0])) / sum over the listed r (summed in ascending r: the
+ *                    probabilities are those of the K listed hypotheses, truncated); NaN beyond count
+ *   hyp_sel [K][nT]  the global column of every target in hypothesis r of its cluster; -1 beyond count and for a target in no cluster
+ *   marginal [nHyp]  sum of hyp_prob[r] over the listed hypotheses that hold the column (ascending r); 0 for a column in none and for
+ *                    a target in no cluster; NaN for the columns of a cluster that was not searched
+ *   work             dev, work_bytes >= mht_kbest_work_bytes(nHyp, nT, nC, depth, K): the listed tuples, 2 K nT bytes rounded up to
+ *                    256 (0 for a negative size, K outside 1 .. MHT_KBEST_MAX_K or a negative depth)
+ * A cluster beyond a limit below -- or whose indices point outside the arrays -- is not searched: MHT_KBEST_TOO_LARGE, count 0.  A
+ * row id other than -1 outside the range: MHT_KBEST_BAD_ROWS, count 0; it indexes nothing.  A target without a finite column, or no
+ * conflict-free choice: MHT_KBEST_OK with count 0.  The search is a depth-first branch and bound, one wavefront per cluster
+ * (csrc/mht_kbest.h states the bound and its rounding allowance); after node_limit sibling tests it stops with the best found so far.
+ * The targets of different clusters must be disjoint.  One launch behind two fills, ASYNCHRONOUS on the ctx stream (mht_synchronize).
+ * MHT_E_INVALID, nothing launched or written: a null pointer (rows may be null with depth 0), nHyp, nT or nC < 1, depth < 0, K outside
+ * 1 .. MHT_KBEST_MAX_K, node_limit < 1, a short workspace.  Exported by both builds (the search is model-free). */
+#define MHT_KBEST_MAX_K 64          /* hypotheses listed per cluster */
+#define MHT_KBEST_MAX_TARGETS 32    /* targets per cluster */
+#define MHT_KBEST_MAX_COLUMNS 1024  /* columns per cluster */
+#define MHT_KBEST_MAX_DEPTH 16      /* row ids per column */
+#define MHT_KBEST_MAX_ROWS 2048     /* row ids are local to the cluster, in [0, MHT_KBEST_MAX_ROWS) */
+#define MHT_KBEST_OK 0              /* the list is exact; count < K: only count feasible hypotheses exist, 0: infeasible */
+#define MHT_KBEST_NODE_LIMIT 1      /* the best found so far, not certified */
+#define MHT_KBEST_TOO_LARGE 2       /* not searched */
+#define MHT_KBEST_BAD_ROWS 3        /* a row id was out of range */
+size_t mht_kbest_work_bytes(int32_t nHyp, int32_t nT, int32_t nC, int32_t depth, int32_t K);
+int mht_kbest_hypotheses(mht_ctx* ctx, int32_t nHyp, int32_t nT, int32_t nC, int32_t depth, int32_t K, int32_t node_limit,
+                         const int32_t* group_ptr, const int32_t* rows, const double* cost, const int32_t* cluster_ptr,
+                         const int32_t* cluster_targets, int32_t* count, int32_t* status, int32_t* nodes, double* hyp_cost,
+                         double* hyp_prob, int32_t* hyp_sel, double* marginal, void* work, size_t work_bytes);
+
 /* ---- AIS-aided children: Tracker.__fuseRadarAndAis (tracker.py:417-552), stateless ------------------------------------------
  * Per leaf and per AIS message (a 4-state report [x, y, vx, vy] of a ship with identity mmsi, made inside the radar period in
  * front of the scan; models/ais.py) that gates with it (eta2_ais, tracker.py:111): the leaf is predicted to the message's time,
@@ -868,6 +907,14 @@ int mht_forest_leaves(mht_ctx* ctx, int32_t capacity, double* x, float* P, doubl
  * mht_forest_leaves rounds those to float32. */
 int mht_forest_leaves_f64(mht_ctx* ctx, int32_t capacity, double* x, double* P, double* cnllr, int32_t* meas,
                           int32_t* target, int32_t* id, int32_t* node, uint8_t* flags, int32_t* n_out);
+/* The window rows of the current leaves, in mht_forest_leaves' order and with its capacity semantics: rows host [capacity][depth]
+ * int32.  One thread per leaf walks `parent` from the leaf up to its target's window root (root_scan / root_node of the target table);
+ * the root itself is left out unless it is the leaf.  Every node on the way with a measurement (meas > 0) gives one key
+ * (level << 24) | meas, level = current scan - the node's scan; the other cells are -1.  These are the rows the reference's ILP gives
+ * the leaf's column, so two leaves share a key exactly where they exclude each other.  The walk is bounded by depth and by the ring;
+ * nothing else is launched, no forest state changes.  depth 1 .. 64.  A forest with MHT_FOREST_AIS: MHT_E_STATE (its columns also
+ * carry message rows).  Synchronises. */
+int mht_forest_leaf_rows(mht_ctx* ctx, int32_t capacity, int32_t depth, int32_t* rows, int32_t* n_out);
 /* Similar-state pruning -- Tracker._pruneSimilarState (tracker.py:1233-1239) -> Target.pruneSimilarState (pyTarget.py:358-412),
  * what addMeasurementList(..., pruneSimilar=True) asks for (tracker.py:230-231) -- for the scans stepped from now on: in every target
  * that is alone in its cluster, the hit children of a node that lie within `threshold` metres (Tracker.pruneThreshold,

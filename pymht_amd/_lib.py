@@ -164,6 +164,8 @@ def _declare(lib, nx=4):
         "mht_trial_hypotheses": [vp, i32, i32, i32, i32, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_gospa_steps": [vp, i32, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
         "mht_ospa2_windows": [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
+        "mht_kbest_hypotheses": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
+        "mht_forest_leaf_rows": [vp, i32, i32, vp, C.POINTER(i32)],
         "mht_forest_create_ex": [vp, vp, vp, C.c_uint32],
         "mht_forest_set_ais": [vp, vp, i32, vp, i32, dbl, dbl],
         "mht_forest_read_mmsi": [vp, i32, i32, i32, vp, vp],
@@ -239,6 +241,8 @@ def _declare(lib, nx=4):
     lib.mht_gospa_work_bytes.restype = C.c_size_t
     lib.mht_ospa2_work_bytes.argtypes = [i32, i32, i32, i32]
     lib.mht_ospa2_work_bytes.restype = C.c_size_t
+    lib.mht_kbest_work_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.mht_kbest_work_bytes.restype = C.c_size_t
     lib.mht_ospa2_set_timing.argtypes = [i32]
     lib.mht_ospa2_set_timing.restype = None
     lib.mht_ospa2_stage_times.argtypes = [C.POINTER(C.c_float * 3)]

@@ -100,6 +100,7 @@ enum KernelSlot : int {
     K_SMOOTH_SCORE,                  // (no LDS either: every kernel of mht_smooth_score.hip goes through launch_kernel under this one)
     K_GOSPA,                         // gospa_kernel (mht_gospa.hip): the search tables of the launch's largest step, 56 KB at 2048 x 2048
     K_OSPA2,                         // the kernels of mht_ospa2.hip; LDS: ospa2_assign_kernel's search tables, sized as K_GOSPA's
+    K_KBEST,                         // kbest_kernel (mht_kbest.hip): a cluster's tables, sized by the launch's arguments, 45.8 KB at the limits
     K_FGROW,
     K_SLOTS = K_FGROW + FG_FAMILIES * 3 * 2
 };

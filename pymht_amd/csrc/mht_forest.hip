@@ -278,6 +278,33 @@ __global__ void leaves_kernel(const LeavesArgs a, const LeavesCt ct) {
     }
 }
 
+// mht_forest_leaf_rows: per leaf (mht_forest_leaves' order) the keys of the measurements on its window path, the root left out unless
+// it is the leaf -- the rows of the leaf's column in the reference's ILP.  One thread per leaf, the walk bounded by depth and the ring.
+struct LeafRowsArgs { mht_nodes layers[MAXR]; TTable tab; const FCounts* cnt; int R, scan, depth, capacity; int32_t* rows; uint8_t* flags; };
+__global__ void leaf_rows_kernel(const LeafRowsArgs a) {
+    const int nT = a.cnt->nT;
+    const int L = a.cnt->L < a.capacity ? a.cnt->L : a.capacity;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < L; i += gridDim.x * blockDim.x) {
+        int lo = 0, hi = nT;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (a.tab.leaf_off[mid] <= i) lo = mid; else hi = mid; }
+        const int t = lo, rs = a.tab.root_scan[t], rn = a.tab.root_node[t];
+        int nd = a.tab.first[t] + (i - a.tab.leaf_off[t]), sc = a.scan, k = 0;
+        int32_t* out = a.rows + (size_t)i * a.depth;
+        a.flags[i] = a.layers[a.scan % a.R].flags[nd];
+        for (int step = 0; step < a.depth && step < a.R && sc >= 0 && nd >= 0 && nd < a.layers[sc % a.R].cap; ++step) {
+            const mht_nodes& l = a.layers[sc % a.R];
+            const bool root = sc == rs && nd == rn;
+            if (root && step > 0) break;
+            const int m = l.meas[nd];
+            if (m > 0) out[k++] = (int32_t)(((unsigned)(a.scan - sc) << 24) | (unsigned)(m & 0xFFFFFF));
+            if (root || sc <= rs) break;
+            nd = l.parent[nd];
+            --sc;
+        }
+        for (; k < a.depth; ++k) out[k] = -1;
+    }
+}
+
 struct ChainArgs { mht_nodes layers[MAXR]; VTab vt[2]; int lgen[MAXR]; int R; int scan, node, max_len; int32_t* nodes; int32_t* meas; double* x; double* cnllr; float* P; int32_t* n_out; double* P64; uint8_t* flags; };
 __device__ __forceinline__ int chain_walk(const ChainArgs& a, const CtLayers& ct, int nd, int32_t* nodes, int32_t* meas, double* x, double* cnllr, float* P, double* P64, uint8_t* flags) {
     int sc = a.scan, n = 0;
@@ -2201,6 +2228,50 @@ extern "C" int mht_forest_leaves(mht_ctx* ctx, int32_t capacity, double* x, floa
 extern "C" int mht_forest_leaves_f64(mht_ctx* ctx, int32_t capacity, double* x, double* P, double* cnllr, int32_t* meas,
                                      int32_t* target, int32_t* id, int32_t* node, uint8_t* flags, int32_t* n_out) {
     return forest_leaves_impl(ctx, capacity, x, P, 8, cnllr, meas, target, id, node, flags, n_out);
+}
+
+extern "C" int mht_forest_leaf_rows(mht_ctx* ctx, int32_t capacity, int32_t depth, int32_t* rows, int32_t* n_out) {
+    MHT_REQUIRE(ctx && ctx->forest && n_out, "mht_forest_leaf_rows: null argument");
+    Forest* f = ctx->forest;
+    MHT_REQUIRE(capacity >= 0 && (rows || capacity == 0), "mht_forest_leaf_rows: negative capacity or no array");
+    MHT_REQUIRE(depth >= 1 && depth <= 64, "mht_forest_leaf_rows: depth is 1 .. 64 (got %d)", depth);
+    if (f->ais) {
+        set_error("mht_forest_leaf_rows: a forest with AIS messages: its columns also carry message rows");
+        return MHT_E_STATE;
+    }
+    MHT_HIP_CHECK(hipSetDevice(ctx->device));
+    { const int rc = flush_commit(ctx, f); if (rc) return rc; }
+    FCounts c;
+    MHT_HIP_CHECK(hipMemcpyAsync(&c, f->cnt, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+    MHT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *n_out = c.L;
+    const int n = c.L < capacity ? c.L : capacity;
+    if (n == 0) return MHT_OK;
+    const size_t row_bytes = (size_t)depth * 4, o_r = 0, o_f = o_r + (size_t)n * row_bytes, total = o_f + n + 16;
+    int rc = stage_host_ensure(f, total);
+    if (rc) return rc;
+    rc = f->stage_dev.ensure(total);
+    if (rc) return rc;
+    char* d = static_cast<char*>(f->stage_dev.ptr);
+    char* h = static_cast<char*>(f->stage_host);
+    LeafRowsArgs a = {};
+    for (int k = 0; k < f->R; ++k) a.layers[k] = f->layer[k];
+    a.tab = f->tab[(f->scan + 1) & 1]; a.cnt = f->cnt; a.R = f->R; a.scan = f->scan; a.depth = depth; a.capacity = n;
+    a.rows = (int32_t*)(d + o_r); a.flags = (uint8_t*)(d + o_f);
+    hipLaunchKernelGGL(leaf_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, a);
+    MHT_HIP_CHECK(hipGetLastError());
+    MHT_HIP_CHECK(hipMemcpyAsync(h, d, total, hipMemcpyDeviceToHost, ctx->stream));
+    MHT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // (leaves that similar-state pruning took out of the tree are squeezed out, as mht_forest_leaves does)
+    const uint8_t* hf = reinterpret_cast<const uint8_t*>(h + o_f);
+    int live = 0;
+    for (int i = 0; i < n; ++i) {
+        if (hf[i] & F_DEAD) continue;
+        memcpy(reinterpret_cast<char*>(rows) + (size_t)live * row_bytes, h + o_r + (size_t)i * row_bytes, row_bytes);
+        ++live;
+    }
+    *n_out = c.L - (n - live);
+    return MHT_OK;
 }
 
 static void chain_args_of(Forest* f, ChainArgs& a, CtLayers& cl) {

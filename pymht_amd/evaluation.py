@@ -837,3 +837,118 @@ def trial_best(pcMax, dcpaMin):
         if best is None or pc[g] < best[0] or (pc[g] == best[0] and dg > best[1]):
             best = (pc[g], dg, g)
     return None if best is None else best[2]
+
+
+# ---- the k best global hypotheses ---------------------------------------------------------------------------------------------------
+KBEST_MAX_K, KBEST_MAX_TARGETS, KBEST_MAX_COLUMNS, KBEST_MAX_DEPTH, KBEST_MAX_ROWS = 64, 32, 1024, 16, 2048      # MHT_KBEST_*, include/mht_amd.h
+KBEST_OK, KBEST_NODE_LIMIT, KBEST_TOO_LARGE, KBEST_BAD_ROWS = 0, 1, 2, 3
+
+
+def k_best_prep(target, rows):
+    """Host preparation of k_best_hypotheses (NumPy and SciPy): the clusters and the cluster-local row ids.
+
+    target [L] non-decreasing target indices, rows [L, D] keys >= 0 or -1.  Two targets belong together when leaves of theirs share a
+    key; the clusters are the connected components.  Returns (group_ptr [T + 1], cluster_ptr [C + 1], cluster_targets [T] -- the
+    clusters in order of their smallest target, ascending inside --, local [D, L] int32: every key replaced by its rank among the keys
+    of its cluster, -1 kept)."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    tg = np.asarray(target, dtype=np.int64)
+    R = np.asarray(rows, dtype=np.int64).reshape(len(tg), -1)
+    L, D = R.shape
+    T = int(tg[-1]) + 1 if L else 0
+    group_ptr = np.searchsorted(tg, np.arange(T + 1)).astype(np.int32)
+    leaf, d = np.nonzero(R >= 0)
+    keys, kid = np.unique(R[leaf, d], return_inverse=True)
+    nK = len(keys)
+    g = coo_matrix((np.ones(len(leaf), dtype=np.int8), (tg[leaf], T + kid)), shape=(T + nK, T + nK))
+    _, lab = connected_components(g, directed=False)
+    # clusters in order of their smallest target
+    first = np.full(lab.max() + 1 if len(lab) else 0, T, dtype=np.int64)
+    np.minimum.at(first, lab[:T], np.arange(T))
+    order = np.argsort(first, kind="stable")
+    rank = np.empty(len(first), dtype=np.int64)
+    rank[order] = np.arange(len(first))
+    tc = rank[lab[:T]]                                  # cluster of every target, 0 .. C - 1
+    C_ = int(tc.max()) + 1 if T else 0
+    cluster_targets = np.argsort(tc, kind="stable").astype(np.int32)
+    cluster_ptr = np.searchsorted(tc[cluster_targets], np.arange(C_ + 1)).astype(np.int32)
+    # a key's local id: its rank among the keys of its cluster (the keys are sorted, so the rank is by value)
+    kc = rank[lab[T:]]
+    ko = np.argsort(kc, kind="stable")
+    start = np.searchsorted(kc[ko], np.arange(C_ + 1))
+    loc = np.empty(nK, dtype=np.int64)
+    loc[ko] = np.arange(nK) - start[kc[ko]]
+    local = np.full((max(D, 1), max(L, 1)), -1, dtype=np.int32)
+    local[d, leaf] = loc[kid]
+    return group_ptr, cluster_ptr, cluster_targets, local
+
+
+def k_best_hypotheses(cost, target, rows, k, nodeLimit=1 << 20, device=0, ctx=None):
+    """The k best GLOBAL hypotheses of every cluster of a leaf set, and what they say about every leaf.
+
+    cost [L]     the cost of every leaf (a Tracker's: cnllr), in leafBatch() order; a leaf whose cost is not finite is never picked
+    target [L]   its target index, non-decreasing
+    rows [L, D]  the keys of the plots on its window path: arbitrary non-negative integers, -1 for none
+    k            1 .. 64 hypotheses listed per cluster;  nodeLimit  sibling tests after which a cluster's search stops
+    device, ctx  the GPU ordinal, or an existing pymht_amd.device.Context (a Tracker's) to run on
+    A global hypothesis picks one leaf per target so that no two picked leaves share a key; its cost is the float64 sum of the picked
+    costs in target order.  The clusters are the connected components of targets whose leaves share a key -- FINER than the scan's
+    gating clusters, which join targets that merely gated the same plot at some scan.  Host preparation (k_best_prep) relabels the keys
+    per cluster; one device call follows (`mht_kbest_hypotheses`, a branch and bound per cluster, no host fallback).
+    Returns a dict:
+        clusters         list of int arrays: the targets of every cluster, ascending
+        count [C]        hypotheses listed (fewer than k: no more exist);  status [C]: 0 exact, 1 the node limit fired (the best found so
+                         far, not certified), 2 not searched (more than 32 targets, 1024 leaves or 16 keys per leaf), 3 not searched
+                         (more than 2048 distinct keys);  nodes [C] sibling tests made
+        cost [C, k]      ascending, ties by the tuple of leaf indices;  prob [C, k] = exp(-(cost - cost[:, :1])) normalised over the k
+                         LISTED hypotheses -- truncated, not the probability among all;  NaN beyond count
+        selection [k, T] the leaf of every target in hypothesis r of its cluster, -1 beyond count
+        leafProbability [L]  the sum of prob over the listed hypotheses that hold the leaf, equally truncated; 0 for a leaf in none
+    Clusters that were not searched are flagged, not guessed: their counts are 0 and their leafProbability is NaN.
+    Empty input gives empty arrays and no device call."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= KBEST_MAX_K:
+        raise ValueError("k_best_hypotheses: k is an integer in 1 .. %d (got %r)" % (KBEST_MAX_K, k))
+    if isinstance(nodeLimit, bool) or not isinstance(nodeLimit, (int, np.integer)) or not 1 <= nodeLimit < 2 ** 31:
+        raise ValueError("k_best_hypotheses: nodeLimit is an integer in 1 .. 2^31 - 1 (got %r)" % (nodeLimit,))
+    cn = np.ascontiguousarray(cost, dtype=np.float64)
+    if cn.ndim != 1:
+        raise ValueError("k_best_hypotheses: cost is an [L] array (got shape %r)" % (cn.shape,))
+    L = len(cn)
+    tg = np.asarray(target)
+    if tg.shape != (L,) or (L and (not np.issubdtype(tg.dtype, np.integer) or tg[0] < 0 or (np.diff(tg) < 0).any())):
+        raise ValueError("k_best_hypotheses: target is a non-decreasing [L] = [%d] array of target indices >= 0" % L)
+    R = np.asarray(rows)
+    if R.ndim != 2 or R.shape[0] != L or (R.size and (not np.issubdtype(R.dtype, np.integer) or (R < -1).any())):
+        raise ValueError("k_best_hypotheses: rows is an [L, D] = [%d, D] integer array of keys >= 0 or -1" % L)
+    k, D = int(k), int(R.shape[1])
+    if L == 0:
+        return {"clusters": [], "count": np.zeros(0, dtype=np.int32), "status": np.zeros(0, dtype=np.int32), "nodes": np.zeros(0, dtype=np.int32),
+                "cost": np.zeros((0, k)), "prob": np.zeros((0, k)), "selection": np.zeros((k, 0), dtype=np.int64), "leafProbability": np.zeros(0)}
+    group_ptr, cluster_ptr, cluster_targets, local = k_best_prep(tg, R)
+    T, nC = len(group_ptr) - 1, len(cluster_ptr) - 1
+    mine = ctx is None
+    if mine:
+        ctx = Context(device)
+    try:
+        dev, lib = ctx.device, ctx.lib
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        gp_d, cp_d, ct_d, rw_d, c_d = up(group_ptr), up(cluster_ptr), up(cluster_targets), up(local), up(cn)
+        ints = torch.empty((3, nC), dtype=torch.int32, device=dev)
+        hyp = torch.empty((2, k, nC), dtype=torch.float64, device=dev)
+        sel_d = torch.empty((k, T), dtype=torch.int32, device=dev)
+        mar_d = torch.empty(L, dtype=torch.float64, device=dev)
+        need = int(lib.mht_kbest_work_bytes(L, T, nC, D, k))
+        work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
+        _lib.check(lib.mht_kbest_hypotheses(ctx.handle, L, T, nC, D, k, int(nodeLimit), gp_d.data_ptr(), rw_d.data_ptr(), c_d.data_ptr(), cp_d.data_ptr(),
+                                            ct_d.data_ptr(), ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr(), hyp[0].data_ptr(), hyp[1].data_ptr(),
+                                            sel_d.data_ptr(), mar_d.data_ptr(), work.data_ptr(), need), lib)
+        _lib.check(lib.mht_synchronize(ctx.handle), lib)
+        ints, hyp, sel, mar = ints.cpu().numpy(), hyp.cpu().numpy(), sel_d.cpu().numpy(), mar_d.cpu().numpy()
+    finally:
+        if mine:
+            ctx.close()
+    return {"clusters": [cluster_targets[cluster_ptr[c]:cluster_ptr[c + 1]].astype(np.int64) for c in range(nC)],
+            "count": ints[0].copy(), "status": ints[1].copy(), "nodes": ints[2].copy(), "cost": np.ascontiguousarray(hyp[0].T),
+            "prob": np.ascontiguousarray(hyp[1].T), "selection": sel.astype(np.int64), "leafProbability": mar}

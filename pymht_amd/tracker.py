@@ -1484,6 +1484,81 @@ class Tracker():
         out["bestWorstCase"] = evaluation.trial_best(out["pcWorstMax"], out["dcpaMinAll"])
         return out
 
+    def leafRows(self):
+        """The keys of the plots on every current leaf's window path, [L, N + 1] int32 in leafBatch() order (`mht_forest_leaf_rows`): per
+        ancestor with a measurement, from the leaf up to its target's window root (the root itself only where it is the leaf),
+        (level << 24) | measurement number with level = scans back from the current one; -1 elsewhere.  Two leaves share a key exactly
+        where the ILP lets only one of them be selected.  aisAided=True raises NotImplementedError (its columns carry message rows too)."""
+        if self._ais:
+            raise NotImplementedError("leafRows: not for an aisAided tracker -- its ILP columns also carry AIS message rows")
+        snap = self._leaf_snapshot()
+        L, depth = len(snap["node"]), int(self._cfg.n_scan) + 1
+        rows = np.full((max(L, 1), depth), -1, dtype=np.int32)
+        n = C.c_int32(0)
+        _lib.check(self._lib.mht_forest_leaf_rows(self._ctx.handle, L, depth, rows.ctypes.data_as(C.c_void_p), C.byref(n)))
+        if n.value != L:
+            raise RuntimeError("leafRows: the forest has %d leaves, leafBatch() had %d" % (n.value, L))
+        return rows[:L]
+
+    def getGlobalHypotheses(self, k=8, nodeLimit=1 << 20):
+        """The k best GLOBAL hypotheses of every cluster of the current leaves: the joint answers -- one leaf per target, no plot used
+        twice -- ranked by their summed cnllr, where getHypothesisEncounters' weights look at one target at a time.  It answers how
+        ambiguous a cluster is, what the second-best joint explanation is, and how probable a leaf is once the other targets have had
+        their say (evaluation.k_best_hypotheses defines the figures and the search; cost = cnllr, so prob is proportional to
+        exp(-sum cnllr)).  Works for 4-state, 6-state and constant-turn trackers alike: the search is model-free.
+
+        THE LIST IS OVER THE CURRENT LEAVES, AFTER PRUNING: what the last scan's N-scan pruning removed is gone, and a target terminated
+        in the last scan has freed its plots -- so rank 0 may be CHEAPER than the tracker's own selection, which was made with that
+        target still competing.  prob and leafProbability are TRUNCATED to the k listed hypotheses (they sum to 1 over the list, not over
+        all global hypotheses).  Clusters that were not searched (status 2 or 3: beyond 32 targets, 1024 leaves or 2048 plots) are
+        flagged, not guessed.  The clusters are the connected components of targets whose leaves share a plot inside the window: finer
+        than the scan's gating clusters.
+        A target born since the last scan is its own only leaf and takes part with NO key: the number of its plot counts the scan's
+        unused plots (the initiator's numbering, as in the reference), so it says nothing about the plots of the other leaves, and the
+        reference's own ILP never sees it either (a window root is left out of its rows).
+        Returns evaluation.k_best_hypotheses' dict -- clusters, count, status, nodes [C], cost, prob [C, k], selection [k, T],
+        leafProbability [L] -- plus `rows` [L, N + 1] (the keys the search used: leafRows() with those targets' blanked), `ids` (the targets' ids in target order), `leafIds` (the target id of every leaf), `selected` [T]
+        (the leaf of each live track node, found as getHypothesisEncounters finds it; -1 if none) and `selectedRank` [C]: the rank of the
+        tracker's own selection in its cluster's list, or -1 where it is not among the k listed.  No live track: empty arrays, no device
+        call.  aisAided=True raises NotImplementedError."""
+        from . import evaluation
+        if self._ais:
+            raise NotImplementedError("getGlobalHypotheses: not for an aisAided tracker -- its ILP columns also carry AIS message rows")
+        nodes = list(self.__trackNodes__)
+        T = len(nodes)
+        ids = [int(i) for i in self._tbl_["id"]]
+        if T == 0:
+            out = evaluation.k_best_hypotheses(np.zeros(0), np.zeros(0, dtype=np.int32), np.zeros((0, 1), dtype=np.int32), k, nodeLimit)
+            out.update(rows=np.zeros((0, int(self._cfg.n_scan) + 1), dtype=np.int32), ids=ids, leafIds=np.zeros(0, dtype=np.int64),
+                       selected=np.zeros(0, dtype=np.int64), selectedRank=np.zeros(0, dtype=np.int64))
+            return out
+        snap = self.leafBatch()
+        rows = self.leafRows().copy()
+        born = np.array([nd._node < 0 for nd in nodes], dtype=bool)
+        if born.any():      # (see the docstring: such a leaf's key is in the initiator's numbering)
+            tg = snap["target"]
+            rows[born[np.minimum(tg, T - 1)] & (tg < T)] = -1
+        out = evaluation.k_best_hypotheses(snap["cnllr"], snap["target"], rows, k, nodeLimit, ctx=self._ctx)
+        out["rows"] = rows
+        sel = np.full(T, -1, dtype=np.int64)
+        for t, nd in enumerate(nodes):
+            own_leaves = snap["target"] == t
+            if nd._node < 0:      # (born after the last scan: the track node is the root itself, the target's only leaf)
+                hit = np.flatnonzero(own_leaves) if own_leaves.sum() == 1 else ()
+            else:
+                hit = np.flatnonzero(own_leaves & (snap["node"] == nd._node))
+            if len(hit):
+                sel[t] = hit[0]
+        rank = np.full(len(out["clusters"]), -1, dtype=np.int64)
+        for c, tg in enumerate(out["clusters"]):
+            tg = tg[tg < T]
+            for r in range(int(out["count"][c])):
+                if len(tg) and (out["selection"][r, tg] == sel[tg]).all():
+                    rank[c] = r
+                    break
+        out.update(ids=ids, leafIds=snap["ID"].astype(np.int64), selected=sel, selectedRank=rank)
+        return out
+
     def getOspa2(self, truth, c, p=2, window=None, every=1, terminated=True, smooth=False, constantTurn=False, ais=False, truthIds=None):
         """The track histories scored against the truth TRAJECTORIES: OSPA(2) over windows of steps (evaluation.ospa2_windows, which
         defines the figures).  Per-scan GOSPA assigns every scan on its own, so this is the figure that sees whether the targets were
