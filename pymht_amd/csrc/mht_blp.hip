@@ -23,6 +23,7 @@
 // out of LDS; larger clusters run the same code on HBM scratch (L2 resident).
 #include "mht_kernels.h"
 #include "mht_commit.h"
+#include "mht_wave.h"
 #include <stdlib.h>
 
 namespace mht {
@@ -80,39 +81,8 @@ struct Red {
     int i[BLP_THREADS / 64];
 };
 
-// wave64 sum with DPP row shifts / row broadcasts (a handful of VALU ops instead of 12 LDS-crossbar permutes);
-// fixed summation order -> deterministic.  Result is valid in every lane.
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_f64(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    v += dpp_f64<0x111, 0xf>(v);      // row_shr:1
-    v += dpp_f64<0x112, 0xf>(v);      // row_shr:2
-    v += dpp_f64<0x114, 0xf>(v);      // row_shr:4
-    v += dpp_f64<0x118, 0xf>(v);      // row_shr:8   -> lane 15 of every row holds the row sum
-    v += dpp_f64<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
-    v += dpp_f64<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3 -> lane 63 holds the total
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-
-// wave64 INCLUSIVE prefix sum of a 32-bit value, the same row shifts / row broadcasts: six VALU adds where a __shfl_up scan pays an
-// LDS-crossbar permute per step (two for a 64-bit value).  Every lane of the wavefront must be active.
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ unsigned dpp_u32(unsigned v) {
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ unsigned wave_scan_u32(unsigned v) {
-    v += dpp_u32<0x111, 0xf>(v);      // row_shr:1
-    v += dpp_u32<0x112, 0xf>(v);      // row_shr:2
-    v += dpp_u32<0x114, 0xf>(v);      // row_shr:4
-    v += dpp_u32<0x118, 0xf>(v);      // row_shr:8   -> inclusive within every row of 16
-    v += dpp_u32<0x142, 0xa>(v);      // row_bcast:15: the sum of row 0 into row 1, of row 2 into row 3
-    v += dpp_u32<0x143, 0xc>(v);      // row_bcast:31: the sum of rows 0 and 1 into rows 2 and 3
-    return v;
-}
-
+// (wave_sum, wave_scan_u32, wave_min_value, wave_min_pair and their 16-lane rows -- DPP row shifts / row broadcasts instead of
+// LDS-crossbar permutes -- live in mht_wave.h, shared with the grow launch)
 __device__ __forceinline__ double block_sum(double v, Red* r) {
     v = wave_sum(v);
     __syncthreads();
@@ -132,50 +102,6 @@ __device__ __forceinline__ int block_or(int v, Red* r) {
 #pragma unroll
     for (int w = 0; w < BLP_THREADS / 64; ++w) s |= r->i[w];
     return s;
-}
-// minimum of a value over a 16-lane row (result in lane 15 of the row) / the wavefront (result in every lane): three VALU
-// ops per step where the (value, index) pair needs a dozen
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ void dpp_min_value(double& v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int nlo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    const int nhi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    v = fmin(v, __hiloint2double(nhi, nlo));
-}
-__device__ __forceinline__ double row16_min_value(double v) {
-    dpp_min_value<0x111, 0xf>(v);
-    dpp_min_value<0x112, 0xf>(v);
-    dpp_min_value<0x114, 0xf>(v);
-    dpp_min_value<0x118, 0xf>(v);
-    return v;
-}
-__device__ __forceinline__ double wave_min_value(double v) {
-    v = row16_min_value(v);
-    dpp_min_value<0x142, 0xa>(v);      // row_bcast:15
-    dpp_min_value<0x143, 0xc>(v);      // row_bcast:31 -> lane 63 holds the minimum
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-// lexicographic (value, index) minimum over the wavefront with DPP (index -1 = none); result valid in every lane
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ void dpp_min_pair(double& v, int& i) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int nlo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    const int nhi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    const int ni = __builtin_amdgcn_update_dpp(i, i, CTRL, ROW_MASK, 0xf, false);
-    const double nv = __hiloint2double(nhi, nlo);
-    if (ni >= 0 && (i < 0 || nv < v || (nv == v && ni < i))) { v = nv; i = ni; }
-}
-__device__ __forceinline__ void row16_min_pair(double& v, int& i) {      // lane 15 of every 16-lane row gets the row minimum
-    dpp_min_pair<0x111, 0xf>(v, i);
-    dpp_min_pair<0x112, 0xf>(v, i);
-    dpp_min_pair<0x114, 0xf>(v, i);
-    dpp_min_pair<0x118, 0xf>(v, i);
-}
-__device__ __forceinline__ void wave_min_pair(double& v, int& i) {
-    row16_min_pair(v, i);
-    dpp_min_pair<0x142, 0xa>(v, i);      // row_bcast:15
-    dpp_min_pair<0x143, 0xc>(v, i);      // row_bcast:31 -> lane 63 holds the minimum
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63), lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
-    v = __hiloint2double(hi, lo);
-    i = __builtin_amdgcn_readlane(i, 63);
 }
 __device__ __forceinline__ void block_min_pair(double& v, int& i, Red* r) {
     wave_min_pair(v, i);

@@ -5,6 +5,7 @@
 #include "mht_commit.h"
 #include "mht_admit.h"
 #include "mht_uf.h"
+#include "mht_wave.h"
 #include <stddef.h>
 #include <hip/hip_ext.h>
 
@@ -92,12 +93,32 @@ __device__ __forceinline__ int fg_sortable(float f) {      // monotone map float
 }
 
 // per-phase wall-clock stamps (tools/grow_profile.py): compiled in only with -DMHT_GROW_STAMPS
+// (-DMHT_GROW_STAMPS_LAST on top: the LAST wavefront -- union-find links, the overlapping tail -- stamps in wavefront 1's row of the
+// same 16-slot layout; thread 0's emission detail, which shares that row, is off; the row's slot 0 takes the end of the tail)
 #ifdef MHT_GROW_STAMPS
-#define FG_STAMP(k) do { if (d.dbg && (threadIdx.x & 63) == 0 && threadIdx.x < 128 && blockIdx.x < 3900) d.dbg[32 + (size_t)blockIdx.x * 16 + (threadIdx.x >> 6) * 8 + (k)] = wall_clock64(); } while (0)
+#ifdef MHT_GROW_STAMPS_LAST
+#define FG_STAMP_ROW() ((threadIdx.x >> 6) == 0 ? 0 : (threadIdx.x >> 6) == FG_THREADS / 64 - 1 ? 1 : -1)
+#define FG_STAMPX(k)
+#define FG_STAMP_TAIL() do { if (d.dbg && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) == FG_THREADS / 64 - 1 && blockIdx.x < 3900) d.dbg[32 + (size_t)blockIdx.x * 16 + 8] = wall_clock64(); } while (0)
+#else
+#define FG_STAMP_ROW() (threadIdx.x < 128 ? (int)(threadIdx.x >> 6) : -1)
 #define FG_STAMPX(k) do { if (d.dbg && threadIdx.x == 0 && blockIdx.x < 3900) d.dbg[32 + (size_t)blockIdx.x * 16 + 8 + (k)] = wall_clock64(); } while (0)
+#define FG_STAMP_TAIL()
+#endif
+#define FG_STAMP(k) do { if (d.dbg && (threadIdx.x & 63) == 0 && FG_STAMP_ROW() >= 0 && blockIdx.x < 3900) d.dbg[32 + (size_t)blockIdx.x * 16 + FG_STAMP_ROW() * 8 + (k)] = wall_clock64(); } while (0)
+#ifdef MHT_GROW_STAMPS_PREBAR      // stamp 5 in FRONT of the barrier behind the counts: each wavefront's own end of that phase (the wait moves into the next column)
+#define FG_STAMP5_PRE() FG_STAMP(5)
+#define FG_STAMP5_POST()
+#else
+#define FG_STAMP5_PRE()
+#define FG_STAMP5_POST() FG_STAMP(5)
+#endif
 #else
 #define FG_STAMP(k)
 #define FG_STAMPX(k)
+#define FG_STAMP_TAIL()
+#define FG_STAMP5_PRE()
+#define FG_STAMP5_POST()
 #endif
 
 // ---- chain workgroups: the gains one scan ahead --------------------------------------------------------------------------
@@ -235,10 +256,11 @@ __device__ __forceinline__ void chain_part(const ARGS& a, const FDyn& d, int cb,
 // done at ~6 us, long before the target workgroups.)
 
 // ---- target workgroups ---------------------------------------------------------------------------------------------------
-// One child, one ROLE: the four wavefronts of the workgroup all walk the children (lane = child) and each does a quarter of
-// the work -- role 0: x[0..1], cumulativeNLLR; 1: x[2..3], P_d, parent; 2: measurement number, covariance column, flags, ILP
-// cost, used-measurement byte; 3: path and ancestor records.  (One wavefront doing everything was a ~1500-instruction serial
-// stream, 2.9 us; what every role needs -- which hit, z_tilde, NIS, the score -- is recomputed by each.)
+// The emission: ONE thread per child does everything (fg_emit_child) -- which hit, path and ancestor records, z_tilde, NIS, the score,
+// the state, parent, measurement number, covariance key, flags, ILP cost, used-measurement byte: a ~1500-instruction serial stream, 2.7 us.
+// (Splitting a child over wavefronts lost twice: four roles per child, one per wavefront, in round 4 -- three of them redid gate_pair and
+// the score, 16.2 -> 19.5 us; the records alone on the two idle wavefronts of a target with at most 128 children, which repeats only the
+// search for the hit: profiles/grow_workgroup.txt.)
 // AIS forest: the two records of child c.  A path record has two halves of `half` levels: radar measurement nodes, AIS message nodes;
 // the parent's entries from the new root on (level + shift) in both, the child's own rows at level `depth`.
 template <int PQ, typename ARGS>
@@ -290,13 +312,13 @@ __device__ __forceinline__ void fg_emit_fused(const ARGS& a, const FDyn& d, cons
 }
 
 template <typename TS, int PQ, int AIS = 0, typename ARGS = void>
-__device__ __forceinline__ void fg_emit_child(const ARGS& a, const FDyn& d, int role, const FLeaf& g, int l, int c, int k, int nh, const unsigned long long* hwl,
+__device__ __forceinline__ void fg_emit_child(const ARGS& a, const FDyn& d, const FLeaf& g, int l, int c, int k, int nh, const unsigned long long* hwl,
                                               const float* zx, const float* zy, const int* s_pp, const int* s_ap, int depth, int shift,
                                               double rootc, int root_f32, const unsigned short* cand = nullptr, const float2* zg = nullptr,
                                               const FLeafX* gx = nullptr) {
     // (gx != null && gx->f64 -- AIS forest, a promoted target: float64 gains, TS = double, the children's covariances are float64)
-    // (cand != null -- the wavefront-per-target kernel: the hit words index the target's candidate list, and the scan is read from
-    // global memory, zg, not from an LDS copy)
+    // (cand != null -- the hit words index the target's candidate list: constant-turn kernel, wavefront-per-target kernel; zg != null -- the
+    // scan is read from global memory, not from an LDS copy)
     const size_t cap = a.cap;
     const uint8_t fl = g.flags;
     int meas = 0, hit = 0, j = -1;
@@ -318,7 +340,7 @@ __device__ __forceinline__ void fg_emit_child(const ARGS& a, const FDyn& d, int 
     FG_STAMPX(2);
     if (AIS) {
         fg_emit_records_ais<PQ>(a, l, c, depth, shift, meas > 0 ? a.cur_slot_base + meas - 1 : -1, -1, s_pp, s_ap);
-    } else if (role == 3 || role < 0) {
+    } else {
         // path / ancestor records of the child: the parent's entries from the new root on (d + shift), its own at level `depth`
         const int* pl = s_pp + l * (PQ * 4);
         const int* al = s_ap + l * (PQ * 4);
@@ -339,7 +361,6 @@ __device__ __forceinline__ void fg_emit_child(const ARGS& a, const FDyn& d, int 
                 po[q] = make_int4(pe[0], pe[1], pe[2], pe[3]);
                 ao[q] = make_int4(ae[0], ae[1], ae[2], ae[3]);
             }
-        if (role == 3) return;
     }
     FG_STAMPX(3);
     double cnl;
@@ -364,7 +385,7 @@ __device__ __forceinline__ void fg_emit_child(const ARGS& a, const FDyn& d, int 
         }
     }
     FG_STAMPX(4);
-    if (role < 0) {          // (all state components)
+    {
         double xo[NX];
 #pragma unroll
         for (int i = 0; i < NX; ++i) xo[i] = g.xbar[i];
@@ -379,22 +400,6 @@ __device__ __forceinline__ void fg_emit_child(const ARGS& a, const FDyn& d, int 
         a.ocnllr[c] = cnl;
         a.opd[c] = g.pd;
         a.oparent[c] = g.src;
-    } else if (role < 2) {          // two state components each
-        const int i0 = 2 * role, i1 = 2 * role + 1;
-        double x0 = g.xbar[i0], x1 = g.xbar[i1];
-        if (k > 0) {
-            x0 = (double)update_component_n<TS>((TS)g.xbar[i0], g.K[i0 * 2], g.K[i0 * 2 + 1], zt, nh == 1);
-            x1 = (double)update_component_n<TS>((TS)g.xbar[i1], g.K[i1 * 2], g.K[i1 * 2 + 1], zt, nh == 1);
-        }
-        a.ox[(size_t)i0 * cap + c] = x0;
-        a.ox[(size_t)i1 * cap + c] = x1;
-        if (role == 0) {
-            a.ocnllr[c] = cnl;
-        } else {
-            a.opd[c] = g.pd;
-            a.oparent[c] = g.src;
-        }
-        return;
     }
     FG_STAMPX(5);
     a.omeas[c] = meas;
@@ -570,8 +575,7 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
         rebuilt_levels = (ti.shift > 0 || rl == WIN_REBUILT_ALL) ? (1 << 20) : rl;      // (shift > 0: the root advanced in the scan before -- that commit may still be pending)
     }
     for (int w = tid; w < AW; w += FG_THREADS) tb[w] = 0ull;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = wave_sum_i32(acc);      // (the wavefront sums, scans and box reduction of this function: DPP row shifts, mht_wave.h -- no LDS round trip per step)
     if (lane == 0) s_red[wave] = acc;      // (summed behind the first barrier below: nothing needs the index before the allocation)
     if (tid < 4 && tid >= FG_THREADS / 64) s_red[tid] = 0;
     const int depth0 = ti.depth, shift0 = ti.shift, cnt = ti.cnt, first = ti.first;
@@ -580,8 +584,7 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
         __syncthreads();
         int nl = 0;
         for (int i = tid; i < cnt; i += FG_THREADS) nl += (a.flags[first + i] & F_DEAD) ? 0 : 1;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nl += __shfl_xor(nl, o);
+        nl = wave_sum_i32(nl);
         if (lane == 0 && nl) atomicAdd(&s_live, nl);
         __syncthreads();
     }
@@ -773,11 +776,7 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                 loy -= fabsf(loy) * 2.4e-7f + 1e-30f; hiy += fabsf(hiy) * 2.4e-7f + 1e-30f;
                 int b0 = valid ? fg_sortable(lox) : 0x7fffffff, b1 = valid ? fg_sortable(hix) : (int)0x80000000;
                 int b2 = valid ? fg_sortable(loy) : 0x7fffffff, b3 = valid ? fg_sortable(hiy) : (int)0x80000000;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    b0 = min(b0, __shfl_xor(b0, o)); b1 = max(b1, __shfl_xor(b1, o));
-                    b2 = min(b2, __shfl_xor(b2, o)); b3 = max(b3, __shfl_xor(b3, o));
-                }
+                b0 = wave_min_i32(b0); b1 = wave_max_i32(b1); b2 = wave_min_i32(b2); b3 = wave_max_i32(b3);
                 if (lane == 0) { s_boxp[wave * 4] = b0; s_boxp[wave * 4 + 1] = b1; s_boxp[wave * 4 + 2] = b2; s_boxp[wave * 4 + 3] = b3; }
             }
             __syncthreads();
@@ -888,19 +887,13 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                 for (int w = 0; w < W; ++w) { h0 += __popcll(hw[(size_t)lane * W + w]); h1 += __popcll(hw[(size_t)l1 * W + w]); }
                 if (AIS) { h0 += s_ais[lane * 4]; h1 += s_ais[l1 * 4]; }      // (fused children behind the radar children)
                 const int m0 = (lane < n && lg[lane].valid) ? 1 + h0 : 0, m1 = (lane + 64 < n && lg[l1].valid) ? 1 + h1 : 0;
-                int i0 = m0, i1 = m1;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int v0 = __shfl_up(i0, o), v1 = __shfl_up(i1, o);
-                    if (lane >= o) { i0 += v0; i1 += v1; }
-                }
-                const int t0 = __shfl(i0, 63);
-                i1 += t0;
+                const int i0 = (int)wave_scan_u32((unsigned)m0);      // (inclusive prefixes of the two halves)
+                const int i1 = (int)wave_scan_u32((unsigned)m1) + __builtin_amdgcn_readlane(i0, 63);
                 s_pref[lane] = i0 - m0;
                 if (lane + 64 < CAP) s_pref[64 + lane] = i1 - m1;
                 for (int q = 0, p = i0 - m0; q < m0 && p < FG_MAP; ++q, ++p) s_map[p] = (unsigned char)lane;          // child -> leaf
                 for (int q = 0, p = i1 - m1; q < m1 && p < FG_MAP; ++q, ++p) s_map[p] = (unsigned char)(lane + 64);
-                const int chunk_total = __shfl(i1, 63);
+                const int chunk_total = __builtin_amdgcn_readlane(i1, 63);
                 if (lane == 63) { s_pref[CAP] = chunk_total; s_total = chunk_total; }
                 if (first_emit && lane == 0) {
                     const int tot = two_pass ? total : chunk_total;
@@ -933,8 +926,7 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                 // measurement and the hits; with two passes the count pass has seen all chunks)
                 int ne = 0;
                 for (int w = lane; w < AW; w += 64) ne += __popcll(tb[w]);
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) ne += __shfl_xor(ne, o);
+                ne = wave_sum_i32(ne);
                 if (lane == 0) {
                     const int seg = blockIdx.x & (EDGE_SEGS - 1);
                     const int e0 = atomicAdd(&a.edge_count[seg], ne);
@@ -942,8 +934,9 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                     if (e0 + ne > a.edge_cap) a.status->overflow = 1;
                 }
             }
+            FG_STAMP5_PRE();
             __syncthreads();
-            FG_STAMP(5);
+            FG_STAMP5_POST();
             if (pass == 0) {
                 total += s_total;
                 __syncthreads();
@@ -978,12 +971,7 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                         const int w = w0 + lane;
                         unsigned long long bits = (w < AW) ? tb[w] : 0ull;
                         const int pc = __popcll(bits);
-                        int incl = pc;
-#pragma unroll
-                        for (int o = 1; o < 64; o <<= 1) {
-                            const int v = __shfl_up(incl, o);
-                            if (lane >= o) incl += v;
-                        }
+                        const int incl = (int)wave_scan_u32((unsigned)pc);
                         int my = eb + incl - pc;
                         while (bits) {
                             const int bpos = __ffsll((long long)bits) - 1;
@@ -991,11 +979,10 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                             if (my < a.edge_cap) a.edges[(size_t)seg * a.edge_cap + my] = ((unsigned)pos << 16) | (unsigned)(w * 64 + bpos);
                             ++my;
                         }
-                        eb += __shfl(incl, 63);
+                        eb += __builtin_amdgcn_readlane(incl, 63);
                     }
                 }
             }
-            // ---- phase 4: lane = child, wavefront = role; children of the chunk at base + run .. --------------------------------------
             FG_STAMP(6);
             // ---- phase 4: one thread per child; children of the chunk at base + run .. ------------------------------------------------
             {
@@ -1038,15 +1025,15 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
 #pragma unroll
                                 for (int q = 0; q < (int)(sizeof(FLeafX) / 16); ++q) dstq[q] = srcq[q];
                             }
-                            if (g.f32state) fg_emit_child<float, PQ, 1>(a, d, -1, g, l, c, k, nhr, hw + (size_t)l * W, zx, zy, s_pp, s_ap, depth, shift, rootc, root_f32);
-                            else fg_emit_child<double, PQ, 1>(a, d, -1, g, l, c, k, nhr, hw + (size_t)l * W, zx, zy, s_pp, s_ap, depth, shift, rootc, root_f32, nullptr, nullptr, &gx);
+                            if (g.f32state) fg_emit_child<float, PQ, 1>(a, d, g, l, c, k, nhr, hw + (size_t)l * W, zx, zy, s_pp, s_ap, depth, shift, rootc, root_f32);
+                            else fg_emit_child<double, PQ, 1>(a, d, g, l, c, k, nhr, hw + (size_t)l * W, zx, zy, s_pp, s_ap, depth, shift, rootc, root_f32, nullptr, nullptr, &gx);
                         }
                     } else {
                         // (constant-turn kernel: the leaf's hit words index the candidate list -- unless they were spilled, full width, to global memory)
                         const unsigned long long* hwl = (CMP && spill) ? hwg + (size_t)l * W : hw + (size_t)l * hstride;
                         const unsigned short* cmap = (CMP && !spill) ? cand : nullptr;
-                        if (g.f32state) fg_emit_child<float, PQ>(a, d, -1, g, l, c, k, nh, hwl, zx, zy, s_pp, s_ap, depth, shift, rootc, root_f32, cmap);
-                        else fg_emit_child<double, PQ>(a, d, -1, g, l, c, k, nh, hwl, zx, zy, s_pp, s_ap, depth, shift, rootc, root_f32, cmap);
+                        if (g.f32state) fg_emit_child<float, PQ>(a, d, g, l, c, k, nh, hwl, zx, zy, s_pp, s_ap, depth, shift, rootc, root_f32, cmap);
+                        else fg_emit_child<double, PQ>(a, d, g, l, c, k, nh, hwl, zx, zy, s_pp, s_ap, depth, shift, rootc, root_f32, cmap);
                     }
                 }
                 run += ctot;
@@ -1062,8 +1049,11 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
         // (Nearly always the index IS the slot -- no target died in the previous scan, the commit's word says so -- and the target's
         // place in the union-find, taken under the slot next to the emission, stands.  Otherwise: once more, under the compacted index and
         // the scan's alternative epoch, which the ILP launch then reads.)
+        // (Tried: the last wavefront alone, behind its links and its share of the emission, without the barrier -- below the bar,
+        // profiles/grow_workgroup.txt.)
         __syncthreads();      // (the candidate list's LDS is free: the union-find's list goes there)
         target_tail(a, d, t, base, fin_tot, tb, reinterpret_cast<int*>(cand), Mpad / 2, &s_misc[17]);
+        FG_STAMP_TAIL();
     }
 }
 
@@ -1415,8 +1405,8 @@ __device__ __forceinline__ void target_wave(KArgs ap0, const FDyn& d, int t, uns
 #else
                     const int* e_pp = a.in_path + (size_t)(first + c0) * PDS; const int* e_ap = a.in_apath + (size_t)(first + c0) * PDS;      // (leaf l of the pass = node first + c0 + l)
 #endif
-                    if (gc.f32state) fg_emit_child<float, PQ>(a, d, -1, gc, l, c, k, nh, mk + l * nblk, zdummy, zdummy, e_pp, e_ap, depth, shift, rootc, root_f32, cand, z2);
-                    else fg_emit_child<double, PQ>(a, d, -1, gc, l, c, k, nh, mk + l * nblk, zdummy, zdummy, e_pp, e_ap, depth, shift, rootc, root_f32, cand, z2);
+                    if (gc.f32state) fg_emit_child<float, PQ>(a, d, gc, l, c, k, nh, mk + l * nblk, zdummy, zdummy, e_pp, e_ap, depth, shift, rootc, root_f32, cand, z2);
+                    else fg_emit_child<double, PQ>(a, d, gc, l, c, k, nh, mk + l * nblk, zdummy, zdummy, e_pp, e_ap, depth, shift, rootc, root_f32, cand, z2);
                 }
                 FW_STAMP(6);
                 // The gains one scan ahead (chain_part's job, folded into the target's wavefront here: a launch of many sectors has no idle
