@@ -617,6 +617,48 @@ int mht_trial_hypotheses(mht_ctx* ctx, int32_t nx, int32_t L, int32_t T, int32_t
                          const double* own, const double* Sown, double w, const double* cand, double* table, double* fig, double* weight,
                          void* work, size_t work_bytes);
 
+/* mht_mc_encounters: encounters by MONTE CARLO.  Every target is a Gaussian mixture of components -- the leaves of the forest with
+ * their weights --; `particles` particles per target are drawn from it, walked over `steps` steps of dt seconds WITH process noise, and
+ * held against G paths of the own ship (csrc/mht_mc.h states the method, the random numbers and the order of every sum).  It answers
+ * what the Gaussian rule of mht_encounters cannot: the probability of coming within R AT ANY TIME of the horizon (a first-passage
+ * figure over correlated steps), a target whose hypotheses disagree (a mixture), and the constant-turn model, whose transition
+ * Phi(dt, w) is taken at every particle's own turn rate.
+ *   nx, transition   4 or 6 states; 0: linear, x+ = Phi x + noise; 1: constant turn (models/ct.py's state, nx 6 only), Phi is not read
+ *   nComp, nTarget   components and targets, 1 <= nTarget <= nComp
+ *   G, steps, particles   1 .. MHT_MC_MAX_PATHS, 1 .. MHT_MC_MAX_STEPS, a multiple of MHT_MC_WARP in MHT_MC_WARP .. MHT_MC_MAX_PARTICLES
+ *   seed             of the Philox4x32-10 stream: one seed, one result, bit for bit, on any device and under any grid
+ *   dt, radius       the step and the safety radius R, positive and finite
+ *   Phi, Q           HOST [nx][nx] row-major f64, finite; of Q the upper triangle is read.  Q is positive SEMIdefinite (models/ct.Q
+ *                    has rank 3): it is factored on the host with a zero-pivot rule
+ *   x, P             dev [nx][nComp] f64 and dev packed upper [nx (nx + 1) / 2][nComp] f64; a P may be singular or zero
+ *   first            dev [nTarget + 1] int32: a target's components are first[t] .. first[t + 1] - 1; first[0] = 0, STRICTLY ascending,
+ *                    first[nTarget] = nComp.  Read back and checked before anything is launched
+ *   cdf              dev [nComp] f64: the cumulative weight inside the target, its last entry 1.0
+ *   ownPath          dev [G][steps + 1][2] f64: the own ship's position at every step of every path
+ *   within           dev [G][steps + 1][nTarget] uint32 out: the particles with |X_k - own_k| < R at step k
+ *   ever             dev [G][nTarget] uint32 out: the particles whose piecewise-linear path comes inside R; ever >= within at every step
+ *   valid            dev [nTarget] uint32 out: `particles` for a scored target, else 0 -- the divisor of the counts
+ *   status           dev [nTarget] int32 out: MHT_MC_OK; MHT_MC_NAN: a NaN in a component's x, P or cdf; MHT_MC_NOT_PSD: a component's
+ *                    P is not positive semidefinite.  Every count of such a target is 0
+ *   work             dev, at least mht_mc_work_bytes(nx, nComp, nTarget, G, steps, particles) bytes (0 for arguments out of range)
+ * Three launches (a component per lane: the factors; a workgroup per slab of a target's particles, a particle per lane; the fold of the
+ * slabs), no atomic.  Synchronises.
+ * MHT_E_INVALID: a null pointer (Phi may be null with transition 1), arguments out of range, a Phi or Q that is not finite, a Q that is
+ * not positive semidefinite, a short work buffer, a `first` that does not ascend strictly from 0 to nComp; nothing has then been
+ * launched or written.  Out of scope: pairs of targets, an own-ship covariance, correlation between targets.  Exported by both builds. */
+#define MHT_MC_MAX_PATHS 64            /* own paths per call */
+#define MHT_MC_MAX_STEPS 64            /* steps of the horizon */
+#define MHT_MC_MAX_PARTICLES 1048576   /* particles per target, 2^20 */
+#define MHT_MC_WARP 64                 /* particles come in multiples of a wavefront */
+#define MHT_MC_OK 0                    /* status: scored */
+#define MHT_MC_NAN 1                   /* a NaN in a component's x, P or cdf */
+#define MHT_MC_NOT_PSD 2               /* a component's P is not positive semidefinite */
+size_t mht_mc_work_bytes(int32_t nx, int32_t nComp, int32_t nTarget, int32_t G, int32_t steps, int32_t particles);
+int mht_mc_encounters(mht_ctx* ctx, int32_t nx, int32_t transition, int32_t nComp, int32_t nTarget, int32_t G, int32_t steps, int32_t particles,
+                      uint64_t seed, double dt, double radius, const double* Phi, const double* Q, const double* x, const double* P,
+                      const int32_t* first, const double* cdf, const double* ownPath, uint32_t* within, uint32_t* ever, uint32_t* valid,
+                      int32_t* status, void* work, size_t work_bytes);
+
 /* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
  * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);
  * with d_ij = sqrt(dx dx + dy dy) in float64 and only pairs with d_ij < c (strictly) assignable,

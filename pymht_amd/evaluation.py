@@ -839,6 +839,185 @@ def trial_best(pcMax, dcpaMin):
     return None if best is None else best[2]
 
 
+# ---- encounters by Monte Carlo: at any time of the horizon, for a mixture, and for the constant-turn model ------------------------------
+MC_MAX_PATHS, MC_MAX_STEPS, MC_MAX_PARTICLES, MC_WARP = 64, 64, 1 << 20, 64      # MHT_MC_*, include/mht_amd.h
+MC_OK, MC_NAN, MC_NOT_PSD = 0, 1, 2
+MC_COUNT_NAMES = ("within", "ever", "valid", "status")
+
+
+def mc_own_paths(own, candidates, turnRate, steps, dt):
+    """The own ship's positions at t = k dt, k = 0 .. steps, for every candidate manoeuvre (dpsi, f, t0): float64 [G, steps + 1, 2].  The
+    manoeuvre of `trial_manoeuvres` (csrc/mht_trial.h: stand on until t0, an arc at rate sign(dpsi) turnRate and speed f |v0| until
+    te = t0 + |dpsi| / turnRate, then straight), in NumPy, every operation in the header's order.  A NaN in a candidate or in `own`
+    makes that candidate's path NaN.  ValueError as `trial_manoeuvres` raises them."""
+    try:
+        w, dt = _trial_number("turnRate", turnRate), _trial_number("dt", dt)
+        cand = trial_candidates(candidates)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("trial_manoeuvres", "mc_own_paths", 1))
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= MC_MAX_STEPS:
+        raise ValueError("mc_own_paths: steps is an integer in 1 .. %d (got %r)" % (MC_MAX_STEPS, steps))
+    try:
+        o = np.ascontiguousarray(own, dtype=np.float64)
+    except (TypeError, ValueError):
+        o = np.zeros(0)
+    if o.shape != (4,) or np.isinf(o).any():
+        raise ValueError("mc_own_paths: own is [x, y, vx, vy], finite or NaN (got %r)" % (own,))
+    p0x, p0y, v0x, v0y = o
+    dpsi, f, t0 = cand[:, 0], cand[:, 1], cand[:, 2]
+    bad = np.isnan(cand).any(axis=1) | np.isnan(o).any()
+    out = np.zeros((len(cand), int(steps) + 1, 2))
+    with np.errstate(all="ignore"):
+        ad = np.abs(dpsi)
+        sg = np.where(dpsi > 0, 1.0, np.where(dpsi < 0, -1.0, 0.0))
+        te = t0 + ad / w
+        ax, ay = p0x + t0 * v0x, p0y + t0 * v0y
+        se, ce = np.sin(ad), np.cos(ad)
+        swe, cwe = se / w, (1.0 - ce) / w
+        bx, by = ax + f * (swe * v0x - (sg * cwe) * v0y), ay + f * ((sg * cwe) * v0x + swe * v0y)
+        ux, uy = f * (ce * v0x - (sg * se) * v0y), f * ((sg * se) * v0x + ce * v0y)
+        for k in range(int(steps) + 1):
+            t = float(k) * dt
+            tau = t - t0
+            sn, cs = np.sin(w * tau), np.cos(w * tau)
+            sw, cw = sn / w, (1.0 - cs) / w
+            arc_x, arc_y = ax + f * (sw * v0x - (sg * cw) * v0y), ay + f * ((sg * cw) * v0x + sw * v0y)
+            r = t - te
+            out[:, k, 0] = np.where(t <= t0, p0x + t * v0x, np.where(t <= te, arc_x, bx + r * ux))
+            out[:, k, 1] = np.where(t <= t0, p0y + t * v0y, np.where(t <= te, arc_y, by + r * uy))
+    out[bad] = np.nan
+    return out
+
+
+def mc_standard_error(p, valid):
+    """sqrt(max(p (1 - p), 1 / S) / S): the binomial standard error of a share p of S particles, floored at one particle so that a
+    count of 0 or S does not claim certainty.  NaN where valid is 0."""
+    S = np.asarray(valid, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        return np.where(S > 0, np.sqrt(np.fmax(p * (1.0 - p), 1.0 / S) / S), np.nan)
+
+
+def mc_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, ownPaths, particles=4096, seed=0, transition="linear", device=0, ctx=None):
+    """Encounters by MONTE CARLO: every target is the Gaussian mixture of its components, `particles` particles per target are drawn from
+    it, walked over steps * dt seconds WITH the model's process noise, and held against G paths of the own ship
+    (csrc/mht_mc.h states the method).  It answers what the Gaussian rule of `encounters` cannot: the probability of coming within
+    `radius` AT ANY TIME of the horizon (a first-passage figure over correlated steps, not the largest per-step mass), a target whose
+    hypotheses disagree (a mixture is sampled as what it is, not averaged cell by cell), and the constant-turn model, walked with
+    Phi(dt, w) at every particle's own turn rate.
+
+    x, P       the components: x [L, nx] (nx 4 or 6), P [L, nx, nx] symmetric (the upper triangle is read); a P may be singular or 0
+    target     [L] integers, any order: the target of every component.  The targets of the result are the distinct values, ascending;
+               the components are grouped by a STABLE sort, which the result returns as `order`
+    weight     [L] >= 0: the components' weights inside their target (any scale).  A target whose weights are all 0, or whose sum is
+               not finite, raises ValueError
+    Phi, Q     [nx, nx] of one step of dt seconds; Q positive SEMIdefinite (models/ct.Q has rank 3).  transition="ct": Phi is not read
+    steps, dt, radius   1 .. 64 steps of dt > 0 seconds; the safety radius > 0
+    ownPaths   [G, steps + 1, 2], G in 1 .. 64, finite: the own ship's position at every step, e.g. `mc_own_paths`
+    particles  S, a multiple of 64 in 64 .. 2^20;  seed: 0 .. 2^64 - 1 -- one seed, one result, bit for bit (Philox4x32-10, counter
+               (particle, step, rank of the target, block): a target's stream does not depend on which component a particle picks)
+    transition "linear", or "ct": models/ct.py's six states, x+ = Phi(dt, x[4]) x + noise
+    ValueError for arguments that do not fit -- before any device is needed.  No component: empty arrays and no device call.
+    Returns a dict.  As the device wrote them: `within` [G, steps + 1, T] and `ever` [G, T] (uint32 counts), `valid` [T] (S for a
+    scored target, else 0) and `status` [T] (0; 1: a NaN in a component; 2: a P that is not positive semidefinite).  Derived on the
+    host, NaN where valid is 0: `pc` = within / valid; `pcMax` [G, T] and `tpc`, the largest pc over the steps and the time k dt of the
+    EARLIEST largest; `pEver` = ever / valid; `sePcMax` and `sePEver`, sqrt(max(p (1 - p), 1 / S) / S) -- a Monte-Carlo figure is not
+    to be read without its error bar.  And `targets` [T], `first` [T + 1], `cdf` [L] and `order` [L] as they were used.
+    Out of scope: pairs of targets, an own-ship covariance, correlation between targets, more than 2^20 particles.
+    One upload, one call of `mht_mc_encounters` (three launches), no host fallback."""
+    X, Pm = np.asarray(x, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    Phi, Q = np.asarray(Phi, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    nx = X.shape[1] if X.ndim == 2 else -1
+    if nx not in (4, 6):
+        raise ValueError("mc_encounters: the states are an [L, 4] or [L, 6] array (got shape %r)" % (X.shape,))
+    L = len(X)
+    if transition not in ("linear", "ct") or (transition == "ct" and nx != 6):
+        raise ValueError("mc_encounters: transition is \"linear\" or, with six states, \"ct\" (got %r with %d states)" % (transition, nx))
+    if Pm.shape != (L, nx, nx) or Phi.shape != (nx, nx) or Q.shape != (nx, nx):
+        raise ValueError("mc_encounters: P, Phi and Q have shapes %r, %r and %r; [%d, %d, %d] and twice [%d, %d] are wanted"
+                         % (Pm.shape, Phi.shape, Q.shape, L, nx, nx, nx, nx))
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= MC_MAX_STEPS:
+        raise ValueError("mc_encounters: steps is an integer in 1 .. %d (got %r)" % (MC_MAX_STEPS, steps))
+    for name, v in (("dt", dt), ("radius", radius)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+            raise ValueError("mc_encounters: %s must be a finite positive number (got %r)" % (name, v))
+    if isinstance(particles, bool) or not isinstance(particles, (int, np.integer)) or not MC_WARP <= particles <= MC_MAX_PARTICLES or particles % MC_WARP:
+        raise ValueError("mc_encounters: particles is a multiple of %d in %d .. %d (got %r)" % (MC_WARP, MC_WARP, MC_MAX_PARTICLES, particles))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
+        raise ValueError("mc_encounters: seed is an integer in 0 .. 2^64 - 1 (got %r)" % (seed,))
+    if not (np.isfinite(Q).all() and (transition == "ct" or np.isfinite(Phi).all())):
+        raise ValueError("mc_encounters: Phi and Q must be finite")
+    steps, S = int(steps), int(particles)
+    try:
+        own = np.ascontiguousarray(ownPaths, dtype=np.float64)
+    except (TypeError, ValueError):
+        own = np.zeros(0)
+    if own.ndim != 3 or own.shape[1:] != (steps + 1, 2) or not 1 <= len(own) <= MC_MAX_PATHS or not np.isfinite(own).all():
+        raise ValueError("mc_encounters: ownPaths is a finite [G, steps + 1, 2] = [G, %d, 2] array, G in 1 .. %d (got shape %r)" % (steps + 1, MC_MAX_PATHS, own.shape))
+    tg, wt = np.asarray(target), np.asarray(weight, dtype=np.float64)
+    if tg.shape != (L,) or not np.issubdtype(tg.dtype, np.integer):
+        raise ValueError("mc_encounters: target is an [L] = [%d] array of integers (got %r)" % (L, target))
+    if wt.shape != (L,) or (wt < 0).any():
+        raise ValueError("mc_encounters: weight is an [L] = [%d] array of numbers >= 0 (got %r)" % (L, weight))
+    order = np.argsort(tg, kind="stable")
+    targets, start = np.unique(tg[order], return_index=True)
+    T, G = len(targets), len(own)
+    first = np.append(start, L).astype(np.int32)
+    cdf = np.zeros(L)
+    for t in range(T):
+        w = wt[order[first[t]:first[t + 1]]]
+        total = w.sum()
+        if not np.isfinite(total) or not total > 0:
+            raise ValueError("mc_encounters: the weights of target %d are all 0 or not finite" % int(targets[t]))
+        cdf[first[t]:first[t + 1]] = np.cumsum(w / total)
+        cdf[first[t + 1] - 1] = 1.0
+    res = dict(targets=targets.astype(np.int64), first=first, cdf=cdf, order=order.astype(np.int64))
+    if L == 0:
+        res.update(within=np.zeros((G, steps + 1, 0), dtype=np.uint32), ever=np.zeros((G, 0), dtype=np.uint32), valid=np.zeros(0, dtype=np.uint32),
+                   status=np.zeros(0, dtype=np.int32))
+    else:
+        iu = np.triu_indices(nx)
+        xp, Pp = np.ascontiguousarray(X[order].T), np.ascontiguousarray(Pm[order][:, iu[0], iu[1]].T)
+        Phi, Q = np.ascontiguousarray(Phi), np.ascontiguousarray(Q)
+        mine = ctx is None
+        if mine:
+            ctx = Context(device, nx=nx)
+        try:
+            dev, lib = ctx.device, ctx.lib
+            x_d, P_d, f_d, c_d, o_d = [torch.from_numpy(a).to(dev) for a in (xp, Pp, first, cdf, own)]
+            need = int(lib.mht_mc_work_bytes(nx, L, T, G, steps, S))
+            work = torch.empty(need, dtype=torch.uint8, device=dev)
+            # (uint32 counts in int32 tensors: the same bits)
+            w_d, e_d = torch.empty((G, steps + 1, T), dtype=torch.int32, device=dev), torch.empty((G, T), dtype=torch.int32, device=dev)
+            v_d, s_d = torch.empty(T, dtype=torch.int32, device=dev), torch.empty(T, dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
+            _lib.check(lib.mht_mc_encounters(ctx.handle, nx, 1 if transition == "ct" else 0, L, T, G, steps, S, int(seed), float(dt), float(radius),
+                                             Phi.ctypes.data, Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(), f_d.data_ptr(), c_d.data_ptr(), o_d.data_ptr(),
+                                             w_d.data_ptr(), e_d.data_ptr(), v_d.data_ptr(), s_d.data_ptr(), work.data_ptr(), need), lib)
+            res.update(within=w_d.cpu().numpy().view(np.uint32), ever=e_d.cpu().numpy().view(np.uint32), valid=v_d.cpu().numpy().view(np.uint32),
+                       status=s_d.cpu().numpy())
+        finally:
+            if mine:
+                ctx.close()
+    res.update(mc_derive(res["within"], res["ever"], res["valid"], float(dt)))
+    return res
+
+
+def mc_derive(within, ever, valid, dt):
+    """The host's figures of `mc_encounters` from its counts: pc, pcMax, tpc, pEver, sePcMax, sePEver (NaN where valid is 0)"""
+    v = np.asarray(valid, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        pc = np.where(v > 0, within / v, np.nan)
+        p_ever = np.where(v > 0, ever / v, np.nan)
+    G, K1, T = pc.shape
+    pc_max, tpc = np.full((G, T), np.nan), np.full((G, T), np.nan)
+    if T:
+        scored = v > 0
+        arg = np.argmax(np.where(scored, pc, -1.0), axis=1)      # (the first of equal largest)
+        pc_max = np.where(scored, np.take_along_axis(pc, arg[:, None, :], axis=1)[:, 0, :], np.nan)
+        tpc = np.where(scored, arg * dt, np.nan)
+    return dict(pc=pc, pcMax=pc_max, tpc=tpc, pEver=p_ever, sePcMax=mc_standard_error(pc_max, v), sePEver=mc_standard_error(p_ever, v))
+
+
 # ---- the k best global hypotheses ---------------------------------------------------------------------------------------------------
 KBEST_MAX_K, KBEST_MAX_TARGETS, KBEST_MAX_COLUMNS, KBEST_MAX_DEPTH, KBEST_MAX_ROWS = 64, 32, 1024, 16, 2048      # MHT_KBEST_*, include/mht_amd.h
 KBEST_OK, KBEST_NODE_LIMIT, KBEST_TOO_LARGE, KBEST_BAD_ROWS = 0, 1, 2, 3

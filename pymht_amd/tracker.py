@@ -1395,6 +1395,22 @@ class Tracker():
         out["best"] = evaluation.trial_best(out["pcMax"], out["dcpaMin"])
         return out
 
+    @staticmethod
+    def _selected_leaves(snap, nodes):
+        """Per live track node the index of its leaf in leafBatch()'s arrays, or -1: the leaf of the node's target whose node is the track
+        node's (a target born since the last scan is its own only leaf).  THE selection rule of getHypothesisEncounters,
+        getGlobalHypotheses and getMonteCarloEncounters."""
+        sel = np.full(len(nodes), -1, dtype=np.int64)
+        for t, nd in enumerate(nodes):
+            own_leaves = snap["target"] == t
+            if nd._node < 0:      # (born after the last scan: the track node is the root itself, the target's only leaf)
+                hit = np.flatnonzero(own_leaves) if own_leaves.sum() == 1 else ()
+            else:
+                hit = np.flatnonzero(own_leaves & (snap["node"] == nd._node))
+            if len(hit):
+                sel[t] = hit[0]
+        return sel
+
     def getHypothesisEncounters(self, horizon, radius, ownShip, courseChanges=(0.0,), turnRate=None, speedFactors=(1.0,), delay=0.0, ownCovariance=None,
                                 steps=None, leafTable=False):
         """getTrialManoeuvres held against EVERY LIVE HYPOTHESIS of every target, not only the selected one.  This is a multi-hypothesis
@@ -1453,15 +1469,7 @@ class Tracker():
         ids = [int(i) for i in self._tbl_["id"]]
         if T:
             snap = self.leafBatch()
-            sel = np.full(T, -1, dtype=np.int64)
-            for t, nd in enumerate(nodes):
-                own_leaves = snap["target"] == t
-                if nd._node < 0:      # (born after the last scan: the track node is the root itself, the target's only leaf)
-                    hit = np.flatnonzero(own_leaves) if own_leaves.sum() == 1 else ()
-                else:
-                    hit = np.flatnonzero(own_leaves & (snap["node"] == nd._node))
-                if len(hit):
-                    sel[t] = hit[0]
+            sel = self._selected_leaves(snap, nodes)
             x, P, cn, tg, leaf_ids = snap["x"], np.asarray(snap["P"], dtype=np.float64), snap["cnllr"], snap["target"], snap["ID"].astype(np.int64)
         else:
             x, P, cn, tg, sel, leaf_ids = np.zeros((0, nx)), np.zeros((0, nx, nx)), np.zeros(0), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
@@ -1482,6 +1490,115 @@ class Tracker():
             out[name], out[name + "Target"] = val, arg
         out["best"] = evaluation.trial_best(out["pcMeanMax"], out["dcpaMinAll"])
         out["bestWorstCase"] = evaluation.trial_best(out["pcWorstMax"], out["dcpaMinAll"])
+        return out
+
+    def getMonteCarloEncounters(self, horizon, radius, ownShip, particles=4096, seed=0, courseChanges=(0.0,), turnRate=None, speedFactors=(1.0,), delay=0.0,
+                                steps=None, hypotheses=True, weights=None):
+        """Encounters by MONTE CARLO (evaluation.mc_encounters defines the figures): particles drawn from the forest's own leaves -- a
+        Gaussian mixture per target --, walked with the model's process noise and held against the own ship's candidate paths.  It gives
+        what getEncounters, getTrialManoeuvres and getHypothesisEncounters cannot: `pEver`, the probability of coming within `radius` AT
+        ANY TIME of the horizon (their pc is the largest per-step mass); a target whose leaves disagree sampled as the mixture it is
+        (their pcMean averages Gaussian cells); and CONSTANT-TURN trackers (models/ct), which those three refuse -- here every particle
+        turns at its own rate, Phi(dt, w) of the real model.  Works for models/pv, models/ca and models/ct.  Times count from the
+        current scan.
+
+        horizon, radius, ownShip, courseChanges, turnRate, speedFactors, delay, steps   as for getHypothesisEncounters; at most 64
+                       candidates
+        particles, seed   particles per target (a multiple of 64 in 64 .. 2^20) and the seed: one seed, one result, bit for bit
+        hypotheses     True: every leaf of leafBatch() with the weight exp(-(cnllr - the target's smallest cnllr)) inside its target (a
+                       leaf without a cnllr, or with +inf: weight 0).  False: the selected leaf of every target alone, by
+                       getHypothesisEncounters' selection rule (a target without one is left out)
+        weights        None, or [L]: replaces those weights, e.g. getGlobalHypotheses()['leafProbability'] -- through it the exclusion
+                       constraints between targets reach an encounter figure.  A NaN in it raises ValueError and names the target
+        The entries are leafBatch()'s leaves at the current scan, the forest's OWN states: nothing is re-filtered.  For an AIS-aided
+        tracker they are the AIS-updated float64 ones.  The own ship is a path without a covariance; targets are independent of each
+        other and pairs of targets are not scored.
+        Returns evaluation.mc_encounters' dict -- within, ever, valid, status, pc, pcMax, tpc, pEver, sePcMax, sePEver, targets, first,
+        cdf, order -- plus `ids` (the id of every target of the result, in its order), `leafIds` (the target id of every leaf used),
+        `candidates` [G, 3], and per candidate `pEverMax` with `pEverMaxTarget` (the largest pEver over the targets and its index into
+        the result's targets; NaN and -1 without a figure) and `best`: the candidate with the smallest pEverMax, among equal ones the
+        LOWEST INDEX (evaluation.trial_best with every dcpa equal: a Monte-Carlo run has no dcpa to break a tie with); None if no
+        candidate has a figure.  No live track: empty arrays, no device call."""
+        from . import evaluation
+        name = "getMonteCarloEncounters"
+        for what, v in (("horizon", horizon), ("radius", radius)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+                raise ValueError("%s: %s must be a finite positive number (got %r)" % (name, what, v))
+        if isinstance(delay, bool) or not isinstance(delay, (int, float, np.integer, np.floating)) or not np.isfinite(delay) or delay < 0:
+            raise ValueError("%s: delay must be a finite number >= 0 (got %r)" % (name, delay))
+        if steps is None:
+            steps = min(int(np.ceil(float(horizon) / float(self.radarPeriod))), evaluation.ENCOUNTER_MAX_STEPS)
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= evaluation.ENCOUNTER_MAX_STEPS:
+            raise ValueError("%s: steps is an integer in 1 .. %d (got %r)" % (name, evaluation.ENCOUNTER_MAX_STEPS, steps))
+        steps = int(steps)
+        dt = float(horizon) / steps
+        model = self._model_mod
+        ct = getattr(model, "transition", None) == "ct"
+        if ct:
+            nx = 6
+            widen = lambda m: np.ascontiguousarray(np.asarray(m, dtype=np.float32).astype(np.float64).reshape(nx, nx))
+            Phi, Q = widen(model.Phi(dt, 0.0)), widen(model.Q(dt))      # (Phi is not read: every particle has its own)
+        else:
+            nx, Phi, Q = evaluation.encounter_model(model, dt)
+        own = np.asarray(ownShip, dtype=np.float64).reshape(-1)
+        if len(own) != 4 or not np.isfinite(own).all():
+            raise ValueError("%s: ownShip is a finite [x, y, vx, vy] (got %r)" % (name, ownShip))
+        dpsi, fs = np.asarray(courseChanges, dtype=np.float64).reshape(-1), np.asarray(speedFactors, dtype=np.float64).reshape(-1)
+        if len(dpsi) == 0 or len(fs) == 0:
+            raise ValueError("%s: courseChanges and speedFactors need one value at least" % name)
+        if turnRate is None:
+            if np.any(dpsi != 0):
+                raise ValueError("%s: turnRate is required with a course change that is not 0" % name)
+            turnRate = 1.0      # (no candidate turns: the rate enters no figure)
+        try:
+            cand = evaluation.trial_candidates([(a, f, float(delay)) for a in dpsi for f in fs])
+            if len(cand) > evaluation.MC_MAX_PATHS or np.isnan(cand).any():
+                raise ValueError("at most %d candidates, none of them NaN (got %d)" % (evaluation.MC_MAX_PATHS, len(cand)))
+            paths = evaluation.mc_own_paths(own, cand, turnRate, steps, dt)
+        except ValueError as exc:
+            raise ValueError("%s: %s" % (name, exc))
+        nodes = list(self.__trackNodes__)
+        ids = [int(i) for i in self._tbl_["id"]]
+        if nodes:
+            snap = self.leafBatch()
+            x, P, tg, leaf_ids = snap["x"], np.asarray(snap["P"], dtype=np.float64), np.asarray(snap["target"]), snap["ID"].astype(np.int64)
+            if weights is not None:
+                w = np.asarray(weights, dtype=np.float64)
+                if w.shape != (len(x),):
+                    raise ValueError("%s: weights is an [L] = [%d] array, one per leaf of leafBatch() (got shape %r)" % (name, len(x), w.shape))
+                if np.isnan(w).any():
+                    t = int(tg[np.flatnonzero(np.isnan(w))[0]])
+                    raise ValueError("%s: a weight of target %d (id %s) is NaN" % (name, t, ids[t] if t < len(ids) else "?"))
+            else:
+                cn = np.asarray(snap["cnllr"], dtype=np.float64)
+                w = np.zeros(len(x))
+                for t in np.unique(tg):
+                    at = np.flatnonzero(tg == t)
+                    if not np.isnan(cn[at]).all():
+                        with np.errstate(all="ignore"):
+                            w[at] = np.where(np.isnan(cn[at]), 0.0, np.exp(-(cn[at] - np.nanmin(cn[at]))))
+            if not hypotheses:
+                sel = self._selected_leaves(snap, nodes)
+                sel = sel[sel >= 0]
+                x, P, tg, leaf_ids, w = x[sel], P[sel], tg[sel], leaf_ids[sel], np.ones(len(sel))
+        else:
+            x, P, tg, leaf_ids, w = np.zeros((0, nx)), np.zeros((0, nx, nx)), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0)
+        try:
+            out = evaluation.mc_encounters(x, P, tg, w, Phi, Q, steps, dt, float(radius), paths, particles=particles, seed=seed,
+                                           transition="ct" if ct else "linear", ctx=self._ctx)
+        except ValueError as exc:
+            raise ValueError("%s: %s" % (name, exc))
+        out["ids"] = [ids[t] if t < len(ids) else -1 for t in out["targets"]]
+        out["leafIds"], out["candidates"] = leaf_ids, cand
+        G = len(cand)
+        val, arg = np.full(G, np.nan), np.full(G, -1, dtype=np.int64)
+        for g in range(G):
+            row = out["pEver"][g]
+            if len(row) and not np.isnan(row).all():
+                val[g] = np.nanmax(row)
+                arg[g] = int(np.flatnonzero(row == val[g])[0])
+        out["pEverMax"], out["pEverMaxTarget"] = val, arg
+        out["best"] = evaluation.trial_best(val, np.zeros(G))
         return out
 
     def leafRows(self):
@@ -1540,15 +1657,7 @@ class Tracker():
             rows[born[np.minimum(tg, T - 1)] & (tg < T)] = -1
         out = evaluation.k_best_hypotheses(snap["cnllr"], snap["target"], rows, k, nodeLimit, ctx=self._ctx)
         out["rows"] = rows
-        sel = np.full(T, -1, dtype=np.int64)
-        for t, nd in enumerate(nodes):
-            own_leaves = snap["target"] == t
-            if nd._node < 0:      # (born after the last scan: the track node is the root itself, the target's only leaf)
-                hit = np.flatnonzero(own_leaves) if own_leaves.sum() == 1 else ()
-            else:
-                hit = np.flatnonzero(own_leaves & (snap["node"] == nd._node))
-            if len(hit):
-                sel[t] = hit[0]
+        sel = self._selected_leaves(snap, nodes)
         rank = np.full(len(out["clusters"]), -1, dtype=np.int64)
         for c, tg in enumerate(out["clusters"]):
             tg = tg[tg < T]
