@@ -6,7 +6,8 @@
 
 namespace mht {
 
-// wave64 sum; fixed summation order -> deterministic.  Result is valid in every lane.
+// wave64 sum; fixed summation order -> deterministic.  Result is valid in every lane.  The order is the balanced pairwise tree over the
+// lanes -- six rounds of x = x[0::2] + x[1::2], lane 63's path never meets a zero fill -- and tests/test_devprobe_gpu.py holds it to that bit for bit.
 template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_f64(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);

@@ -283,8 +283,11 @@ def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None
     identity_start = em is not None and em[1] == "reference"
     lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx, identity_start)
     dev = ctx.device
-    xs_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
-    Ps_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev) if covariances else None
+    # (the smoothers leave the rows behind a track's end as they were, the filters write NaN there: handed on as they lie, the arrays
+    # start as NaN, so that both read the same and nothing of an earlier allocation shows through)
+    alloc = (lambda shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)) if on_device else (lambda shape: torch.empty(shape, dtype=torch.float64, device=dev))
+    xs_d = alloc((L_max, nx, n))
+    Ps_d = alloc((L_max, ns, n)) if covariances else None
     lib, extra, trace = ctx.lib, (), ()
     if ais is not None:
         extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
