@@ -916,7 +916,9 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
                 }
             } else if (wave == FG_THREADS / 64 - 1 && first_emit && d.uf_epoch) {
                 // no edge list: the target joins the device-wide union-find.  Its nodes' owner words are exchanged here, next to the
-                // counts (the answers are back before wavefront 0 is through its prefix); the links go out next to the emission
+                // counts, in ONE round over all chunks of the bitset unless a lane holds more than four nodes (1.4 us; wavefront 0 is through its
+                // prefix after 1.1 us and waits at the barrier below.  Collecting the answers BEHIND the barrier, next to the emission, was built
+                // and measured below this: profiles/claim_split.txt, section 7); the links go out next to the emission
                 // (overlapping launch: the compacted index is not known yet -- hooked under the SLOT, which is the index unless a target died in
                 // the previous scan; the end of the workgroup redoes it in that case)
                 const int pos = ovl ? t : (d.fused ? (s_red[0] + s_red[1] + s_red[2] + s_red[3]) : t);
@@ -945,8 +947,9 @@ __device__ __forceinline__ void target_part(KArgs ap0, const FDyn& d0, int t, un
             if (first_emit) {
                 base = s_base;
                 fin_tot = two_pass ? total : s_total;
-                // the target's entries of the child tables go out behind the barrier: in front of it the barrier's release waited for
-                // the acknowledgement of these global stores (~1 us on the workgroup's critical path)
+                // the target's entries of the child tables go out behind the barrier: when they moved here that took ~1 us off the
+                // workgroup's critical path.  (Why is not known: with this toolchain the barrier is s_waitcnt lgkmcnt(0) + s_barrier and
+                // does not wait for vector memory, profiles/claim_split.txt -- not, as this comment used to say, for the stores' acknowledgement.)
                 if (tid == 0) {
                     const int tot = fin_tot;
                     atomicAdd(&a.status->n_children, tot);

@@ -27,38 +27,42 @@ __device__ __forceinline__ void uf_link(unsigned long long* parent, unsigned epo
 }
 // One wavefront, target `pos`: every measurement node of the association set (LDS bitset tb, AW words) exchanges its owner word; the
 // targets found there go to an LDS list (conf[0 .. cap), *nconf of them; beyond cap they are linked straight away).
+// A lane owns the words lane, lane + 64, ... of the bitset and walks them as ONE sequence of nodes: a round sends up to four exchanges per
+// lane counted over all its words together, so one round trip serves every 64-word chunk of the bitset unless a lane holds more than four
+// nodes (a target has a few dozen nodes over 64 lanes; the headline's bitset is 144 words, a round per chunk was up to three dependent
+// round trips -- profiles/claim_split.txt).
 __device__ __forceinline__ void uf_claim(unsigned long long* owner, unsigned long long* parent, unsigned epoch, int pos, const unsigned long long* tb, int AW, int lane,
                                          int* conf, int cap, int* nconf) {
     const unsigned long long mine = ((unsigned long long)epoch << 32) | (unsigned)pos;
     int n = 0;      // (wave-uniform)
-    for (int w0 = 0; w0 < AW; w0 += 64) {
-        const int w = w0 + lane;
-        unsigned long long bits = (w < AW) ? tb[w] : 0ull;
-        while (__any(bits != 0ull)) {
-            // up to four nodes per lane and round: the atomics go out together, their answers are looked at afterwards
-            unsigned long long old[4];
-            bool has[4];
+    // the lane's place in its words: the nodes of word w not sent yet (bits == 0 behind a skip: none left); its words behind w have not been read
+    int w = lane;
+    unsigned long long bits = (lane < AW) ? tb[lane] : 0ull;
+    auto skip = [&]() { while (bits == 0ull && w + 64 < AW) { w += 64; bits = tb[w]; } };
+    skip();
+    while (__any(bits != 0ull)) {
+        // up to four nodes per lane and round: the atomics go out together, their answers are looked at afterwards
+        unsigned long long old[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                has[q] = bits != 0ull;
-                old[q] = 0ull;
-                if (has[q]) {
-                    const int b = __ffsll((long long)bits) - 1;
-                    bits &= bits - 1;
-                    old[q] = atomicMax(&owner[w * 64 + b], mine);
-                }
+        for (int q = 0; q < 4; ++q) {
+            old[q] = mine;      // (nothing sent: the target's own word, which is no conflict)
+            if (bits != 0ull) {
+                const int b = __ffsll((long long)bits) - 1;
+                bits &= bits - 1;
+                old[q] = atomicMax(&owner[w * 64 + b], mine);
             }
+            skip();
+        }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const bool cf = has[q] && (unsigned)(old[q] >> 32) == epoch && (int)(unsigned)old[q] != pos;
-                const unsigned long long bal = __ballot(cf);
-                if (cf) {
-                    const int i = n + __popcll(bal & ((1ull << lane) - 1ull));
-                    if (i < cap) conf[i] = (int)(unsigned)old[q];
-                    else uf_link(parent, epoch, pos, (int)(unsigned)old[q]);
-                }
-                n += __popcll(bal);
+        for (int q = 0; q < 4; ++q) {
+            const bool cf = (unsigned)(old[q] >> 32) == epoch && (int)(unsigned)old[q] != pos;
+            const unsigned long long bal = __ballot(cf);
+            if (cf) {
+                const int i = n + __popcll(bal & ((1ull << lane) - 1ull));
+                if (i < cap) conf[i] = (int)(unsigned)old[q];
+                else uf_link(parent, epoch, pos, (int)(unsigned)old[q]);
             }
+            n += __popcll(bal);
         }
     }
     if (lane == 0) *nconf = n < cap ? n : cap;
