@@ -645,7 +645,8 @@ int mht_trial_hypotheses(mht_ctx* ctx, int32_t nx, int32_t L, int32_t T, int32_t
  * slabs), no atomic.  Synchronises.
  * MHT_E_INVALID: a null pointer (Phi may be null with transition 1), arguments out of range, a Phi or Q that is not finite, a Q that is
  * not positive semidefinite, a short work buffer, a `first` that does not ascend strictly from 0 to nComp; nothing has then been
- * launched or written.  Out of scope: pairs of targets, an own-ship covariance, correlation between targets.  Exported by both builds. */
+ * launched or written.  Pairs of targets: mht_mc_pair_encounters below.  Out of scope: an own-ship covariance, correlation between
+ * targets, the time of the first violation (firstAt, which the pair engine has).  Exported by both builds. */
 #define MHT_MC_MAX_PATHS 64            /* own paths per call */
 #define MHT_MC_MAX_STEPS 64            /* steps of the horizon */
 #define MHT_MC_MAX_PARTICLES 1048576   /* particles per target, 2^20 */
@@ -658,6 +659,35 @@ int mht_mc_encounters(mht_ctx* ctx, int32_t nx, int32_t transition, int32_t nCom
                       uint64_t seed, double dt, double radius, const double* Phi, const double* Q, const double* x, const double* P,
                       const int32_t* first, const double* cdf, const double* ownPath, uint32_t* within, uint32_t* ever, uint32_t* valid,
                       int32_t* status, void* work, size_t work_bytes);
+
+/* mht_mc_pair_encounters: Monte-Carlo encounters between PAIRS OF TARGETS -- target against target, what a VTS operator or a fleet
+ * monitor asks for -- with the engine of mht_mc_encounters: particle p of target a is held against particle p of target b, both drawn
+ * from their target's mixture and walked exactly as mht_mc_encounters walks them (the same Philox stream keyed by (seed, target), the
+ * same sums, the constant-turn model included; csrc/mht_mc_pair.h states the definition).  Per pair j = (a, b), with d_k the difference
+ * of the two positions at step k:
+ *   nx, transition, nComp, nTarget, steps, particles, seed, dt, radius, Phi, Q, x, P, first, cdf   as for mht_mc_encounters
+ *   nPair            1 .. MHT_MC_MAX_PAIRS
+ *   pairs            dev [nPair][2] int32: the two target indices of every pair, 0 <= a, b < nTarget and a != b.  Duplicates and both
+ *                    orders of a pair are allowed (and give equal counts).  Read back and checked before anything is launched
+ *   within           dev [steps + 1][nPair] uint32 out: the particles with |d_k| < R at step k
+ *   firstAt          dev [steps + 1][nPair] uint32 out: the particles whose relative path comes inside R FIRST at step k (at the step, or
+ *                    on the segment that ends in it): the distribution of the time to the first violation; its sum over k is ever
+ *   ever             dev [nPair] uint32 out: the particles whose piecewise-linear relative path comes inside R; ever >= within at every step
+ *   valid            dev [nPair] uint32 out: `particles` for a scored pair, else 0 -- the divisor of the counts
+ *   status           dev [nPair] int32 out: MHT_MC_OK; MHT_MC_NAN: either target has a NaN in a component's x, P or cdf; MHT_MC_NOT_PSD:
+ *                    either target has a component whose P is not positive semidefinite (NAN wins).  Every count of such a pair is 0
+ *   work             dev, at least mht_mc_pair_work_bytes(nx, nComp, nTarget, nPair, steps, particles) bytes (0 for arguments out of range)
+ * No particle position is stored: a target in many pairs is walked once per pair.  Three launches (a component per lane: the factors; a
+ * workgroup per slab of a pair's particle indices, a pair of particles per lane; the fold of the slabs), no atomic.  Synchronises.
+ * MHT_E_INVALID: as for mht_mc_encounters, and an nPair out of range or a pair that names a target outside 0 .. nTarget - 1 or one
+ * target twice; nothing has then been launched or written.  Out of scope: correlation between targets (two targets' particles are
+ * independent), pairs across mht_trial_hypotheses' Gaussian cells.  Exported by both builds. */
+#define MHT_MC_MAX_PAIRS 1048576       /* pairs per call, 2^20 */
+size_t mht_mc_pair_work_bytes(int32_t nx, int32_t nComp, int32_t nTarget, int32_t nPair, int32_t steps, int32_t particles);
+int mht_mc_pair_encounters(mht_ctx* ctx, int32_t nx, int32_t transition, int32_t nComp, int32_t nTarget, int32_t nPair, int32_t steps,
+                           int32_t particles, uint64_t seed, double dt, double radius, const double* Phi, const double* Q, const double* x,
+                           const double* P, const int32_t* first, const double* cdf, const int32_t* pairs, uint32_t* within,
+                           uint32_t* firstAt, uint32_t* ever, uint32_t* valid, int32_t* status, void* work, size_t work_bytes);
 
 /* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
  * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);

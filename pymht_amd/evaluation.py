@@ -897,6 +897,52 @@ def mc_standard_error(p, valid):
         return np.where(S > 0, np.sqrt(np.fmax(p * (1.0 - p), 1.0 / S) / S), np.nan)
 
 
+def _mc_arguments(who, x, P, target, weight, Phi, Q, steps, dt, radius, particles, seed, transition):
+    """What `mc_encounters` and `mc_pair_encounters` share: every check of the model, the sizes and the seed (ValueError under the
+    caller's name `who`), the components grouped by target with a STABLE sort, and the cdf of the weights inside every target.  A dict:
+    x, P, Phi, Q (float64 arrays), nx, L, steps, S, order [L], targets [T], first [T + 1] (int32), cdf [L], T."""
+    X, Pm = np.asarray(x, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    Phi, Q = np.asarray(Phi, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    nx = X.shape[1] if X.ndim == 2 else -1
+    if nx not in (4, 6):
+        raise ValueError("%s: the states are an [L, 4] or [L, 6] array (got shape %r)" % (who, X.shape))
+    L = len(X)
+    if transition not in ("linear", "ct") or (transition == "ct" and nx != 6):
+        raise ValueError("%s: transition is \"linear\" or, with six states, \"ct\" (got %r with %d states)" % (who, transition, nx))
+    if Pm.shape != (L, nx, nx) or Phi.shape != (nx, nx) or Q.shape != (nx, nx):
+        raise ValueError("%s: P, Phi and Q have shapes %r, %r and %r; [%d, %d, %d] and twice [%d, %d] are wanted"
+                         % (who, Pm.shape, Phi.shape, Q.shape, L, nx, nx, nx, nx))
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= MC_MAX_STEPS:
+        raise ValueError("%s: steps is an integer in 1 .. %d (got %r)" % (who, MC_MAX_STEPS, steps))
+    for name, v in (("dt", dt), ("radius", radius)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+            raise ValueError("%s: %s must be a finite positive number (got %r)" % (who, name, v))
+    if isinstance(particles, bool) or not isinstance(particles, (int, np.integer)) or not MC_WARP <= particles <= MC_MAX_PARTICLES or particles % MC_WARP:
+        raise ValueError("%s: particles is a multiple of %d in %d .. %d (got %r)" % (who, MC_WARP, MC_WARP, MC_MAX_PARTICLES, particles))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
+        raise ValueError("%s: seed is an integer in 0 .. 2^64 - 1 (got %r)" % (who, seed))
+    if not (np.isfinite(Q).all() and (transition == "ct" or np.isfinite(Phi).all())):
+        raise ValueError("%s: Phi and Q must be finite" % who)
+    tg, wt = np.asarray(target), np.asarray(weight, dtype=np.float64)
+    if tg.shape != (L,) or not np.issubdtype(tg.dtype, np.integer):
+        raise ValueError("%s: target is an [L] = [%d] array of integers (got %r)" % (who, L, target))
+    if wt.shape != (L,) or (wt < 0).any():
+        raise ValueError("%s: weight is an [L] = [%d] array of numbers >= 0 (got %r)" % (who, L, weight))
+    order = np.argsort(tg, kind="stable")
+    targets, start = np.unique(tg[order], return_index=True)
+    T = len(targets)
+    first = np.append(start, L).astype(np.int32)
+    cdf = np.zeros(L)
+    for t in range(T):
+        w = wt[order[first[t]:first[t + 1]]]
+        total = w.sum()
+        if not np.isfinite(total) or not total > 0:
+            raise ValueError("%s: the weights of target %d are all 0 or not finite" % (who, int(targets[t])))
+        cdf[first[t]:first[t + 1]] = np.cumsum(w / total)
+        cdf[first[t + 1] - 1] = 1.0
+    return dict(x=X, P=Pm, Phi=Phi, Q=Q, nx=nx, L=L, steps=int(steps), S=int(particles), order=order, targets=targets, first=first, cdf=cdf, T=T)
+
+
 def mc_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, ownPaths, particles=4096, seed=0, transition="linear", device=0, ctx=None):
     """Encounters by MONTE CARLO: every target is the Gaussian mixture of its components, `particles` particles per target are drawn from
     it, walked over steps * dt seconds WITH the model's process noise, and held against G paths of the own ship
@@ -922,54 +968,19 @@ def mc_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, ownPaths, par
     host, NaN where valid is 0: `pc` = within / valid; `pcMax` [G, T] and `tpc`, the largest pc over the steps and the time k dt of the
     EARLIEST largest; `pEver` = ever / valid; `sePcMax` and `sePEver`, sqrt(max(p (1 - p), 1 / S) / S) -- a Monte-Carlo figure is not
     to be read without its error bar.  And `targets` [T], `first` [T + 1], `cdf` [L] and `order` [L] as they were used.
-    Out of scope: pairs of targets, an own-ship covariance, correlation between targets, more than 2^20 particles.
+    Pairs of targets: `mc_pair_encounters`.  Out of scope: an own-ship covariance, correlation between targets, the time of the first
+    violation (`firstAt`, which the pair engine has), more than 2^20 particles.
     One upload, one call of `mht_mc_encounters` (three launches), no host fallback."""
-    X, Pm = np.asarray(x, dtype=np.float64), np.asarray(P, dtype=np.float64)
-    Phi, Q = np.asarray(Phi, dtype=np.float64), np.asarray(Q, dtype=np.float64)
-    nx = X.shape[1] if X.ndim == 2 else -1
-    if nx not in (4, 6):
-        raise ValueError("mc_encounters: the states are an [L, 4] or [L, 6] array (got shape %r)" % (X.shape,))
-    L = len(X)
-    if transition not in ("linear", "ct") or (transition == "ct" and nx != 6):
-        raise ValueError("mc_encounters: transition is \"linear\" or, with six states, \"ct\" (got %r with %d states)" % (transition, nx))
-    if Pm.shape != (L, nx, nx) or Phi.shape != (nx, nx) or Q.shape != (nx, nx):
-        raise ValueError("mc_encounters: P, Phi and Q have shapes %r, %r and %r; [%d, %d, %d] and twice [%d, %d] are wanted"
-                         % (Pm.shape, Phi.shape, Q.shape, L, nx, nx, nx, nx))
-    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= MC_MAX_STEPS:
-        raise ValueError("mc_encounters: steps is an integer in 1 .. %d (got %r)" % (MC_MAX_STEPS, steps))
-    for name, v in (("dt", dt), ("radius", radius)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
-            raise ValueError("mc_encounters: %s must be a finite positive number (got %r)" % (name, v))
-    if isinstance(particles, bool) or not isinstance(particles, (int, np.integer)) or not MC_WARP <= particles <= MC_MAX_PARTICLES or particles % MC_WARP:
-        raise ValueError("mc_encounters: particles is a multiple of %d in %d .. %d (got %r)" % (MC_WARP, MC_WARP, MC_MAX_PARTICLES, particles))
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
-        raise ValueError("mc_encounters: seed is an integer in 0 .. 2^64 - 1 (got %r)" % (seed,))
-    if not (np.isfinite(Q).all() and (transition == "ct" or np.isfinite(Phi).all())):
-        raise ValueError("mc_encounters: Phi and Q must be finite")
-    steps, S = int(steps), int(particles)
+    a = _mc_arguments("mc_encounters", x, P, target, weight, Phi, Q, steps, dt, radius, particles, seed, transition)
+    X, Pm, Phi, Q, nx, L, steps, S = a["x"], a["P"], a["Phi"], a["Q"], a["nx"], a["L"], a["steps"], a["S"]
+    order, targets, first, cdf, T = a["order"], a["targets"], a["first"], a["cdf"], a["T"]
     try:
         own = np.ascontiguousarray(ownPaths, dtype=np.float64)
     except (TypeError, ValueError):
         own = np.zeros(0)
     if own.ndim != 3 or own.shape[1:] != (steps + 1, 2) or not 1 <= len(own) <= MC_MAX_PATHS or not np.isfinite(own).all():
         raise ValueError("mc_encounters: ownPaths is a finite [G, steps + 1, 2] = [G, %d, 2] array, G in 1 .. %d (got shape %r)" % (steps + 1, MC_MAX_PATHS, own.shape))
-    tg, wt = np.asarray(target), np.asarray(weight, dtype=np.float64)
-    if tg.shape != (L,) or not np.issubdtype(tg.dtype, np.integer):
-        raise ValueError("mc_encounters: target is an [L] = [%d] array of integers (got %r)" % (L, target))
-    if wt.shape != (L,) or (wt < 0).any():
-        raise ValueError("mc_encounters: weight is an [L] = [%d] array of numbers >= 0 (got %r)" % (L, weight))
-    order = np.argsort(tg, kind="stable")
-    targets, start = np.unique(tg[order], return_index=True)
-    T, G = len(targets), len(own)
-    first = np.append(start, L).astype(np.int32)
-    cdf = np.zeros(L)
-    for t in range(T):
-        w = wt[order[first[t]:first[t + 1]]]
-        total = w.sum()
-        if not np.isfinite(total) or not total > 0:
-            raise ValueError("mc_encounters: the weights of target %d are all 0 or not finite" % int(targets[t]))
-        cdf[first[t]:first[t + 1]] = np.cumsum(w / total)
-        cdf[first[t + 1] - 1] = 1.0
+    G = len(own)
     res = dict(targets=targets.astype(np.int64), first=first, cdf=cdf, order=order.astype(np.int64))
     if L == 0:
         res.update(within=np.zeros((G, steps + 1, 0), dtype=np.uint32), ever=np.zeros((G, 0), dtype=np.uint32), valid=np.zeros(0, dtype=np.uint32),
@@ -1016,6 +1027,152 @@ def mc_derive(within, ever, valid, dt):
         pc_max = np.where(scored, np.take_along_axis(pc, arg[:, None, :], axis=1)[:, 0, :], np.nan)
         tpc = np.where(scored, arg * dt, np.nan)
     return dict(pc=pc, pcMax=pc_max, tpc=tpc, pEver=p_ever, sePcMax=mc_standard_error(pc_max, v), sePEver=mc_standard_error(p_ever, v))
+
+
+# ---- encounters by Monte Carlo between pairs of targets ---------------------------------------------------------------------------------
+MC_MAX_PAIRS = 1 << 20      # MHT_MC_MAX_PAIRS, include/mht_amd.h
+MC_PAIR_COUNT_NAMES = ("within", "firstAt", "ever", "valid", "status")
+
+
+def mc_pair_derive(within, firstAt, ever, valid, dt):
+    """The host's figures of `mc_pair_encounters` from its counts (within, firstAt [K + 1, n]; ever, valid [n]): pc, pcMax, tpc, pEver,
+    sePcMax, sePEver by `mc_derive`'s rules, and pEverBy [K + 1, n] = cumsum(firstAt) / valid.  NaN where valid is 0."""
+    d = mc_derive(np.asarray(within)[None], np.asarray(ever)[None], valid, dt)
+    out = {k: v[0] for k, v in d.items()}
+    v = np.asarray(valid, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        out["pEverBy"] = np.where(v > 0, np.cumsum(np.asarray(firstAt, dtype=np.int64), axis=0) / v, np.nan)
+    return out
+
+
+def mc_pair_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, pairs, particles=4096, seed=0, transition="linear", device=0, ctx=None):
+    """Encounters by MONTE CARLO between PAIRS OF TARGETS: what a VTS operator or a fleet monitor asks for, with the engine of
+    `mc_encounters` (csrc/mht_mc_pair.h states the definition).  Every target is the Gaussian mixture of its components; particle p of
+    target a is held against particle p of target b, both walked over steps * dt seconds with the model's process noise -- exactly the
+    particles `mc_encounters` walks for the same seed, the constant-turn model with Phi(dt, w) at every particle's own turn rate
+    included.  With d_k the difference of the two positions at step k, a pair's relative path is the piecewise-linear one through
+    d_0 .. d_K.
+
+    x, P, target, weight, Phi, Q, steps, dt, radius, particles, seed, transition   as for `mc_encounters`
+    pairs      [n, 2] integers, n <= 2^20: pairs of target VALUES, as they appear in `target`.  Duplicates and both orders of a pair
+               are allowed (and give equal counts).  A pair that names a target not present, or one target twice, raises ValueError
+    ValueError for arguments that do not fit -- before any device is needed.  No pair or no component: empty arrays, no device call.
+    Returns a dict.  As the device wrote them: `within` [steps + 1, n] (the particles within `radius` at step k), `firstAt`
+    [steps + 1, n] (the particles whose relative path comes inside `radius` FIRST at step k -- at the step or on the segment that ends
+    in it: the distribution of the time to the first violation), `ever` [n] = the sum of firstAt over the steps, `valid` [n] (S for a
+    scored pair, else 0) and `status` [n] (0; 1: either target has a NaN in a component; 2: either target has a P that is not positive
+    semidefinite).  Derived on the host, NaN where valid is 0: `pc`, `pcMax`, `tpc`, `pEver`, `sePcMax`, `sePEver` by `mc_derive`'s
+    rules, and `pEverBy` [steps + 1, n] = cumsum(firstAt) / valid, the probability of having come within `radius` by the time k dt
+    (its last row is pEver).  And `pairs` [n, 2] as given, `targets` [T], `first` [T + 1], `cdf` [L] and `order` [L] as they were used.
+    Out of scope: correlation between targets (the particles of two targets are independent), an own-ship covariance, pairs across
+    `trial_hypotheses`' Gaussian cells, and `firstAt` for the own-ship engine `mc_encounters`.
+    One upload, one call of `mht_mc_pair_encounters` (three launches), no host fallback; no particle position is stored, a target in
+    many pairs is walked once per pair."""
+    who = "mc_pair_encounters"
+    a = _mc_arguments(who, x, P, target, weight, Phi, Q, steps, dt, radius, particles, seed, transition)
+    X, Pm, Phi, Q, nx, L, steps, S = a["x"], a["P"], a["Phi"], a["Q"], a["nx"], a["L"], a["steps"], a["S"]
+    order, targets, first, cdf, T = a["order"], a["targets"], a["first"], a["cdf"], a["T"]
+    try:
+        pr = np.asarray(pairs)
+    except (TypeError, ValueError):
+        pr = np.zeros(0)
+    if pr.size == 0:
+        pr = np.zeros((0, 2), dtype=np.int64)
+    if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer) or len(pr) > MC_MAX_PAIRS:
+        raise ValueError("%s: pairs is an [n, 2] array of integers, n <= %d (got %r)" % (who, MC_MAX_PAIRS, getattr(pr, "shape", pairs)))
+    pr = pr.astype(np.int64)
+    n = len(pr)
+    rank = np.searchsorted(targets, pr) if T else np.zeros_like(pr)
+    there = (targets[np.minimum(rank, T - 1)] == pr) if T else np.zeros(pr.shape, dtype=bool)
+    if not there.all():
+        j = int(np.flatnonzero(~there.all(axis=1))[0])
+        raise ValueError("%s: pair %d is (%d, %d), and target %d has no component" % (who, j, pr[j, 0], pr[j, 1], pr[j][~there[j]][0]))
+    if n and (pr[:, 0] == pr[:, 1]).any():
+        j = int(np.flatnonzero(pr[:, 0] == pr[:, 1])[0])
+        raise ValueError("%s: pair %d names target %d twice" % (who, j, pr[j, 0]))
+    res = dict(pairs=pr, targets=targets.astype(np.int64), first=first, cdf=cdf, order=order.astype(np.int64))
+    if L == 0 or n == 0:
+        res.update(within=np.zeros((steps + 1, 0), dtype=np.uint32), firstAt=np.zeros((steps + 1, 0), dtype=np.uint32), ever=np.zeros(0, dtype=np.uint32),
+                   valid=np.zeros(0, dtype=np.uint32), status=np.zeros(0, dtype=np.int32))
+    else:
+        iu = np.triu_indices(nx)
+        xp, Pp = np.ascontiguousarray(X[order].T), np.ascontiguousarray(Pm[order][:, iu[0], iu[1]].T)
+        Phi, Q = np.ascontiguousarray(Phi), np.ascontiguousarray(Q)
+        idx = np.ascontiguousarray(rank, dtype=np.int32)
+        mine = ctx is None
+        if mine:
+            ctx = Context(device, nx=nx)
+        try:
+            dev, lib = ctx.device, ctx.lib
+            x_d, P_d, f_d, c_d, p_d = [torch.from_numpy(v).to(dev) for v in (xp, Pp, first, cdf, idx)]
+            need = int(lib.mht_mc_pair_work_bytes(nx, L, T, n, steps, S))
+            work = torch.empty(need, dtype=torch.uint8, device=dev)
+            # (uint32 counts in int32 tensors: the same bits)
+            w_d, a_d = torch.empty((steps + 1, n), dtype=torch.int32, device=dev), torch.empty((steps + 1, n), dtype=torch.int32, device=dev)
+            e_d, v_d, s_d = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3)]
+            torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
+            _lib.check(lib.mht_mc_pair_encounters(ctx.handle, nx, 1 if transition == "ct" else 0, L, T, n, steps, S, int(seed), float(dt), float(radius),
+                                                  Phi.ctypes.data, Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(), f_d.data_ptr(), c_d.data_ptr(), p_d.data_ptr(),
+                                                  w_d.data_ptr(), a_d.data_ptr(), e_d.data_ptr(), v_d.data_ptr(), s_d.data_ptr(), work.data_ptr(), need), lib)
+            res.update(within=w_d.cpu().numpy().view(np.uint32), firstAt=a_d.cpu().numpy().view(np.uint32), ever=e_d.cpu().numpy().view(np.uint32),
+                       valid=v_d.cpu().numpy().view(np.uint32), status=s_d.cpu().numpy())
+        finally:
+            if mine:
+                ctx.close()
+    res.update(mc_pair_derive(res["within"], res["firstAt"], res["ever"], res["valid"], float(dt)))
+    return res
+
+
+def mc_pair_screen(x, target, weight, horizon, distance, block=256):
+    """Which pairs of targets are worth a Monte-Carlo run: A PRE-FILTER, NOT A FIGURE -- a pair it drops gets no result at all, so
+    choose `distance` generously (several safety radii plus the spread of the targets' hypotheses over the horizon).  Per target the
+    weight-normalised mean of x[:, :4] = [x, y, vx, vy] over its components; per pair the distance at the clamped closest point of
+    approach of the two STRAIGHT-LINE motions over [0, horizon]: with r and v the differences of the mean positions and velocities,
+    t* = clamp(-(r . v) / (v . v), 0, horizon) (0 for v = 0) and d = |r + t* v|.  For constant-turn targets the straight line is only
+    a guide: more generous still.  Host NumPy, a block of rows at a time (2 000 targets need no dense cube).
+
+    x [L, >= 4], target [L] integers, weight [L] >= 0; horizon >= 0 and distance > 0, finite.
+    Returns the pairs with d < distance as [n, 2] int64 target VALUES, a < b, ascending.  A target whose mean is NaN (a NaN component of
+    positive weight, or weights that are all 0) is in no pair."""
+    who = "mc_pair_screen"
+    X, tg, wt = np.asarray(x, dtype=np.float64), np.asarray(target), np.asarray(weight, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] < 4:
+        raise ValueError("%s: the states are an [L, 4] array or wider (got shape %r)" % (who, X.shape))
+    L = len(X)
+    if tg.shape != (L,) or not np.issubdtype(tg.dtype, np.integer):
+        raise ValueError("%s: target is an [L] = [%d] array of integers (got %r)" % (who, L, target))
+    if wt.shape != (L,) or not (wt >= 0).all():
+        raise ValueError("%s: weight is an [L] = [%d] array of numbers >= 0 (got %r)" % (who, L, weight))
+    for name, v, low in (("horizon", horizon, True), ("distance", distance, False)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not (v >= 0 if low else v > 0):
+            raise ValueError("%s: %s must be a finite number %s 0 (got %r)" % (who, name, ">=" if low else ">", v))
+    targets, inv = np.unique(tg, return_inverse=True)
+    T = len(targets)
+    mean = np.zeros((T, 4))
+    total = np.zeros(T)
+    for i in range(4):
+        # (a component of weight 0 does not enter, whatever its state: 0 * NaN would)
+        np.add.at(mean[:, i], inv, np.where(wt > 0, wt * X[:, i], 0.0))
+    np.add.at(total, inv, wt)
+    with np.errstate(all="ignore"):
+        mean = mean / total[:, None]
+    ok = np.isfinite(mean).all(axis=1)
+    h, d2max = float(horizon), float(distance) * float(distance)
+    keep = []
+    for lo in range(0, T, int(block)):
+        hi = min(lo + int(block), T)
+        r = mean[lo:hi, None, :2] - mean[None, :, :2]
+        v = mean[lo:hi, None, 2:] - mean[None, :, 2:]
+        rv, vv = r[..., 0] * v[..., 0] + r[..., 1] * v[..., 1], v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]
+        with np.errstate(all="ignore"):
+            ts = np.where(vv > 0, np.fmin(np.fmax(-rv / np.where(vv > 0, vv, 1.0), 0.0), h), 0.0)
+            cx, cy = r[..., 0] + ts * v[..., 0], r[..., 1] + ts * v[..., 1]
+            near = cx * cx + cy * cy < d2max
+        near &= ok[lo:hi, None] & ok[None, :] & (np.arange(lo, hi)[:, None] < np.arange(T)[None, :])
+        a, b = np.nonzero(near)
+        keep.append(np.stack([targets[a + lo], targets[b]], axis=1))
+    out = np.concatenate(keep, axis=0) if keep else np.zeros((0, 2))
+    return np.ascontiguousarray(out, dtype=np.int64).reshape(-1, 2)
 
 
 # ---- the k best global hypotheses ---------------------------------------------------------------------------------------------------

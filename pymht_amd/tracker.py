@@ -1492,6 +1492,38 @@ class Tracker():
         out["bestWorstCase"] = evaluation.trial_best(out["pcWorstMax"], out["dcpaMinAll"])
         return out
 
+    def _mc_leaves(self, name, nx, hypotheses, weights):
+        """The leaves and weights of a Monte-Carlo call, gathered once for getMonteCarloEncounters and getMonteCarloPairEncounters:
+        leafBatch()'s leaves (the AIS-updated float64 ones of an AIS-aided tracker) with exp(-(cnllr - the target's smallest cnllr)) or
+        the caller's `weights`; hypotheses=False: the selected leaf of every target alone.  (x, P, target, leafIds, weight, ids)."""
+        nodes = list(self.__trackNodes__)
+        ids = [int(i) for i in self._tbl_["id"]]
+        if nodes:
+            snap = self.leafBatch()
+            x, P, tg, leaf_ids = snap["x"], np.asarray(snap["P"], dtype=np.float64), np.asarray(snap["target"]), snap["ID"].astype(np.int64)
+            if weights is not None:
+                w = np.asarray(weights, dtype=np.float64)
+                if w.shape != (len(x),):
+                    raise ValueError("%s: weights is an [L] = [%d] array, one per leaf of leafBatch() (got shape %r)" % (name, len(x), w.shape))
+                if np.isnan(w).any():
+                    t = int(tg[np.flatnonzero(np.isnan(w))[0]])
+                    raise ValueError("%s: a weight of target %d (id %s) is NaN" % (name, t, ids[t] if t < len(ids) else "?"))
+            else:
+                cn = np.asarray(snap["cnllr"], dtype=np.float64)
+                w = np.zeros(len(x))
+                for t in np.unique(tg):
+                    at = np.flatnonzero(tg == t)
+                    if not np.isnan(cn[at]).all():
+                        with np.errstate(all="ignore"):
+                            w[at] = np.where(np.isnan(cn[at]), 0.0, np.exp(-(cn[at] - np.nanmin(cn[at]))))
+            if not hypotheses:
+                sel = self._selected_leaves(snap, nodes)
+                sel = sel[sel >= 0]
+                x, P, tg, leaf_ids, w = x[sel], P[sel], tg[sel], leaf_ids[sel], np.ones(len(sel))
+        else:
+            x, P, tg, leaf_ids, w = np.zeros((0, nx)), np.zeros((0, nx, nx)), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0)
+        return x, P, tg, leaf_ids, w, ids
+
     def getMonteCarloEncounters(self, horizon, radius, ownShip, particles=4096, seed=0, courseChanges=(0.0,), turnRate=None, speedFactors=(1.0,), delay=0.0,
                                 steps=None, hypotheses=True, weights=None):
         """Encounters by MONTE CARLO (evaluation.mc_encounters defines the figures): particles drawn from the forest's own leaves -- a
@@ -1512,7 +1544,7 @@ class Tracker():
                        constraints between targets reach an encounter figure.  A NaN in it raises ValueError and names the target
         The entries are leafBatch()'s leaves at the current scan, the forest's OWN states: nothing is re-filtered.  For an AIS-aided
         tracker they are the AIS-updated float64 ones.  The own ship is a path without a covariance; targets are independent of each
-        other and pairs of targets are not scored.
+        other.  Pairs of targets: getMonteCarloPairEncounters.
         Returns evaluation.mc_encounters' dict -- within, ever, valid, status, pc, pcMax, tpc, pEver, sePcMax, sePEver, targets, first,
         cdf, order -- plus `ids` (the id of every target of the result, in its order), `leafIds` (the target id of every leaf used),
         `candidates` [G, 3], and per candidate `pEverMax` with `pEverMaxTarget` (the largest pEver over the targets and its index into
@@ -1557,32 +1589,7 @@ class Tracker():
             paths = evaluation.mc_own_paths(own, cand, turnRate, steps, dt)
         except ValueError as exc:
             raise ValueError("%s: %s" % (name, exc))
-        nodes = list(self.__trackNodes__)
-        ids = [int(i) for i in self._tbl_["id"]]
-        if nodes:
-            snap = self.leafBatch()
-            x, P, tg, leaf_ids = snap["x"], np.asarray(snap["P"], dtype=np.float64), np.asarray(snap["target"]), snap["ID"].astype(np.int64)
-            if weights is not None:
-                w = np.asarray(weights, dtype=np.float64)
-                if w.shape != (len(x),):
-                    raise ValueError("%s: weights is an [L] = [%d] array, one per leaf of leafBatch() (got shape %r)" % (name, len(x), w.shape))
-                if np.isnan(w).any():
-                    t = int(tg[np.flatnonzero(np.isnan(w))[0]])
-                    raise ValueError("%s: a weight of target %d (id %s) is NaN" % (name, t, ids[t] if t < len(ids) else "?"))
-            else:
-                cn = np.asarray(snap["cnllr"], dtype=np.float64)
-                w = np.zeros(len(x))
-                for t in np.unique(tg):
-                    at = np.flatnonzero(tg == t)
-                    if not np.isnan(cn[at]).all():
-                        with np.errstate(all="ignore"):
-                            w[at] = np.where(np.isnan(cn[at]), 0.0, np.exp(-(cn[at] - np.nanmin(cn[at]))))
-            if not hypotheses:
-                sel = self._selected_leaves(snap, nodes)
-                sel = sel[sel >= 0]
-                x, P, tg, leaf_ids, w = x[sel], P[sel], tg[sel], leaf_ids[sel], np.ones(len(sel))
-        else:
-            x, P, tg, leaf_ids, w = np.zeros((0, nx)), np.zeros((0, nx, nx)), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0)
+        x, P, tg, leaf_ids, w, ids = self._mc_leaves(name, nx, hypotheses, weights)
         try:
             out = evaluation.mc_encounters(x, P, tg, w, Phi, Q, steps, dt, float(radius), paths, particles=particles, seed=seed,
                                            transition="ct" if ct else "linear", ctx=self._ctx)
@@ -1599,6 +1606,76 @@ class Tracker():
                 arg[g] = int(np.flatnonzero(row == val[g])[0])
         out["pEverMax"], out["pEverMaxTarget"] = val, arg
         out["best"] = evaluation.trial_best(val, np.zeros(G))
+        return out
+
+    def getMonteCarloPairEncounters(self, horizon, radius, particles=4096, seed=0, steps=None, pairs=None, screen=None, hypotheses=True, weights=None):
+        """Encounters by MONTE CARLO between PAIRS OF TARGETS (evaluation.mc_pair_encounters defines the figures): target against target,
+        what a VTS operator or a fleet monitor asks for, with the engine of getMonteCarloEncounters -- particles drawn from the forest's
+        own leaves, a Gaussian mixture per target, walked with the model's process noise; particle p of one target is held against
+        particle p of the other.  Next to `pEver` it gives `firstAt` and `pEverBy`, the distribution of the time to the first violation.
+        getEncounters(ownShip=None) is the Gaussian rule for the same question: one re-filtered Gaussian per track, the largest per-step
+        mass, and no constant-turn tracker.  Works for models/pv, models/ca and models/ct.  Times count from the current scan.
+
+        horizon, radius, particles, seed, steps, hypotheses, weights   as for getMonteCarloEncounters
+        pairs          [n, 2] pairs of target INDICES (leafBatch()'s `target`, the order of getTrackNodes()), or None
+        screen         with pairs=None: the `distance` of evaluation.mc_pair_screen over `horizon` -- only pairs whose straight-line
+                       closest approach is below it are scored.  A PRE-FILTER: a pair it drops gets no result; choose it generously,
+                       more so for a constant-turn tracker
+        With pairs and screen both None all T (T - 1) / 2 pairs are taken, if that is at most evaluation.MC_MAX_PAIRS = 2^20; beyond it
+        ValueError asks for a screen.
+        Returns evaluation.mc_pair_encounters' dict -- within, firstAt, ever, valid, status, pc, pcMax, tpc, pEver, sePcMax, sePEver,
+        pEverBy, pairs, targets, first, cdf, order -- plus `ids` [n, 2] (the two target ids of every pair), `leafIds` (the target id of
+        every leaf used), `ranking` (the pair indices by descending pEver, ties by index, pairs that are not scored last) and `worst`
+        (ranking[0], or None without a pair).  Fewer than two live targets: empty arrays, no device call.
+        Out of scope: correlation between targets, the own ship's covariance (there is no own ship here), pairs across
+        getHypothesisEncounters' Gaussian cells, and firstAt for getMonteCarloEncounters."""
+        from . import evaluation
+        name = "getMonteCarloPairEncounters"
+        for what, v in (("horizon", horizon), ("radius", radius)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+                raise ValueError("%s: %s must be a finite positive number (got %r)" % (name, what, v))
+        if steps is None:
+            steps = min(int(np.ceil(float(horizon) / float(self.radarPeriod))), evaluation.ENCOUNTER_MAX_STEPS)
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= evaluation.ENCOUNTER_MAX_STEPS:
+            raise ValueError("%s: steps is an integer in 1 .. %d (got %r)" % (name, evaluation.ENCOUNTER_MAX_STEPS, steps))
+        steps = int(steps)
+        dt = float(horizon) / steps
+        model = self._model_mod
+        ct = getattr(model, "transition", None) == "ct"
+        if ct:
+            nx = 6
+            widen = lambda m: np.ascontiguousarray(np.asarray(m, dtype=np.float32).astype(np.float64).reshape(nx, nx))
+            Phi, Q = widen(model.Phi(dt, 0.0)), widen(model.Q(dt))      # (Phi is not read: every particle has its own)
+        else:
+            nx, Phi, Q = evaluation.encounter_model(model, dt)
+        x, P, tg, leaf_ids, w, ids = self._mc_leaves(name, nx, hypotheses, weights)
+        present = np.unique(tg)
+        try:
+            if len(present) < 2:
+                if pairs is not None and np.size(pairs):
+                    raise ValueError("pairs were given, and fewer than two targets are live")
+                pairs = np.zeros((0, 2), dtype=np.int64)
+            elif pairs is None and screen is not None:
+                pairs = evaluation.mc_pair_screen(x, tg, w, float(horizon), screen)
+            elif pairs is None:
+                T = len(present)
+                if T * (T - 1) // 2 > evaluation.MC_MAX_PAIRS:
+                    raise ValueError("%d targets make %d pairs, more than %d: give screen= (or pairs=)" % (T, T * (T - 1) // 2, evaluation.MC_MAX_PAIRS))
+                a, b = np.triu_indices(T, 1)
+                pairs = np.stack([present[a], present[b]], axis=1).astype(np.int64)
+            if len(present) < 2:      # (no pair: nothing is uploaded)
+                x, P, tg, leaf_ids, w = x[:0], P[:0], tg[:0], leaf_ids[:0], w[:0]
+            out = evaluation.mc_pair_encounters(x, P, tg, w, Phi, Q, steps, dt, float(radius), pairs, particles=particles, seed=seed,
+                                                transition="ct" if ct else "linear", ctx=self._ctx)
+        except ValueError as exc:
+            raise ValueError("%s: %s" % (name, str(exc).replace("mc_pair_screen: distance", "mc_pair_screen: screen", 1)))
+        lookup = lambda t: ids[t] if 0 <= t < len(ids) else -1
+        out["ids"] = np.array([[lookup(int(a)), lookup(int(b))] for a, b in out["pairs"]], dtype=np.int64).reshape(-1, 2)
+        out["leafIds"] = leaf_ids
+        p = out["pEver"]
+        n = len(p)
+        out["ranking"] = np.lexsort((np.arange(n), np.where(np.isnan(p), np.inf, -p))).astype(np.int64)
+        out["worst"] = int(out["ranking"][0]) if n else None
         return out
 
     def leafRows(self):
