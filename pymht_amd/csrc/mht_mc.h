@@ -62,6 +62,7 @@
 // MC_FILL = 1024 workgroups (four for each of the 256 compute units), at most one per 256 particles; 1024 targets or more get one chunk.
 // The split depends on (T, S) alone -- not on the device -- so the sizer and the launch agree, and it does not move a count.
 #pragma once
+#include <type_traits>
 #include "mht_smooth_ct_math.h"
 
 namespace mht {
@@ -190,6 +191,36 @@ struct McModel {
     double dt, R2;
 };
 
+MHT_HD bool mc_finite(double v) { return v - v == 0.0; }
+
+// The model of a call: Phi copied (null: zeros, for the constant-turn walk, which does not read it) and Q factored.  False: Q is not
+// positive semidefinite.
+template <int N>
+MHT_HD bool mc_model(const double* Phi, const double* Q, double dt, double R, McModel<N>& m) {
+    for (int c = 0; c < N * N; ++c) m.Phi[c] = Phi ? Phi[c] : 0.0;
+    m.dt = dt;
+    m.R2 = R * R;
+    return mc_factor<N, true>(Q, m.F) == 0;
+}
+
+// (nx, transition), as the seams admit them, to the instance <N, CT>: f(std::integral_constant<int, N>, std::bool_constant<CT>)
+template <class F>
+auto mc_dispatch(int nx, int transition, F&& f) {
+    if (nx == 4) return f(std::integral_constant<int, 4>{}, std::false_type{});
+    if (transition != 0) return f(std::integral_constant<int, 6>{}, std::true_type{});
+    return f(std::integral_constant<int, 6>{}, std::false_type{});
+}
+
+// The status of target t from its components' (1 wins over 2): the serial form of the kernels' strided fold
+MHT_HD int mc_target_status(const int32_t* first, const int32_t* cstatus, int t) {
+    bool nan = false, indefinite = false;
+    for (int c = first[t]; c < first[t + 1]; ++c) {
+        nan = nan || cstatus[c] == 1;
+        indefinite = indefinite || cstatus[c] == 2;
+    }
+    return nan ? 1 : (indefinite ? 2 : 0);
+}
+
 // The first component of lo .. hi (inclusive) with u < cdf[c]; hi if there is none
 MHT_HD int mc_pick(const double* cdf, int lo, int hi, double u) {
     while (lo < hi) {
@@ -240,6 +271,18 @@ MHT_HD bool mc_segment_inside(double px, double py, double dx, double dy, double
     return cx * cx + cy * cy < R2;
 }
 
+// X_0 of a particle from component c of nn: step 2 of the walk
+template <int N>
+MHT_HD void mc_draw(const double* x, const double* Lw, size_t nn, int c, const double* z, double* X) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double acc = Lw[(size_t)(i * (i + 1) / 2) * nn + c] * z[0];
+#pragma unroll
+        for (int j = 1; j <= i; ++j) acc = acc + Lw[(size_t)(i * (i + 1) / 2 + j) * nn + c] * z[j];
+        X[i] = x[(size_t)i * nn + c] + acc;
+    }
+}
+
 // Particle p of target t, held against the G paths of own [G][K + 1][2].  `live` false: a lane beyond the slab's end, which walks along
 // (the sink's ballots and barriers want every lane) and counts nowhere.  The sink takes
 //   within(g, inside)   per step, g = 0 .. G - 1 in turn, then   step_done(k)
@@ -256,17 +299,8 @@ MHT_HD void mc_walk(const McModel<N>& m, const double* x, const double* Lw, cons
     int k = 0;
     do {      // (K >= 1 and G >= 1, the seam's ranges: loops without a guard in front)
         mc_normals<N>(p, (uint32_t)k, (uint32_t)t, seed, z);
-        if (k == 0) {
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                double acc = Lw[(size_t)(i * (i + 1) / 2) * nn + c] * z[0];
-#pragma unroll
-                for (int j = 1; j <= i; ++j) acc = acc + Lw[(size_t)(i * (i + 1) / 2 + j) * nn + c] * z[j];
-                X[i] = x[(size_t)i * nn + c] + acc;
-            }
-        } else {
-            mc_step<N, CT>(m, z, X);
-        }
+        if (k == 0) mc_draw<N>(x, Lw, nn, c, z, X);
+        else mc_step<N, CT>(m, z, X);
         int g = 0;
         do {
             const double* o = own + ((size_t)g * (size_t)(K + 1) + (size_t)k) * 2;

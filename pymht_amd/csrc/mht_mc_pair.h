@@ -3,8 +3,8 @@
 // particle walked with process noise and, under the constant-turn model, with Phi(dt, w) of its own turn rate, counts that are the
 // same bits for one seed.  This header includes mht_mc.h and uses its functions unchanged: mc_philox keyed by (seed, target) -- the
 // streams of two targets are independent by construction --, mc_normals, the zero-pivot factor (mc_factor, mc_component), mc_pick,
-// mc_step<N, CT> and mc_segment_inside.  What it adds is a walk that carries two particles at once.  The code a lane of the kernels of
-// mht_mc_pair.hip runs per pair-particle, and tests/hostmath/mc_pair_host.cpp on the CPU.
+// mc_draw, mc_step<N, CT> and mc_segment_inside.  What it adds is a walk that carries two particles at once.  The code a lane of
+// mc_pair_walk_kernel (mht_mc.hip) runs per pair-particle, and tests/hostmath/mc_pair_host.cpp on the CPU.
 //
 // DEFINITION.  For pair j = (a, b) of distinct targets and particle index p = 0 .. S - 1: particle p of target a and particle p of
 // target b are walked EXACTLY as mc_walk walks them -- the same counter words (particle, step, target, block), the same order of every
@@ -33,18 +33,6 @@ namespace mht {
 
 constexpr int MC_MAX_PAIRS = 1 << 20;      // MHT_MC_MAX_PAIRS of include/mht_amd.h
 
-// X_0 of a particle from component c: mc_walk's draw, sum for sum
-template <int N>
-MHT_HD void mc_pair_draw(const double* x, const double* Lw, size_t nn, int c, const double* z, double* X) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double acc = Lw[(size_t)(i * (i + 1) / 2) * nn + c] * z[0];
-#pragma unroll
-        for (int j = 1; j <= i; ++j) acc = acc + Lw[(size_t)(i * (i + 1) / 2 + j) * nn + c] * z[j];
-        X[i] = x[(size_t)i * nn + c] + acc;
-    }
-}
-
 // Particle p of target ta against particle p of target tb.  The sink takes
 //   step(k, inside, first)   per step: the pair is inside R at step k; k is the first step with hit_k
 //   done(came)               at the end: the relative path came inside R
@@ -70,7 +58,7 @@ MHT_HD void mc_pair_walk(const McModel<N>& m, const double* x, const double* Lw,
         mc_normals<N>(p, (uint32_t)k, (uint32_t)tx, seed, z);
         if (k == 0) {      // (the particle's component and X_0, as mc_walk picks and draws them)
             const McRand u = mc_philox(p, MC_PICK_STEP, (uint32_t)tx, 0u, k0, k1);
-            mc_pair_draw<N>(x, Lw, nn, mc_pick(cdf, first[tx], first[tx + 1] - 1, mc_uniform(u.v[0])), z, X);
+            mc_draw<N>(x, Lw, nn, mc_pick(cdf, first[tx], first[tx + 1] - 1, mc_uniform(u.v[0])), z, X);
         } else {
             mc_step<N, CT>(m, z, X);
         }

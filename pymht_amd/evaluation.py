@@ -943,6 +943,35 @@ def _mc_arguments(who, x, P, target, weight, Phi, Q, steps, dt, radius, particle
     return dict(x=X, P=Pm, Phi=Phi, Q=Q, nx=nx, L=L, steps=int(steps), S=int(particles), order=order, targets=targets, first=first, cdf=cdf, T=T)
 
 
+def _mc_call(a, sizer, seam, extra, mid, shapes, dt, radius, seed, transition, device, ctx):
+    """The device call `mc_encounters` and `mc_pair_encounters` share, on `_mc_arguments`' dict `a`: x and P packed in `order`, one
+    upload (with `extra`, the seam's own device input: the own paths or the pairs' ranks), the work buffer of `sizer`, one int32 tensor
+    per entry of `shapes` (name -> shape, in the seam's order), the call of `seam` with `mid` as its middle size argument (G or n),
+    and the arrays read back: uint32 counts, `status` int32.  A context of its own where `ctx` is None."""
+    nx, L, T, steps, S, order = a["nx"], a["L"], a["T"], a["steps"], a["S"], a["order"]
+    iu = np.triu_indices(nx)
+    xp, Pp = np.ascontiguousarray(a["x"][order].T), np.ascontiguousarray(a["P"][order][:, iu[0], iu[1]].T)
+    Phi, Q = np.ascontiguousarray(a["Phi"]), np.ascontiguousarray(a["Q"])
+    mine = ctx is None
+    if mine:
+        ctx = Context(device, nx=nx)
+    try:
+        dev, lib = ctx.device, ctx.lib
+        x_d, P_d, f_d, c_d, e_d = [torch.from_numpy(v).to(dev) for v in (xp, Pp, a["first"], a["cdf"], extra)]
+        need = int(getattr(lib, sizer)(nx, L, T, mid, steps, S))
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        # (uint32 counts in int32 tensors: the same bits)
+        out = {name: torch.empty(shape, dtype=torch.int32, device=dev) for name, shape in shapes.items()}
+        torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
+        _lib.check(getattr(lib, seam)(ctx.handle, nx, 1 if transition == "ct" else 0, L, T, mid, steps, S, int(seed), float(dt), float(radius), Phi.ctypes.data,
+                                      Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(), f_d.data_ptr(), c_d.data_ptr(), e_d.data_ptr(),
+                                      *[t.data_ptr() for t in out.values()], work.data_ptr(), need), lib)
+        return {name: t.cpu().numpy() if name == "status" else t.cpu().numpy().view(np.uint32) for name, t in out.items()}
+    finally:
+        if mine:
+            ctx.close()
+
+
 def mc_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, ownPaths, particles=4096, seed=0, transition="linear", device=0, ctx=None):
     """Encounters by MONTE CARLO: every target is the Gaussian mixture of its components, `particles` particles per target are drawn from
     it, walked over steps * dt seconds WITH the model's process noise, and held against G paths of the own ship
@@ -972,8 +1001,7 @@ def mc_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, ownPaths, par
     violation (`firstAt`, which the pair engine has), more than 2^20 particles.
     One upload, one call of `mht_mc_encounters` (three launches), no host fallback."""
     a = _mc_arguments("mc_encounters", x, P, target, weight, Phi, Q, steps, dt, radius, particles, seed, transition)
-    X, Pm, Phi, Q, nx, L, steps, S = a["x"], a["P"], a["Phi"], a["Q"], a["nx"], a["L"], a["steps"], a["S"]
-    order, targets, first, cdf, T = a["order"], a["targets"], a["first"], a["cdf"], a["T"]
+    L, steps, order, targets, first, cdf, T = a["L"], a["steps"], a["order"], a["targets"], a["first"], a["cdf"], a["T"]
     try:
         own = np.ascontiguousarray(ownPaths, dtype=np.float64)
     except (TypeError, ValueError):
@@ -986,29 +1014,8 @@ def mc_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, ownPaths, par
         res.update(within=np.zeros((G, steps + 1, 0), dtype=np.uint32), ever=np.zeros((G, 0), dtype=np.uint32), valid=np.zeros(0, dtype=np.uint32),
                    status=np.zeros(0, dtype=np.int32))
     else:
-        iu = np.triu_indices(nx)
-        xp, Pp = np.ascontiguousarray(X[order].T), np.ascontiguousarray(Pm[order][:, iu[0], iu[1]].T)
-        Phi, Q = np.ascontiguousarray(Phi), np.ascontiguousarray(Q)
-        mine = ctx is None
-        if mine:
-            ctx = Context(device, nx=nx)
-        try:
-            dev, lib = ctx.device, ctx.lib
-            x_d, P_d, f_d, c_d, o_d = [torch.from_numpy(a).to(dev) for a in (xp, Pp, first, cdf, own)]
-            need = int(lib.mht_mc_work_bytes(nx, L, T, G, steps, S))
-            work = torch.empty(need, dtype=torch.uint8, device=dev)
-            # (uint32 counts in int32 tensors: the same bits)
-            w_d, e_d = torch.empty((G, steps + 1, T), dtype=torch.int32, device=dev), torch.empty((G, T), dtype=torch.int32, device=dev)
-            v_d, s_d = torch.empty(T, dtype=torch.int32, device=dev), torch.empty(T, dtype=torch.int32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
-            _lib.check(lib.mht_mc_encounters(ctx.handle, nx, 1 if transition == "ct" else 0, L, T, G, steps, S, int(seed), float(dt), float(radius),
-                                             Phi.ctypes.data, Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(), f_d.data_ptr(), c_d.data_ptr(), o_d.data_ptr(),
-                                             w_d.data_ptr(), e_d.data_ptr(), v_d.data_ptr(), s_d.data_ptr(), work.data_ptr(), need), lib)
-            res.update(within=w_d.cpu().numpy().view(np.uint32), ever=e_d.cpu().numpy().view(np.uint32), valid=v_d.cpu().numpy().view(np.uint32),
-                       status=s_d.cpu().numpy())
-        finally:
-            if mine:
-                ctx.close()
+        res.update(_mc_call(a, "mht_mc_work_bytes", "mht_mc_encounters", own, G, dict(within=(G, steps + 1, T), ever=(G, T), valid=(T,), status=(T,)), dt, radius, seed,
+                            transition, device, ctx))
     res.update(mc_derive(res["within"], res["ever"], res["valid"], float(dt)))
     return res
 
@@ -1070,8 +1077,7 @@ def mc_pair_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, pairs, p
     many pairs is walked once per pair."""
     who = "mc_pair_encounters"
     a = _mc_arguments(who, x, P, target, weight, Phi, Q, steps, dt, radius, particles, seed, transition)
-    X, Pm, Phi, Q, nx, L, steps, S = a["x"], a["P"], a["Phi"], a["Q"], a["nx"], a["L"], a["steps"], a["S"]
-    order, targets, first, cdf, T = a["order"], a["targets"], a["first"], a["cdf"], a["T"]
+    L, steps, order, targets, first, cdf, T = a["L"], a["steps"], a["order"], a["targets"], a["first"], a["cdf"], a["T"]
     try:
         pr = np.asarray(pairs)
     except (TypeError, ValueError):
@@ -1095,30 +1101,8 @@ def mc_pair_encounters(x, P, target, weight, Phi, Q, steps, dt, radius, pairs, p
         res.update(within=np.zeros((steps + 1, 0), dtype=np.uint32), firstAt=np.zeros((steps + 1, 0), dtype=np.uint32), ever=np.zeros(0, dtype=np.uint32),
                    valid=np.zeros(0, dtype=np.uint32), status=np.zeros(0, dtype=np.int32))
     else:
-        iu = np.triu_indices(nx)
-        xp, Pp = np.ascontiguousarray(X[order].T), np.ascontiguousarray(Pm[order][:, iu[0], iu[1]].T)
-        Phi, Q = np.ascontiguousarray(Phi), np.ascontiguousarray(Q)
-        idx = np.ascontiguousarray(rank, dtype=np.int32)
-        mine = ctx is None
-        if mine:
-            ctx = Context(device, nx=nx)
-        try:
-            dev, lib = ctx.device, ctx.lib
-            x_d, P_d, f_d, c_d, p_d = [torch.from_numpy(v).to(dev) for v in (xp, Pp, first, cdf, idx)]
-            need = int(lib.mht_mc_pair_work_bytes(nx, L, T, n, steps, S))
-            work = torch.empty(need, dtype=torch.uint8, device=dev)
-            # (uint32 counts in int32 tensors: the same bits)
-            w_d, a_d = torch.empty((steps + 1, n), dtype=torch.int32, device=dev), torch.empty((steps + 1, n), dtype=torch.int32, device=dev)
-            e_d, v_d, s_d = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3)]
-            torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
-            _lib.check(lib.mht_mc_pair_encounters(ctx.handle, nx, 1 if transition == "ct" else 0, L, T, n, steps, S, int(seed), float(dt), float(radius),
-                                                  Phi.ctypes.data, Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(), f_d.data_ptr(), c_d.data_ptr(), p_d.data_ptr(),
-                                                  w_d.data_ptr(), a_d.data_ptr(), e_d.data_ptr(), v_d.data_ptr(), s_d.data_ptr(), work.data_ptr(), need), lib)
-            res.update(within=w_d.cpu().numpy().view(np.uint32), firstAt=a_d.cpu().numpy().view(np.uint32), ever=e_d.cpu().numpy().view(np.uint32),
-                       valid=v_d.cpu().numpy().view(np.uint32), status=s_d.cpu().numpy())
-        finally:
-            if mine:
-                ctx.close()
+        res.update(_mc_call(a, "mht_mc_pair_work_bytes", "mht_mc_pair_encounters", np.ascontiguousarray(rank, dtype=np.int32), n,
+                            dict(within=(steps + 1, n), firstAt=(steps + 1, n), ever=(n,), valid=(n,), status=(n,)), dt, radius, seed, transition, device, ctx))
     res.update(mc_pair_derive(res["within"], res["firstAt"], res["ever"], res["valid"], float(dt)))
     return res
 

@@ -1524,6 +1524,30 @@ class Tracker():
             x, P, tg, leaf_ids, w = np.zeros((0, nx)), np.zeros((0, nx, nx)), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0)
         return x, P, tg, leaf_ids, w, ids
 
+    def _mc_horizon(self, name, horizon, radius, steps):
+        """What both getMonteCarlo* calls make of (horizon, radius, steps), ValueError under the caller's `name`: (steps, dt, nx, Phi, Q,
+        ct) -- the steps (None: one per radar period, at most evaluation.ENCOUNTER_MAX_STEPS), dt = horizon / steps, and the model's
+        matrices of one step, widened from float32; ct: a constant-turn tracker, whose Phi no particle reads."""
+        from . import evaluation
+        for what, v in (("horizon", horizon), ("radius", radius)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+                raise ValueError("%s: %s must be a finite positive number (got %r)" % (name, what, v))
+        if steps is None:
+            steps = min(int(np.ceil(float(horizon) / float(self.radarPeriod))), evaluation.ENCOUNTER_MAX_STEPS)
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= evaluation.ENCOUNTER_MAX_STEPS:
+            raise ValueError("%s: steps is an integer in 1 .. %d (got %r)" % (name, evaluation.ENCOUNTER_MAX_STEPS, steps))
+        steps = int(steps)
+        dt = float(horizon) / steps
+        model = self._model_mod
+        ct = getattr(model, "transition", None) == "ct"
+        if ct:
+            nx = 6
+            widen = lambda m: np.ascontiguousarray(np.asarray(m, dtype=np.float32).astype(np.float64).reshape(nx, nx))
+            Phi, Q = widen(model.Phi(dt, 0.0)), widen(model.Q(dt))      # (Phi is not read: every particle has its own)
+        else:
+            nx, Phi, Q = evaluation.encounter_model(model, dt)
+        return steps, dt, nx, Phi, Q, ct
+
     def getMonteCarloEncounters(self, horizon, radius, ownShip, particles=4096, seed=0, courseChanges=(0.0,), turnRate=None, speedFactors=(1.0,), delay=0.0,
                                 steps=None, hypotheses=True, weights=None):
         """Encounters by MONTE CARLO (evaluation.mc_encounters defines the figures): particles drawn from the forest's own leaves -- a
@@ -1553,25 +1577,9 @@ class Tracker():
         candidate has a figure.  No live track: empty arrays, no device call."""
         from . import evaluation
         name = "getMonteCarloEncounters"
-        for what, v in (("horizon", horizon), ("radius", radius)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
-                raise ValueError("%s: %s must be a finite positive number (got %r)" % (name, what, v))
         if isinstance(delay, bool) or not isinstance(delay, (int, float, np.integer, np.floating)) or not np.isfinite(delay) or delay < 0:
             raise ValueError("%s: delay must be a finite number >= 0 (got %r)" % (name, delay))
-        if steps is None:
-            steps = min(int(np.ceil(float(horizon) / float(self.radarPeriod))), evaluation.ENCOUNTER_MAX_STEPS)
-        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= evaluation.ENCOUNTER_MAX_STEPS:
-            raise ValueError("%s: steps is an integer in 1 .. %d (got %r)" % (name, evaluation.ENCOUNTER_MAX_STEPS, steps))
-        steps = int(steps)
-        dt = float(horizon) / steps
-        model = self._model_mod
-        ct = getattr(model, "transition", None) == "ct"
-        if ct:
-            nx = 6
-            widen = lambda m: np.ascontiguousarray(np.asarray(m, dtype=np.float32).astype(np.float64).reshape(nx, nx))
-            Phi, Q = widen(model.Phi(dt, 0.0)), widen(model.Q(dt))      # (Phi is not read: every particle has its own)
-        else:
-            nx, Phi, Q = evaluation.encounter_model(model, dt)
+        steps, dt, nx, Phi, Q, ct = self._mc_horizon(name, horizon, radius, steps)
         own = np.asarray(ownShip, dtype=np.float64).reshape(-1)
         if len(own) != 4 or not np.isfinite(own).all():
             raise ValueError("%s: ownShip is a finite [x, y, vx, vy] (got %r)" % (name, ownShip))
@@ -1631,23 +1639,7 @@ class Tracker():
         getHypothesisEncounters' Gaussian cells, and firstAt for getMonteCarloEncounters."""
         from . import evaluation
         name = "getMonteCarloPairEncounters"
-        for what, v in (("horizon", horizon), ("radius", radius)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
-                raise ValueError("%s: %s must be a finite positive number (got %r)" % (name, what, v))
-        if steps is None:
-            steps = min(int(np.ceil(float(horizon) / float(self.radarPeriod))), evaluation.ENCOUNTER_MAX_STEPS)
-        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= steps <= evaluation.ENCOUNTER_MAX_STEPS:
-            raise ValueError("%s: steps is an integer in 1 .. %d (got %r)" % (name, evaluation.ENCOUNTER_MAX_STEPS, steps))
-        steps = int(steps)
-        dt = float(horizon) / steps
-        model = self._model_mod
-        ct = getattr(model, "transition", None) == "ct"
-        if ct:
-            nx = 6
-            widen = lambda m: np.ascontiguousarray(np.asarray(m, dtype=np.float32).astype(np.float64).reshape(nx, nx))
-            Phi, Q = widen(model.Phi(dt, 0.0)), widen(model.Q(dt))      # (Phi is not read: every particle has its own)
-        else:
-            nx, Phi, Q = evaluation.encounter_model(model, dt)
+        steps, dt, nx, Phi, Q, ct = self._mc_horizon(name, horizon, radius, steps)
         x, P, tg, leaf_ids, w, ids = self._mc_leaves(name, nx, hypotheses, weights)
         present = np.unique(tg)
         try:

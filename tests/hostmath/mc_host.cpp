@@ -3,22 +3,7 @@
 // particles of a target as a loop and the wavefronts' ballots as plain increments, so that the generator, the factor, the pick, both
 // walks and the counts are checked against tests/mc_ref.py without a GPU (tests/test_mc_cpu.py), and the seam against this twin
 // (tests/test_mc_gpu.py).  tests/hostmath/mc_host_main.cpp makes a stand-alone program of it for a sanitizer build.
-#include <cmath>
-#include <cstdint>
-#include <cstddef>
-#include <cstdio>
-#include <vector>
-using std::fma;
-using std::sqrt;
-using std::fabs;
-using std::fmin;
-using std::fmax;
-using std::log;
-using std::sin;
-using std::cos;
-#include "../../pymht_amd/csrc/mht_mc.h"
-
-using namespace mht;
+#include "mc_host_common.h"
 
 namespace {
 
@@ -33,34 +18,37 @@ struct HostSink {      // one particle at a time: a ballot's popcount is 0 or 1
     void particle_done() { k = 0; }
 };
 
-bool is_finite(double v) { return v - v == 0.0; }
-
 template <int N, bool CT>
 int run(int32_t nComp, int32_t T, int32_t G, int32_t K, int32_t S, uint64_t seed, double dt, double R, const double* Phi, const double* Q, const double* x,
         const double* P, const int32_t* first, const double* cdf, const double* own, uint32_t* within, uint32_t* ever, uint32_t* valid, int32_t* status) {
-    constexpr int NS = N * (N + 1) / 2;
     McModel<N> m;
-    for (int c = 0; c < N * N; ++c) m.Phi[c] = CT ? 0.0 : Phi[c];
-    if (mc_factor<N, true>(Q, m.F) != 0) return -1;
-    m.dt = dt;
-    m.R2 = R * R;
-    std::vector<double> Lw((size_t)NS * (size_t)nComp);
-    std::vector<int32_t> cst((size_t)nComp);
-    for (int c = 0; c < nComp; ++c) mc_component<N>(x, P, cdf, nComp, c, Lw.data(), cst.data());      // a lane's component
+    std::vector<double> Lw;
+    std::vector<int32_t> tst;
+    if (!prepare<N, CT>(nComp, T, dt, R, Phi, Q, x, P, first, cdf, m, Lw, tst)) return -1;
     for (size_t i = 0; i < (size_t)G * (size_t)(K + 1) * (size_t)T; ++i) within[i] = 0;
     for (size_t i = 0; i < (size_t)G * (size_t)T; ++i) ever[i] = 0;
     for (int t = 0; t < T; ++t) {
-        bool nan = false, indefinite = false;
-        for (int c = first[t]; c < first[t + 1]; ++c) {
-            nan = nan || cst[c] == 1;
-            indefinite = indefinite || cst[c] == 2;
-        }
-        status[t] = nan ? 1 : (indefinite ? 2 : 0);
+        status[t] = tst[t];
         valid[t] = status[t] == 0 ? (uint32_t)S : 0u;
         if (status[t] != 0) continue;
         HostSink sink{within + t, ever + t, (size_t)T, K};
         for (int32_t p = 0; p < S; ++p)      // a lane's particle
             mc_walk<N, CT>(m, x, Lw.data(), first, cdf, own, nComp, G, K, seed, t, (uint32_t)p, true, sink);
+    }
+    return 0;
+}
+
+// The states of one walk from x0 with the noise of (particle, target): out [K + 1][N]
+template <int N, bool CT>
+int path(int32_t K, double dt, const double* Phi, const double* Q, const double* x0, uint64_t seed, uint32_t particle, uint32_t target, double* out) {
+    McModel<N> m;
+    if (!mc_model<N>(CT ? nullptr : Phi, Q, dt, 0.0, m)) return -1;
+    double X[N], z[N];
+    for (int i = 0; i < N; ++i) out[i] = X[i] = x0[i];
+    for (int k = 1; k <= K; ++k) {
+        mc_normals<N>(particle, (uint32_t)k, target, seed, z);
+        mc_step<N, CT>(m, z, X);
+        for (int i = 0; i < N; ++i) out[k * N + i] = X[i];
     }
     return 0;
 }
@@ -97,47 +85,15 @@ extern "C" void mc_chunks_host(int32_t T, int32_t S, int32_t* out) {
 // The states of ONE walk from x0 [nx] (no draw of X_0) with the noise of (particle, target): out [K + 1][nx]
 extern "C" int mc_path_host(int32_t nx, int32_t transition, int32_t K, double dt, const double* Phi, const double* Q, const double* x0, uint64_t seed,
                             uint32_t particle, uint32_t target, double* out) {
-    double X[6], z[6];
-    for (int i = 0; i < nx; ++i) out[i] = X[i] = x0[i];
-    if (nx == 4) {
-        McModel<4> m;
-        for (int c = 0; c < 16; ++c) m.Phi[c] = Phi[c];
-        if (mc_factor<4, true>(Q, m.F) != 0) return -1;
-        m.dt = dt;
-        for (int k = 1; k <= K; ++k) {
-            mc_normals<4>(particle, (uint32_t)k, target, seed, z);
-            mc_step<4, false>(m, z, X);
-            for (int i = 0; i < 4; ++i) out[k * 4 + i] = X[i];
-        }
-        return 0;
-    }
-    McModel<6> m;
-    for (int c = 0; c < 36; ++c) m.Phi[c] = transition ? 0.0 : Phi[c];
-    if (mc_factor<6, true>(Q, m.F) != 0) return -1;
-    m.dt = dt;
-    for (int k = 1; k <= K; ++k) {
-        mc_normals<6>(particle, (uint32_t)k, target, seed, z);
-        if (transition) mc_step<6, true>(m, z, X);
-        else mc_step<6, false>(m, z, X);
-        for (int i = 0; i < 6; ++i) out[k * 6 + i] = X[i];
-    }
-    return 0;
+    return mc_dispatch(nx, transition, [&](auto n, auto ct) { return path<decltype(n)::value, decltype(ct)::value>(K, dt, Phi, Q, x0, seed, particle, target, out); });
 }
 
 // The seam's arguments on host arrays.  Returns 0, or -1 where the seam refuses (nothing written).
 extern "C" int mc_encounters_host(int32_t nx, int32_t transition, int32_t nComp, int32_t T, int32_t G, int32_t K, int32_t S, uint64_t seed, double dt, double R,
                                   const double* Phi, const double* Q, const double* x, const double* P, const int32_t* first, const double* cdf,
                                   const double* own, uint32_t* within, uint32_t* ever, uint32_t* valid, int32_t* status) {
-    if ((nx != 4 && nx != 6) || (transition != 0 && transition != 1) || (transition == 1 && nx != 6)) return -1;
-    if (nComp < 1 || T < 1 || T > nComp || G < 1 || G > MC_MAX_PATHS || K < 1 || K > MC_MAX_STEPS) return -1;
-    if (S < MC_WARP || S > MC_MAX_PARTICLES || S % MC_WARP != 0) return -1;
-    if (!(R > 0.0) || !(dt > 0.0) || !is_finite(R) || !is_finite(dt)) return -1;
-    if (first[0] != 0 || first[T] != nComp) return -1;
-    for (int t = 0; t < T; ++t)
-        if (first[t + 1] <= first[t]) return -1;
-    for (int c = 0; c < nx * nx; ++c)
-        if (!is_finite(Q[c]) || (transition == 0 && !is_finite(Phi[c]))) return -1;
-    if (nx == 4) return run<4, false>(nComp, T, G, K, S, seed, dt, R, Phi, Q, x, P, first, cdf, own, within, ever, valid, status);
-    if (transition) return run<6, true>(nComp, T, G, K, S, seed, dt, R, Phi, Q, x, P, first, cdf, own, within, ever, valid, status);
-    return run<6, false>(nComp, T, G, K, S, seed, dt, R, Phi, Q, x, P, first, cdf, own, within, ever, valid, status);
+    if (!fits(nx, transition, nComp, T, K, dt, R, Phi, Q, first) || !particles_fit(S) || G < 1 || G > MC_MAX_PATHS) return -1;
+    return mc_dispatch(nx, transition, [&](auto n, auto ct) {
+        return run<decltype(n)::value, decltype(ct)::value>(nComp, T, G, K, S, seed, dt, R, Phi, Q, x, P, first, cdf, own, within, ever, valid, status);
+    });
 }

@@ -1,24 +1,9 @@
-// TEST-ONLY host build of csrc/mht_mc_pair.h: mc_pair_walk itself -- what a lane of mc_pair_walk_kernel (mht_mc_pair.hip) runs per
+// TEST-ONLY host build of csrc/mht_mc_pair.h: mc_pair_walk itself -- what a lane of mc_pair_walk_kernel (mht_mc.hip) runs per
 // pair-particle -- and mht_mc.h's mc_component, compiled for the CPU and run over a call in the seam's own layouts, the particle
 // indices of a pair as a loop and the wavefronts' ballots as plain increments, so that the pair engine's counts are checked against
 // tests/mc_pair_ref.py without a GPU (tests/test_mc_pair_cpu.py), and the seam against this twin (tests/test_mc_pair_gpu.py).
 // tests/hostmath/mc_pair_host_main.cpp makes a stand-alone program of it for a sanitizer build.
-#include <cmath>
-#include <cstdint>
-#include <cstddef>
-#include <cstdio>
-#include <vector>
-using std::fma;
-using std::sqrt;
-using std::fabs;
-using std::fmin;
-using std::fmax;
-using std::log;
-using std::sin;
-using std::cos;
-#include "../../pymht_amd/csrc/mht_mc_pair.h"
-
-using namespace mht;
+#include "mc_host_common.h"
 
 namespace {
 
@@ -56,31 +41,6 @@ struct PairPathSink {       // one pair-particle: its two states, its relative p
     void done(bool came) { flags[2 * (K + 1)] = came ? 1 : 0; }
 };
 
-bool is_finite(double v) { return v - v == 0.0; }
-
-template <int N, bool CT>
-bool prepare(int32_t nComp, int32_t T, double dt, double R, const double* Phi, const double* Q, const double* x, const double* P, const int32_t* first,
-             const double* cdf, McModel<N>& m, std::vector<double>& Lw, std::vector<int32_t>& tst) {
-    constexpr int NS = N * (N + 1) / 2;
-    for (int c = 0; c < N * N; ++c) m.Phi[c] = CT ? 0.0 : Phi[c];
-    if (mc_factor<N, true>(Q, m.F) != 0) return false;
-    m.dt = dt;
-    m.R2 = R * R;
-    Lw.assign((size_t)NS * (size_t)nComp, 0.0);
-    std::vector<int32_t> cst((size_t)nComp);
-    for (int c = 0; c < nComp; ++c) mc_component<N>(x, P, cdf, nComp, c, Lw.data(), cst.data());      // a lane's component
-    tst.assign((size_t)T, 0);
-    for (int t = 0; t < T; ++t) {
-        bool nan = false, indefinite = false;
-        for (int c = first[t]; c < first[t + 1]; ++c) {
-            nan = nan || cst[c] == 1;
-            indefinite = indefinite || cst[c] == 2;
-        }
-        tst[t] = nan ? 1 : (indefinite ? 2 : 0);
-    }
-    return true;
-}
-
 template <int N, bool CT>
 int run(int32_t nComp, int32_t T, int32_t nPair, int32_t K, int32_t S, uint64_t seed, double dt, double R, const double* Phi, const double* Q, const double* x,
         const double* P, const int32_t* first, const double* cdf, const int32_t* pairs, uint32_t* within, uint32_t* firstAt, uint32_t* ever, uint32_t* valid,
@@ -117,33 +77,20 @@ int one(int32_t nComp, int32_t T, int32_t K, uint64_t seed, double dt, double R,
     return 0;
 }
 
-bool fits(int32_t nx, int32_t transition, int32_t nComp, int32_t T, int32_t K, double dt, double R, const double* Phi, const double* Q, const int32_t* first) {
-    if ((nx != 4 && nx != 6) || (transition != 0 && transition != 1) || (transition == 1 && nx != 6)) return false;
-    if (nComp < 1 || T < 1 || T > nComp || K < 1 || K > MC_MAX_STEPS) return false;
-    if (!(R > 0.0) || !(dt > 0.0) || !is_finite(R) || !is_finite(dt)) return false;
-    if (first[0] != 0 || first[T] != nComp) return false;
-    for (int t = 0; t < T; ++t)
-        if (first[t + 1] <= first[t]) return false;
-    for (int c = 0; c < nx * nx; ++c)
-        if (!is_finite(Q[c]) || (transition == 0 && !is_finite(Phi[c]))) return false;
-    return true;
-}
-
 }  // namespace
 
 // The seam's arguments on host arrays.  Returns 0, or -1 where the seam refuses (nothing written).
 extern "C" int mc_pair_encounters_host(int32_t nx, int32_t transition, int32_t nComp, int32_t T, int32_t nPair, int32_t K, int32_t S, uint64_t seed, double dt,
                                        double R, const double* Phi, const double* Q, const double* x, const double* P, const int32_t* first, const double* cdf,
                                        const int32_t* pairs, uint32_t* within, uint32_t* firstAt, uint32_t* ever, uint32_t* valid, int32_t* status) {
-    if (!fits(nx, transition, nComp, T, K, dt, R, Phi, Q, first)) return -1;
-    if (nPair < 1 || nPair > MC_MAX_PAIRS || S < MC_WARP || S > MC_MAX_PARTICLES || S % MC_WARP != 0) return -1;
+    if (!fits(nx, transition, nComp, T, K, dt, R, Phi, Q, first) || !particles_fit(S) || nPair < 1 || nPair > MC_MAX_PAIRS) return -1;
     for (int j = 0; j < nPair; ++j) {
         const int32_t a = pairs[2 * (size_t)j], b = pairs[2 * (size_t)j + 1];
         if (a < 0 || a >= T || b < 0 || b >= T || a == b) return -1;
     }
-    if (nx == 4) return run<4, false>(nComp, T, nPair, K, S, seed, dt, R, Phi, Q, x, P, first, cdf, pairs, within, firstAt, ever, valid, status);
-    if (transition) return run<6, true>(nComp, T, nPair, K, S, seed, dt, R, Phi, Q, x, P, first, cdf, pairs, within, firstAt, ever, valid, status);
-    return run<6, false>(nComp, T, nPair, K, S, seed, dt, R, Phi, Q, x, P, first, cdf, pairs, within, firstAt, ever, valid, status);
+    return mc_dispatch(nx, transition, [&](auto n, auto ct) {
+        return run<decltype(n)::value, decltype(ct)::value>(nComp, T, nPair, K, S, seed, dt, R, Phi, Q, x, P, first, cdf, pairs, within, firstAt, ever, valid, status);
+    });
 }
 
 // ONE pair-particle: the two particles' states [K + 1][2][nx] (a, then b), the relative path d_k [K + 1][2], and flags [K + 1][2]
@@ -153,9 +100,9 @@ extern "C" int mc_pair_path_host(int32_t nx, int32_t transition, int32_t nComp, 
                                  const double* Q, const double* x, const double* P, const int32_t* first, const double* cdf, int32_t ta, int32_t tb,
                                  uint32_t particle, double* states, double* rel, int32_t* flags) {
     if (!fits(nx, transition, nComp, T, K, dt, R, Phi, Q, first) || ta < 0 || ta >= T || tb < 0 || tb >= T || ta == tb) return -1;
-    if (nx == 4) return one<4, false>(nComp, T, K, seed, dt, R, Phi, Q, x, P, first, cdf, ta, tb, particle, states, rel, flags);
-    if (transition) return one<6, true>(nComp, T, K, seed, dt, R, Phi, Q, x, P, first, cdf, ta, tb, particle, states, rel, flags);
-    return one<6, false>(nComp, T, K, seed, dt, R, Phi, Q, x, P, first, cdf, ta, tb, particle, states, rel, flags);
+    return mc_dispatch(nx, transition, [&](auto n, auto ct) {
+        return one<decltype(n)::value, decltype(ct)::value>(nComp, T, K, seed, dt, R, Phi, Q, x, P, first, cdf, ta, tb, particle, states, rel, flags);
+    });
 }
 
 // The sizer's split of a pair's particle indices: (chunks, slab) of mc_chunks(nPair, S)

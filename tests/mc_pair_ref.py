@@ -115,7 +115,7 @@ def untouched(out):
 
 
 def work_bytes(nx, nComp, T, nPair, K, S):
-    """csrc/mht_mc_pair.hip's layout restated: the factors, the chunks' counts (within, firstAt and ever of every pair), the components'
+    """csrc/mht_mc.hip's layout of a pair call restated: the factors, the chunks' counts (within, firstAt and ever of every pair), the components'
     and the pairs' status"""
     chunks = ref.chunks(nPair, S)[0]
     return (nx * (nx + 1) // 2 * nComp * 8 + chunks * (2 * (K + 1) + 1) * nPair * 4 + nComp * 4 + nPair * 4 + 255) // 256 * 256

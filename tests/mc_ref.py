@@ -286,6 +286,28 @@ def scene_c():
     return _cache["c"]
 
 
+def scene_stride():
+    """Targets 2, 37 and 38 of scene A against THREE own paths over K = 5 steps, S = 768: several chunks (3 of 256 particles), several
+    paths and several targets at once, with K + 1 = 6 != G = 3 -- the smallest call in which a word of a workgroup's slab stored with
+    a wrong stride (the chunk's, the path's or the target's) lands in another cell."""
+    a = scene_a()
+    idx = [2, 37, 38]
+    cand = np.array([[0.0, 1.0, 0.0], [tref.DEG40, 1.0, 10.0], [-tref.DEG40, 1.0, 0.0]])
+    return scene(a["x"][idx], a["P"][idx], np.arange(4), np.ones(3), a["Phi"], a["Q"], own_paths(a["x"][0, :4], cand, 5, DT), K=5, S=768)
+
+
+def check_stride_counts(o):
+    """scene_stride's own conditions on a set of counts: every (path, target) comes inside R with some and not with all particles, and
+    no two targets and not all paths have the same counts, so that a transposed or mis-strided store cannot pass."""
+    assert chunks(3, 768) == (3, 256)
+    assert o["within"].shape == (3, 6, 3) and o["ever"].shape == (3, 3) and o["valid"].tolist() == [768] * 3 and o["status"].tolist() == [0] * 3
+    assert ((o["ever"] > 0) & (o["ever"] < 768)).all() and (o["within"].sum(axis=1) > 0).all() and (o["ever"] >= o["within"].max(axis=1)).all()
+    for name in ("within", "ever"):
+        c = o[name]
+        assert all(not np.array_equal(c[..., s], c[..., t]) for s in range(3) for t in range(s)), name      # every two targets differ
+        assert sum(not np.array_equal(c[g], c[h]) for g in range(3) for h in range(g)) >= 2, name           # at least two paths differ
+
+
 def reference(sc, name=None):
     """encounters() of a scene, computed once per name"""
     if name is not None and ("ref", name) in _cache:

@@ -128,6 +128,15 @@ def test_a_target_of_67_components(twin):
     assert ref.hold_counts("67 components", got, want) == 0 and 0 < got["within"][0, 0, 0] < 1024
 
 
+def test_three_chunks_three_paths_three_targets(twin):
+    """mc_ref.scene_stride: the reference alone satisfies the case's conditions, and the twin's counts are the reference's"""
+    sc = ref.scene_stride()
+    got, want = ref.call_twin(twin, sc), ref.reference(sc)
+    ref.check_stride_counts(want)
+    assert ref.hold_counts("strides", got, want) == 0
+    ref.check_stride_counts(got)
+
+
 def test_scene_c_constant_turn(twin):
     sc = ref.scene_c()
     got, want = ref.call_twin(twin, sc), ref.reference(sc, "c")

@@ -86,6 +86,9 @@ def test_scenes_a_and_c_equal_the_twin_and_no_sentinel_is_left(ctxs, twin, name,
     assert int(((got["within"] > 0) & (got["within"] < sc["S"])).sum()) >= 40
 
 
+STRIDES = "3 chunks, G=3, K=5, T=3 (the strides of a workgroup's slab)"
+
+
 def _shape_scene(kind):
     a, c = ref.scene_a(), ref.scene_c()
     pick = lambda sc, idx, **kw: ref.scene(sc["x"][idx], sc["P"][idx], np.arange(len(idx) + 1), np.ones(len(idx)), sc["Phi"], sc["Q"],
@@ -108,6 +111,8 @@ def _shape_scene(kind):
         return pick(sc, few, K=K, dt=1.0, own=ref.own_paths(sc["x"][12, :4], cand, K, 1.0), S=256)
     if kind == "G=1":
         return pick(a, few, own=np.ascontiguousarray(a["own"][:1]), S=512)
+    if kind == STRIDES:
+        return ref.scene_stride()
     rng = np.random.default_rng(67)
     if kind == "67 components":
         n = 67
@@ -124,7 +129,7 @@ def _shape_scene(kind):
 
 
 @pytest.mark.parametrize("kind", ["S=64", "S=320", "T=1, S=65536", "T=70 (the factor launch past a wavefront)", "K=1", "K=64", "G=1", "G=64", "67 components",
-                                  "a NaN first component among good ones"])
+                                  "a NaN first component among good ones", STRIDES])
 def test_shapes_at_which_the_kernels_take_another_path(ctxs, twin, kind):
     sc = _shape_scene(kind)
     want = ref.call_twin(twin, sc)
@@ -132,6 +137,8 @@ def test_shapes_at_which_the_kernels_take_another_path(ctxs, twin, kind):
         rc, got = _raw(ctxs[lib_nx], sc)
         assert rc == 0, kind
         assert _hold("%s, %d-state build" % (kind, lib_nx), got, want, sc) == 0
+    if kind == STRIDES:
+        ref.check_stride_counts(want)
     if kind.startswith("a NaN"):
         assert want["status"].tolist() == [0, 1, 0] and want["valid"].tolist() == [512, 0, 512] and not want["within"][:, :, 1].any()
     assert want["within"].any() and (want["ever"] >= want["within"].max(axis=1)).all()
