@@ -179,6 +179,12 @@ int mht_solve_blp(mht_ctx* ctx, int32_t nHyp, int32_t nT, int32_t nRows, int32_t
 int mht_prune(mht_ctx* ctx, int32_t n_nodes, const int32_t* parent, int32_t T, const int32_t* sel, const int32_t* window,
               int32_t* new_root, uint8_t* keep);
 
+/* ---- the seams over a batch of track histories, (v) and (vi) below, share one host path (csrc/mht_smooth_seam.h): the model and the
+ * batch are checked on the host before anything is launched, the lengths go to the front of the workspace, one launch (EM: one per
+ * walk), a wait.  A workspace that is too small is MHT_E_CAPACITY from mht_smooth_tracks, mht_smooth_tracks_ct and
+ * mht_smooth_tracks_ais, and MHT_E_INVALID from every other seam, mht_smooth_tracks_em* included; a launch that fails is waited for
+ * before its error goes back, since the copy of the lengths reads the caller's array. */
+
 /* ---- seam (v): Target.getSmoothTrack (pyTarget.py:580-609) for ALL tracks of an export -- Tracker.getSmoothTracks, and the
  * <SmoothedStates> of every <Track> (pyTarget.py:745-802) -- stateless ---------------------------------------------------------
  * A fixed-interval Rauch-Tung-Striebel smoother over a batch of track histories, float64 throughout.  The reference hands each

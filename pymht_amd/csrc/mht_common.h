@@ -97,7 +97,7 @@ enum FgFamily : int { FG_PLAIN, FG_WAVE, FG_ADM, FG_AIS, FG_CT, FG_BATCH, FG_BAT
 enum KernelSlot : int {
     K_GATE, K_CLUSTER, K_CLUSTER_INIT, K_CLUSTER_BIG, K_CLUSTER_BATCH, K_BLP, K_BLP_UF, K_BLP_UF_PLAIN, K_BLP_BATCH, K_BLP_LIGHT_BATCH,
     K_SMOOTH_EM4, K_SMOOTH_EM6,      // (no LDS: the slots only route mht_smooth_tracks_em through launch_kernel)
-    K_SMOOTH_SCORE,                  // (no LDS either: every kernel of mht_smooth_score.hip goes through launch_kernel under this one)
+    K_SMOOTH_SCORE,                  // (no LDS either: every other kernel over track histories goes through launch_kernel under this one)
     K_GOSPA,                         // gospa_kernel (mht_gospa.hip): the search tables of the launch's largest step, 56 KB at 2048 x 2048
     K_OSPA2,                         // the kernels of mht_ospa2.hip; LDS: ospa2_assign_kernel's search tables, sized as K_GOSPA's
     K_KBEST,                         // kbest_kernel (mht_kbest.hip): a cluster's tables, sized by the launch's arguments, 45.8 KB at the limits

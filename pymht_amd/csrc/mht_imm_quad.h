@@ -49,17 +49,11 @@ static size_t imm_table_bytes(int32_t nx, int32_t r) {      // the mode table, P
 
 static size_t imm_work_bytes(int32_t nx, int32_t n_tracks, int32_t r) { return smooth_len_bytes(n_tracks) + imm_table_bytes(nx, r); }
 
-struct ImmBatch {      // what the seams are handed besides their model
-    int32_t n, L_max;
-    const int32_t* len;
-    const double *x_init, *P_init, *z;
-    const uint8_t* has_z;
+struct ImmBatch : TrackBatch {      // with the modes and the outputs
     int32_t r;
     const double *Q, *R, *Pi, *mu0;
     double *mu, *x, *P, *ll;
     int32_t* nobs;
-    void* work;
-    size_t work_bytes;
 };
 
 // A distribution over the modes: entries in [0, 1] that add up to 1

@@ -35,42 +35,19 @@ static int run_imm_smooth(mht_ctx* ctx, const char* seam, const Steps& steps, co
     if (b.n == 0) return MHT_OK;
     MHT_REQUIRE(b.len && b.x_init && b.P_init && b.z && b.has_z && b.Q && b.R && b.Pi && b.mu0 && b.mu && b.x && b.P && b.work, "%s: null array", seam);
     MHT_REQUIRE((b.ll == nullptr) == (b.nobs == nullptr), "%s: ll and nobs are handed over together, or both left out", seam);
-    for (int32_t t = 0; t < b.n; ++t)
-        MHT_REQUIRE(b.len[t] >= 1 && b.len[t] <= b.L_max, "%s: track %d has length %d (1 .. L_max = %d)", seam, t, b.len[t], b.L_max);
-    const size_t front = imm_work_bytes(N, b.n, b.r), need = front + imm_smooth_rows_bytes(N, b.n, b.L_max, b.r);
-    MHT_REQUIRE(b.work_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed (mht_imm_smooth_work_bytes)", seam, b.work_bytes, need);
-    const int rcc = check_chain(seam, b);
-    if (rcc != MHT_OK) return rcc;
+    const size_t front = imm_work_bytes(N, b.n, b.r);
+    int rc = check_lengths(seam, b);
+    if (rc == MHT_OK) rc = check_workspace(seam, b, front + imm_smooth_rows_bytes(N, b.n, b.L_max, b.r), "mht_imm_smooth_work_bytes", MHT_E_INVALID);
+    if (rc == MHT_OK) rc = check_chain(seam, b);
+    if (rc != MHT_OK) return rc;
     const std::vector<double> table = imm_table<N>(b);
-    MHT_HIP_CHECK(hipSetDevice(ctx->device));
-    char* w = static_cast<char*>(b.work);
     ImmSmoothArgs<N, Steps> a = {};
     a.f = imm_args<N>(steps, b);
     a.muf = muf;
-    a.rows = reinterpret_cast<double*>(w + front);
-    int rc = MHT_OK;
-    // (the copies read the caller's array and `table`: whatever fails from here on, the stream is waited for before the error goes back)
-    hipError_t e = hipMemcpyAsync(w, b.len, (size_t)b.n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(w + smooth_len_bytes(b.n), table.data(), table.size() * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        set_error("%s: copying to the workspace: %s", seam, hipGetErrorString(e));
-        rc = MHT_E_HIP;
-    } else {
-        rc = launch_kernel(ctx, K_SMOOTH_SCORE, imm_smooth_kernel<N, Steps>, dim3((b.n + 15) / 16), dim3(64), 0, false, a);
-    }
-    if (rc != MHT_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    MHT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHT_OK;
-}
-
-template <int N>
-static int run_imm_smooth_linear(mht_ctx* ctx, const mht_model_x* model, const ImmBatch& b, double* muf) {
-    LinearSteps<N> steps = {};
-    widen<N>(model, steps.model, steps.model.A);      // (Q and R too: every lane overwrites them with its mode's)
-    return run_imm_smooth<N>(ctx, "mht_imm_smooth_tracks", steps, b, muf);
+    a.rows = reinterpret_cast<double*>(static_cast<char*>(b.work) + front);
+    return run_over_lengths(ctx, seam, b, table.data(), table.size(), [&] {
+        return launch_kernel(ctx, K_SMOOTH_SCORE, imm_smooth_kernel<N, Steps>, dim3((b.n + 15) / 16), dim3(64), 0, false, a);
+    });
 }
 
 }  // namespace mht
@@ -82,33 +59,24 @@ extern "C" size_t mht_imm_smooth_work_bytes(int32_t nx, int32_t n_tracks, int32_
     return imm_work_bytes(nx, n_tracks, n_modes) + imm_smooth_rows_bytes(nx, n_tracks, L_max, n_modes);
 }
 
+// (the steps carry the model's Q and R too: every lane overwrites them with its mode's)
 extern "C" int mht_imm_smooth_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                                      const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_modes,
                                      const double* Q, const double* R, const double* Pi, const double* mu0, double* mus, double* xs, double* Ps,
                                      double* muf, double* ll, int32_t* nobs, void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_imm_smooth_tracks: null argument");
-    MHT_REQUIRE(model->nx == 4 || model->nx == 6, "mht_imm_smooth_tracks: nx must be 4 or 6 (got %d)", model->nx);
-    MHT_REQUIRE(model->transition == 0, "mht_imm_smooth_tracks: a state-dependent transition (%d) has no linear smoother to run", model->transition);
-    MHT_REQUIRE(model->A && model->Q && model->C && model->R, "mht_imm_smooth_tracks: null model matrix");
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_imm_smooth_tracks: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
-    const ImmBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, n_modes, Q, R, Pi, mu0, mus, xs, Ps, ll, nobs, work, work_bytes};
-    return model->nx == 4 ? run_imm_smooth_linear<4>(ctx, model, b, muf) : run_imm_smooth_linear<6>(ctx, model, b, muf);
+    const char* seam = "mht_imm_smooth_tracks";
+    const int rc = check_linear(seam, ctx, model, n_tracks, L_max);
+    if (rc != MHT_OK) return rc;
+    const ImmBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, n_modes, Q, R, Pi, mu0, mus, xs, Ps, ll, nobs};
+    return model->nx == 4 ? run_imm_smooth<4>(ctx, seam, linear_steps<4>(model), b, muf) : run_imm_smooth<6>(ctx, seam, linear_steps<6>(model), b, muf);
 }
 
 extern "C" int mht_imm_smooth_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                                         const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_modes,
                                         const double* Q, const double* R, const double* Pi, const double* mu0, double* mus, double* xs, double* Ps,
                                         double* muf, double* ll, int32_t* nobs, void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_imm_smooth_tracks_ct: null argument");
-    MHT_REQUIRE(model->nx == 6, "mht_imm_smooth_tracks_ct: the constant-turn model has 6 states (got nx = %d)", model->nx);
-    MHT_REQUIRE(model->transition == 1, "mht_imm_smooth_tracks_ct: transition must be 1 (got %d; a linear model belongs to mht_imm_smooth_tracks)",
-                model->transition);
-    MHT_REQUIRE(model->Q && model->C && model->R, "mht_imm_smooth_tracks_ct: null model matrix");
-    MHT_REQUIRE(model->period > 0.0, "mht_imm_smooth_tracks_ct: the model's period must be positive (got %g)", model->period);
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_imm_smooth_tracks_ct: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
-    ConstantTurnSteps steps = {};
-    widen<6>(model, steps.model);
-    steps.model.T = model->period;
-    const ImmBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, n_modes, Q, R, Pi, mu0, mus, xs, Ps, ll, nobs, work, work_bytes};
-    return run_imm_smooth<6>(ctx, "mht_imm_smooth_tracks_ct", steps, b, muf);
+    const int rc = check_ct("mht_imm_smooth_tracks_ct", ctx, model, n_tracks, L_max);
+    if (rc != MHT_OK) return rc;
+    const ImmBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, n_modes, Q, R, Pi, mu0, mus, xs, Ps, ll, nobs};
+    return run_imm_smooth<6>(ctx, "mht_imm_smooth_tracks_ct", ct_steps(model), b, muf);
 }

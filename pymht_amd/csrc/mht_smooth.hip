@@ -1,5 +1,6 @@
 // mht_smooth_tracks, mht_smooth_tracks_ct, mht_smooth_tracks_ais: fixed-interval Rauch-Tung-Striebel smoothing of a batch of track histories
-// (include/mht_amd.h).  One walk (smooth_walk, mht_smooth_walk.h) with a step policy per model, one kernel per model and one host path;
+// (include/mht_amd.h).  One walk (smooth_walk, mht_smooth_walk.h) with a step policy per model, one kernel per model and one host path
+// (mht_smooth_seam.h, shared with every other seam over track histories);
 // the arithmetic is mht_smooth_math.h, mht_smooth_ct_math.h and mht_smooth_ais_math.h.
 //
 // mht_smooth_tracks: what the reference does per track with pykalman at the end of a run (Target.getSmoothTrack, pyTarget.py:580-609,
@@ -71,16 +72,12 @@ template <int N, typename Steps>
 static int run_smooth(mht_ctx* ctx, const char* seam, const char* sizer, const Steps& steps, bool extras, const SmoothBatch& b,
                       void (*with_cov)(SmoothArgs<N, Steps>), void (*means_only)(SmoothArgs<N, Steps>)) {
     if (b.n == 0) return MHT_OK;
-    const int rc = check_batch(seam, sizer, N, Steps::SLOTS, b, extras);
+    const int rc = check_batch(seam, b, extras && b.xs, smooth_work_bytes(N, Steps::SLOTS, b.n, b.L_max), sizer, MHT_E_CAPACITY);
     if (rc != MHT_OK) return rc;
-    MHT_HIP_CHECK(hipSetDevice(ctx->device));
     SmoothArgs<N, Steps> a;
     smooth_args<N>(steps, b, a);
-    MHT_HIP_CHECK(hipMemcpyAsync(b.work, b.len, (size_t)b.n * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(b.Ps ? with_cov : means_only, dim3((b.n + 63) / 64), dim3(64), 0, ctx->stream, a);
-    MHT_HIP_CHECK(hipGetLastError());
-    MHT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHT_OK;
+    return run_over_lengths(ctx, seam, b, nullptr, 0,
+                            [&] { return launch_kernel(ctx, K_SMOOTH_SCORE, b.Ps ? with_cov : means_only, dim3((b.n + 63) / 64), dim3(64), 0, false, a); });
 }
 
 }  // namespace mht
@@ -92,23 +89,15 @@ extern "C" size_t mht_smooth_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_
     return smooth_work_bytes(nx, 1, n_tracks, L_max);
 }
 
-template <int N>
-static int run_linear(mht_ctx* ctx, const mht_model_x* model, const SmoothBatch& b) {
-    LinearSteps<N> steps = {};
-    widen<N>(model, steps.model, steps.model.A);
-    return run_smooth<N>(ctx, "mht_smooth_tracks", "mht_smooth_work_bytes", steps, true, b, smooth_rts_kernel<N, true>, smooth_rts_kernel<N, false>);
-}
-
 extern "C" int mht_smooth_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                                  const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* xs, double* Ps,
                                  void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_smooth_tracks: null argument");
-    MHT_REQUIRE(model->nx == 4 || model->nx == 6, "mht_smooth_tracks: nx must be 4 or 6 (got %d)", model->nx);
-    MHT_REQUIRE(model->transition == 0, "mht_smooth_tracks: a state-dependent transition (%d) has no linear smoother", model->transition);
-    MHT_REQUIRE(model->A && model->Q && model->C && model->R, "mht_smooth_tracks: null model matrix");
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_smooth_tracks: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
-    const SmoothBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, xs, Ps, work, work_bytes};
-    return model->nx == 4 ? run_linear<4>(ctx, model, b) : run_linear<6>(ctx, model, b);
+    const char *seam = "mht_smooth_tracks", *sizer = "mht_smooth_work_bytes";
+    const int rc = check_linear(seam, ctx, model, n_tracks, L_max);
+    if (rc != MHT_OK) return rc;
+    const SmoothBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, xs, Ps};
+    return model->nx == 4 ? run_smooth<4>(ctx, seam, sizer, linear_steps<4>(model), true, b, smooth_rts_kernel<4, true>, smooth_rts_kernel<4, false>)
+                          : run_smooth<6>(ctx, seam, sizer, linear_steps<6>(model), true, b, smooth_rts_kernel<6, true>, smooth_rts_kernel<6, false>);
 }
 
 extern "C" size_t mht_smooth_ct_work_bytes(int32_t n_tracks, int32_t L_max) {
@@ -119,17 +108,11 @@ extern "C" size_t mht_smooth_ct_work_bytes(int32_t n_tracks, int32_t L_max) {
 extern "C" int mht_smooth_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                                     const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, double* xs, double* Ps,
                                     void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_smooth_tracks_ct: null argument");
-    MHT_REQUIRE(model->nx == 6, "mht_smooth_tracks_ct: the constant-turn model has 6 states (got nx = %d)", model->nx);
-    MHT_REQUIRE(model->transition == 1, "mht_smooth_tracks_ct: transition must be 1 (got %d; a linear model belongs to mht_smooth_tracks)", model->transition);
-    MHT_REQUIRE(model->Q && model->C && model->R, "mht_smooth_tracks_ct: null model matrix");
-    MHT_REQUIRE(model->period > 0.0, "mht_smooth_tracks_ct: the model's period must be positive (got %g)", model->period);
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_smooth_tracks_ct: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
-    ConstantTurnSteps steps = {};
-    widen<6>(model, steps.model);
-    steps.model.T = model->period;
-    const SmoothBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, xs, Ps, work, work_bytes};
-    return run_smooth<6>(ctx, "mht_smooth_tracks_ct", "mht_smooth_ct_work_bytes", steps, true, b, smooth_rts_ct_kernel<true>, smooth_rts_ct_kernel<false>);
+    const int rc = check_ct("mht_smooth_tracks_ct", ctx, model, n_tracks, L_max);
+    if (rc != MHT_OK) return rc;
+    const SmoothBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, xs, Ps};
+    return run_smooth<6>(ctx, "mht_smooth_tracks_ct", "mht_smooth_ct_work_bytes", ct_steps(model), true, b, smooth_rts_ct_kernel<true>,
+                         smooth_rts_ct_kernel<false>);
 }
 
 extern "C" size_t mht_smooth_ais_work_bytes(int32_t n_tracks, int32_t L_max) {
@@ -141,15 +124,10 @@ extern "C" int mht_smooth_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int
                                      const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, const uint8_t* kind,
                                      const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
                                      double* xs, double* Ps, void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_smooth_tracks_ais: null argument");
-    MHT_REQUIRE(model->nx == 4, "mht_smooth_tracks_ais: AIS messages report four states (got nx = %d)", model->nx);
-    MHT_REQUIRE(model->transition == 0, "mht_smooth_tracks_ais: a state-dependent transition (%d) has no AIS-aware smoother", model->transition);
-    MHT_REQUIRE(model->A && model->Q && model->C && model->R, "mht_smooth_tracks_ais: null model matrix");
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1 && n_legs >= 0, "mht_smooth_tracks_ais: bad size (n_tracks %d, L_max %d, n_legs %d)", n_tracks, L_max, n_legs);
-    AisSteps steps = {};
-    widen<4>(model, steps.model, steps.model.A);
-    steps.kind = kind; steps.ais_z = ais_z; steps.ais_r = ais_r; steps.leg = leg; steps.legs = legs;
-    const SmoothBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, xs, Ps, work, work_bytes};
-    return run_smooth<4>(ctx, "mht_smooth_tracks_ais", "mht_smooth_ais_work_bytes", steps, kind && ais_z && ais_r && leg && (legs || n_legs == 0), b,
-                         smooth_ais_kernel<true>, smooth_ais_kernel<false>);
+    const int rc = check_ais("mht_smooth_tracks_ais", ctx, model, n_tracks, L_max, n_legs);
+    if (rc != MHT_OK) return rc;
+    bool extras;
+    const AisSteps steps = ais_steps(model, kind, ais_z, ais_r, leg, legs, n_legs, &extras);
+    const SmoothBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, xs, Ps};
+    return run_smooth<4>(ctx, "mht_smooth_tracks_ais", "mht_smooth_ais_work_bytes", steps, extras, b, smooth_ais_kernel<true>, smooth_ais_kernel<false>);
 }

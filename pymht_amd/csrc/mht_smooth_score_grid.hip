@@ -28,17 +28,11 @@ static size_t score_grid_work_bytes(int32_t nx, int32_t n_tracks, int32_t n_cand
     return smooth_len_bytes(n_tracks) + score_grid_table_bytes(nx, n_cand);
 }
 
-struct ScoreGridBatch {      // what both seams are handed besides their model
-    int32_t n, L_max;
-    const int32_t* len;
-    const double *x_init, *P_init, *z;
-    const uint8_t* has_z;
+struct ScoreGridBatch : TrackBatch {
     int32_t n_cand;
     const double *Q_cand, *R_cand;
     double *ll, *nis;
     int32_t* nobs;
-    void* work;
-    size_t work_bytes;
 };
 
 // run_score (mht_smooth_score.hip) with the table behind the lengths: an empty batch is done; any other is checked, the lengths and
@@ -48,11 +42,9 @@ static int run_score_grid(mht_ctx* ctx, const char* seam, const Steps& steps, co
     constexpr int NS = N * (N + 1) / 2;
     MHT_REQUIRE(b.n_cand >= 1 && b.n_cand <= SCORE_GRID_MAX_CAND, "%s: n_cand must be 1 .. %d (got %d)", seam, SCORE_GRID_MAX_CAND, b.n_cand);
     if (b.n == 0) return MHT_OK;
-    MHT_REQUIRE(b.len && b.x_init && b.P_init && b.z && b.has_z && b.Q_cand && b.R_cand && b.ll && b.nis && b.nobs && b.work, "%s: null array", seam);
-    for (int32_t t = 0; t < b.n; ++t)
-        MHT_REQUIRE(b.len[t] >= 1 && b.len[t] <= b.L_max, "%s: track %d has length %d (1 .. L_max = %d)", seam, t, b.len[t], b.L_max);
-    const size_t need = score_grid_work_bytes(N, b.n, b.n_cand);
-    MHT_REQUIRE(b.work_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed (mht_score_grid_work_bytes)", seam, b.work_bytes, need);
+    const int rc = check_batch(seam, b, b.Q_cand && b.R_cand && b.ll && b.nis && b.nobs, score_grid_work_bytes(N, b.n, b.n_cand),
+                               "mht_score_grid_work_bytes", MHT_E_INVALID);
+    if (rc != MHT_OK) return rc;
     std::vector<double> table((size_t)b.n_cand * (NS + 3));
     for (int32_t g = 0; g < b.n_cand; ++g) {
         double* row = table.data() + (size_t)g * (NS + 3);
@@ -61,7 +53,6 @@ static int run_score_grid(mht_ctx* ctx, const char* seam, const Steps& steps, co
             for (int j = i; j < N; ++j) row[sym_idx(N, i, j)] = Q[i * N + j];
         row[NS] = R[0]; row[NS + 1] = R[1]; row[NS + 2] = R[3];
     }
-    MHT_HIP_CHECK(hipSetDevice(ctx->device));
     char* w = static_cast<char*>(b.work);
     ScoreGridArgs<N, Steps> a = {};
     a.s.steps = steps;
@@ -71,29 +62,9 @@ static int run_score_grid(mht_ctx* ctx, const char* seam, const Steps& steps, co
     a.s.ll = b.ll; a.s.nis = b.nis; a.s.nobs = b.nobs;
     a.cand = reinterpret_cast<const double*>(w + smooth_len_bytes(b.n));
     a.n_cand = b.n_cand;
-    int rc = MHT_OK;
-    // (the copies read the caller's array and `table`: whatever fails from here on, the stream is waited for before the error goes back)
-    hipError_t e = hipMemcpyAsync(w, b.len, (size_t)b.n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(w + smooth_len_bytes(b.n), table.data(), table.size() * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        set_error("%s: copying to the workspace: %s", seam, hipGetErrorString(e));
-        rc = MHT_E_HIP;
-    } else {
-        rc = launch_kernel(ctx, K_SMOOTH_SCORE, smooth_score_grid_kernel<N, Steps>, dim3((b.n + 63) / 64, b.n_cand), dim3(64), 0, false, a);
-    }
-    if (rc != MHT_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    MHT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHT_OK;
-}
-
-template <int N>
-static int run_score_grid_linear(mht_ctx* ctx, const mht_model_x* model, const ScoreGridBatch& b) {
-    LinearSteps<N> steps = {};
-    widen<N>(model, steps.model, steps.model.A);      // (Q and R too: every walk overwrites them with its candidate's)
-    return run_score_grid<N>(ctx, "mht_score_tracks_grid", steps, b);
+    return run_over_lengths(ctx, seam, b, table.data(), table.size(), [&] {
+        return launch_kernel(ctx, K_SMOOTH_SCORE, smooth_score_grid_kernel<N, Steps>, dim3((b.n + 63) / 64, b.n_cand), dim3(64), 0, false, a);
+    });
 }
 
 }  // namespace mht
@@ -105,33 +76,24 @@ extern "C" size_t mht_score_grid_work_bytes(int32_t nx, int32_t n_tracks, int32_
     return score_grid_work_bytes(nx, n_tracks, n_cand);
 }
 
+// (the steps carry the model's Q and R too: every walk overwrites them with its candidate's)
 extern "C" int mht_score_tracks_grid(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                                      const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_cand,
                                      const double* Q_cand, const double* R_cand, double* ll_out, double* nis_out, int32_t* nobs_out, void* work,
                                      size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_score_tracks_grid: null argument");
-    MHT_REQUIRE(model->nx == 4 || model->nx == 6, "mht_score_tracks_grid: nx must be 4 or 6 (got %d)", model->nx);
-    MHT_REQUIRE(model->transition == 0, "mht_score_tracks_grid: a state-dependent transition (%d) has no linear filter to score", model->transition);
-    MHT_REQUIRE(model->A && model->Q && model->C && model->R, "mht_score_tracks_grid: null model matrix");
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_score_tracks_grid: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
-    const ScoreGridBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, n_cand, Q_cand, R_cand, ll_out, nis_out, nobs_out, work, work_bytes};
-    return model->nx == 4 ? run_score_grid_linear<4>(ctx, model, b) : run_score_grid_linear<6>(ctx, model, b);
+    const char* seam = "mht_score_tracks_grid";
+    const int rc = check_linear(seam, ctx, model, n_tracks, L_max);
+    if (rc != MHT_OK) return rc;
+    const ScoreGridBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, n_cand, Q_cand, R_cand, ll_out, nis_out, nobs_out};
+    return model->nx == 4 ? run_score_grid<4>(ctx, seam, linear_steps<4>(model), b) : run_score_grid<6>(ctx, seam, linear_steps<6>(model), b);
 }
 
 extern "C" int mht_score_tracks_ct_grid(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                                         const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, int32_t n_cand,
                                         const double* Q_cand, const double* R_cand, double* ll_out, double* nis_out, int32_t* nobs_out,
                                         void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_score_tracks_ct_grid: null argument");
-    MHT_REQUIRE(model->nx == 6, "mht_score_tracks_ct_grid: the constant-turn model has 6 states (got nx = %d)", model->nx);
-    MHT_REQUIRE(model->transition == 1, "mht_score_tracks_ct_grid: transition must be 1 (got %d; a linear model belongs to mht_score_tracks_grid)",
-                model->transition);
-    MHT_REQUIRE(model->Q && model->C && model->R, "mht_score_tracks_ct_grid: null model matrix");
-    MHT_REQUIRE(model->period > 0.0, "mht_score_tracks_ct_grid: the model's period must be positive (got %g)", model->period);
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_score_tracks_ct_grid: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
-    ConstantTurnSteps steps = {};
-    widen<6>(model, steps.model);
-    steps.model.T = model->period;
-    const ScoreGridBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, n_cand, Q_cand, R_cand, ll_out, nis_out, nobs_out, work, work_bytes};
-    return run_score_grid<6>(ctx, "mht_score_tracks_ct_grid", steps, b);
+    const int rc = check_ct("mht_score_tracks_ct_grid", ctx, model, n_tracks, L_max);
+    if (rc != MHT_OK) return rc;
+    const ScoreGridBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, n_cand, Q_cand, R_cand, ll_out, nis_out, nobs_out};
+    return run_score_grid<6>(ctx, "mht_score_tracks_ct_grid", ct_steps(model), b);
 }

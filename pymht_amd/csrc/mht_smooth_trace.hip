@@ -1,8 +1,7 @@
 // mht_trace_tracks, mht_trace_tracks_ct, mht_trace_tracks_ais (include/mht_amd.h): the per-node innovation sequence of a batch of track
 // histories -- v_k, S_k, nis_k and ll_k at every node with a plot, and the same for every AIS message -- where mht_score_tracks*
-// (mht_smooth_score.hip) hands out their sums.  The fourth sibling next to smooth, EM and score: one walk (smooth_trace_walk,
-// mht_smooth_trace.h) with the smoothers' step policies, ONE TRACK PER LANE, everything in memory track-minor, no lane touching
-// anything of another -- a track's figures do not depend on where in the batch it sits.  The workspace holds the lengths and nothing
+// (mht_smooth_score.hip) hands out their sums.  One walk (smooth_trace_walk, mht_smooth_trace.h) with the smoothers' step policies; the
+// lanes and the layout are mht_smooth.hip's, the host path mht_smooth_seam.h's.  The workspace holds the lengths and nothing
 // else; the outputs are [node][element][track], so the 7 (16) stores a lane makes per node are contiguous over a wavefront, and a lane
 // writes EVERY row of its track, NaN where there is nothing to say: the caller's memory need not be initialised.  Like the score
 // kernels, nothing but (x, P), one prediction and one gain is live at a time, and the node's figures are stored in front of the gain:
@@ -23,47 +22,25 @@ __global__ void __launch_bounds__(64) smooth_trace_kernel(const TraceArgs<N, Ste
 
 static size_t trace_work_bytes(int32_t n_tracks) { return smooth_len_bytes(n_tracks); }      // the lengths
 
-struct TraceBatch {      // what every trace seam is handed besides its model
-    int32_t n, L_max;
-    const int32_t* len;
-    const double *x_init, *P_init, *z;
-    const uint8_t* has_z;
+struct TraceBatch : TrackBatch {
     double* radar;
-    void* work;
-    size_t work_bytes;
 };
 
 // An empty batch is done; any other is checked, then the lengths go to the workspace; then one launch and a wait
 template <int N, typename Steps>
 static int run_trace(mht_ctx* ctx, const char* seam, const Steps& steps, bool extras, const TraceBatch& b, double* ais) {
     if (b.n == 0) return MHT_OK;
-    MHT_REQUIRE(b.len && b.x_init && b.P_init && b.z && b.has_z && extras && b.radar && b.work, "%s: null array", seam);
-    for (int32_t t = 0; t < b.n; ++t)
-        MHT_REQUIRE(b.len[t] >= 1 && b.len[t] <= b.L_max, "%s: track %d has length %d (1 .. L_max = %d)", seam, t, b.len[t], b.L_max);
-    MHT_REQUIRE(b.work_bytes >= trace_work_bytes(b.n), "%s: the workspace has %zu bytes, %zu are needed (mht_trace_work_bytes)", seam, b.work_bytes,
-                trace_work_bytes(b.n));
-    MHT_HIP_CHECK(hipSetDevice(ctx->device));
+    const int rc = check_batch(seam, b, extras && b.radar, trace_work_bytes(b.n), "mht_trace_work_bytes", MHT_E_INVALID);
+    if (rc != MHT_OK) return rc;
     TraceArgs<N, Steps> a = {};
     a.steps = steps;
     a.n = b.n; a.L_max = b.L_max;
     a.len = static_cast<const int32_t*>(b.work);
     a.x_init = b.x_init; a.P_init = b.P_init; a.z = b.z; a.has_z = b.has_z;
     a.radar = b.radar; a.ais = ais;
-    MHT_HIP_CHECK(hipMemcpyAsync(b.work, b.len, (size_t)b.n * 4, hipMemcpyHostToDevice, ctx->stream));
-    const int rc = launch_kernel(ctx, K_SMOOTH_SCORE, smooth_trace_kernel<N, Steps>, dim3((b.n + 63) / 64), dim3(64), 0, false, a);
-    if (rc != MHT_OK) {      // (the copy of the lengths reads the caller's array: it is waited for before the error goes back)
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    MHT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHT_OK;
-}
-
-template <int N>
-static int run_trace_linear(mht_ctx* ctx, const mht_model_x* model, const TraceBatch& b) {
-    LinearSteps<N> steps = {};
-    widen<N>(model, steps.model, steps.model.A);
-    return run_trace<N>(ctx, "mht_trace_tracks", steps, true, b, nullptr);
+    return run_over_lengths(ctx, seam, b, nullptr, 0, [&] {
+        return launch_kernel(ctx, K_SMOOTH_SCORE, smooth_trace_kernel<N, Steps>, dim3((b.n + 63) / 64), dim3(64), 0, false, a);
+    });
 }
 
 }  // namespace mht
@@ -77,42 +54,30 @@ extern "C" size_t mht_trace_work_bytes(int32_t nx, int32_t n_tracks, int32_t L_m
 
 extern "C" int mht_trace_tracks(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len, const double* x_init,
                                 const double* P_init, const double* z, const uint8_t* has_z, double* radar_out, void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_trace_tracks: null argument");
-    MHT_REQUIRE(model->nx == 4 || model->nx == 6, "mht_trace_tracks: nx must be 4 or 6 (got %d)", model->nx);
-    MHT_REQUIRE(model->transition == 0, "mht_trace_tracks: a state-dependent transition (%d) has no linear filter to trace", model->transition);
-    MHT_REQUIRE(model->A && model->Q && model->C && model->R, "mht_trace_tracks: null model matrix");
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_trace_tracks: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
-    const TraceBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, radar_out, work, work_bytes};
-    return model->nx == 4 ? run_trace_linear<4>(ctx, model, b) : run_trace_linear<6>(ctx, model, b);
+    const char* seam = "mht_trace_tracks";
+    const int rc = check_linear(seam, ctx, model, n_tracks, L_max);
+    if (rc != MHT_OK) return rc;
+    const TraceBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, radar_out};
+    return model->nx == 4 ? run_trace<4>(ctx, seam, linear_steps<4>(model), true, b, nullptr)
+                          : run_trace<6>(ctx, seam, linear_steps<6>(model), true, b, nullptr);
 }
 
 extern "C" int mht_trace_tracks_ct(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len, const double* x_init,
                                    const double* P_init, const double* z, const uint8_t* has_z, double* radar_out, void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_trace_tracks_ct: null argument");
-    MHT_REQUIRE(model->nx == 6, "mht_trace_tracks_ct: the constant-turn model has 6 states (got nx = %d)", model->nx);
-    MHT_REQUIRE(model->transition == 1, "mht_trace_tracks_ct: transition must be 1 (got %d; a linear model belongs to mht_trace_tracks)", model->transition);
-    MHT_REQUIRE(model->Q && model->C && model->R, "mht_trace_tracks_ct: null model matrix");
-    MHT_REQUIRE(model->period > 0.0, "mht_trace_tracks_ct: the model's period must be positive (got %g)", model->period);
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1, "mht_trace_tracks_ct: bad size (n_tracks %d, L_max %d)", n_tracks, L_max);
-    ConstantTurnSteps steps = {};
-    widen<6>(model, steps.model);
-    steps.model.T = model->period;
-    const TraceBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, radar_out, work, work_bytes};
-    return run_trace<6>(ctx, "mht_trace_tracks_ct", steps, true, b, nullptr);
+    const int rc = check_ct("mht_trace_tracks_ct", ctx, model, n_tracks, L_max);
+    if (rc != MHT_OK) return rc;
+    const TraceBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, radar_out};
+    return run_trace<6>(ctx, "mht_trace_tracks_ct", ct_steps(model), true, b, nullptr);
 }
 
 extern "C" int mht_trace_tracks_ais(mht_ctx* ctx, const mht_model_x* model, int32_t n_tracks, int32_t L_max, const int32_t* len,
                                     const double* x_init, const double* P_init, const double* z, const uint8_t* has_z, const uint8_t* kind,
                                     const double* ais_z, const double* ais_r, const int32_t* leg, const double* legs, int32_t n_legs,
                                     double* radar_out, double* ais_out, void* work, size_t work_bytes) {
-    MHT_REQUIRE(ctx && model, "mht_trace_tracks_ais: null argument");
-    MHT_REQUIRE(model->nx == 4, "mht_trace_tracks_ais: AIS messages report four states (got nx = %d)", model->nx);
-    MHT_REQUIRE(model->transition == 0, "mht_trace_tracks_ais: a state-dependent transition (%d) has no AIS-aware filter to trace", model->transition);
-    MHT_REQUIRE(model->A && model->Q && model->C && model->R, "mht_trace_tracks_ais: null model matrix");
-    MHT_REQUIRE(n_tracks >= 0 && L_max >= 1 && n_legs >= 0, "mht_trace_tracks_ais: bad size (n_tracks %d, L_max %d, n_legs %d)", n_tracks, L_max, n_legs);
-    AisSteps steps = {};
-    widen<4>(model, steps.model, steps.model.A);
-    steps.kind = kind; steps.ais_z = ais_z; steps.ais_r = ais_r; steps.leg = leg; steps.legs = legs;
-    const TraceBatch b = {n_tracks, L_max, len, x_init, P_init, z, has_z, radar_out, work, work_bytes};
-    return run_trace<4>(ctx, "mht_trace_tracks_ais", steps, kind && ais_z && ais_r && leg && (legs || n_legs == 0) && ais_out, b, ais_out);
+    const int rc = check_ais("mht_trace_tracks_ais", ctx, model, n_tracks, L_max, n_legs);
+    if (rc != MHT_OK) return rc;
+    bool extras;
+    const AisSteps steps = ais_steps(model, kind, ais_z, ais_r, leg, legs, n_legs, &extras);
+    const TraceBatch b = {{n_tracks, L_max, len, x_init, P_init, z, has_z, work, work_bytes}, radar_out};
+    return run_trace<4>(ctx, "mht_trace_tracks_ais", steps, extras && ais_out, b, ais_out);
 }

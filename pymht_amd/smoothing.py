@@ -59,12 +59,29 @@ from . import _lib
 from .device import Context
 
 
-# model kind -> the seam, its workspace sizer, whether the sizer takes nx in front of (n_tracks, L_max); the AIS seam takes its per-node
-# arrays and the leg table between has_z and xs, the argument lists are the same otherwise
-_SEAMS = {"linear": ("mht_smooth_tracks", "mht_smooth_work_bytes", True),
-          "ct": ("mht_smooth_tracks_ct", "mht_smooth_ct_work_bytes", False),
-          "ais": ("mht_smooth_tracks_ais", "mht_smooth_ais_work_bytes", False),
-          "em": ("mht_smooth_tracks_em", "mht_smooth_em_work_bytes", True)}
+# (family, model kind) -> the seam, its workspace sizer, whether the sizer takes nx in front of (n_tracks, L_max), whether it takes the
+# number of modes / candidates behind them.  Every seam takes (ctx, model, n, L_max, len, x_init, P_init, z, has_z) first and
+# (work, work_bytes) behind its outputs; an AIS seam takes its per-node arrays and the leg table behind has_z (`_launch`).
+_SEAMS = {("smooth", "linear"): ("mht_smooth_tracks", "mht_smooth_work_bytes", True, False),
+          ("smooth", "ct"): ("mht_smooth_tracks_ct", "mht_smooth_ct_work_bytes", False, False),
+          ("smooth", "ais"): ("mht_smooth_tracks_ais", "mht_smooth_ais_work_bytes", False, False),
+          ("em", "linear"): ("mht_smooth_tracks_em", "mht_smooth_em_work_bytes", True, False),
+          ("em_ll", "linear"): ("mht_smooth_tracks_em_ll", "mht_smooth_em_work_bytes", True, False),
+          ("score", "linear"): ("mht_score_tracks", "mht_score_work_bytes", True, False),
+          ("score", "ct"): ("mht_score_tracks_ct", "mht_score_work_bytes", True, False),
+          ("score", "ais"): ("mht_score_tracks_ais", "mht_score_work_bytes", True, False),
+          ("score_grid", "linear"): ("mht_score_tracks_grid", "mht_score_grid_work_bytes", True, True),
+          ("score_grid", "ct"): ("mht_score_tracks_ct_grid", "mht_score_grid_work_bytes", True, True),
+          ("trace", "linear"): ("mht_trace_tracks", "mht_trace_work_bytes", True, False),
+          ("trace", "ct"): ("mht_trace_tracks_ct", "mht_trace_work_bytes", True, False),
+          ("trace", "ais"): ("mht_trace_tracks_ais", "mht_trace_work_bytes", True, False),
+          ("filter", "linear"): ("mht_filter_tracks", "mht_filter_work_bytes", True, False),
+          ("filter", "ct"): ("mht_filter_tracks_ct", "mht_filter_work_bytes", True, False),
+          ("filter", "ais"): ("mht_filter_tracks_ais", "mht_filter_work_bytes", True, False),
+          ("imm", "linear"): ("mht_imm_tracks", "mht_imm_work_bytes", True, True),
+          ("imm", "ct"): ("mht_imm_tracks_ct", "mht_imm_work_bytes", True, True),
+          ("imm_smooth", "linear"): ("mht_imm_smooth_tracks", "mht_imm_smooth_work_bytes", True, True),
+          ("imm_smooth", "ct"): ("mht_imm_smooth_tracks_ct", "mht_imm_smooth_work_bytes", True, True)}
 EM_MAX_ITER = 64      # (SMOOTH_EM_MAX_ITER of csrc/mht_smooth_em.h)
 
 
@@ -149,14 +166,14 @@ def smooth_tracks(model, radarPeriod, tracks, device=0, ctx=None, covariances=Tr
                  not used (what `Target.backtrackMeasurement()` returns can be handed in as it is).
     device, ctx  the GPU ordinal, or an existing pymht_amd.device.Context (a Tracker's) to run on
     Returns per track (xs [L, nx], Ps [L, nx, nx]) float64, Ps None with covariances=False (means only: the cheaper kernel)."""
-    return _smooth_on(ctx, device, model, radarPeriod, tracks, _check_model(model), covariances, False)
+    return _run(_smooth, [], ctx, device, model, radarPeriod, tracks, _check_model(model), "linear", covariances)
 
 
 def smooth_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None, covariances=True):
     """`smooth_tracks` for a constant-turn model (`model.transition == "ct"`: pymht_amd.models.ct; anything else raises ValueError): same
     arguments, same outputs with nx = 6.  A_k = Phi(T, w) at the filtered turn rate of node k, in float64 and not rounded to float32 as
     `model.Phi` returns it, no Jacobian with respect to w."""
-    return _smooth_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), covariances, True)
+    return _run(_smooth, [], ctx, device, model, radarPeriod, tracks, _check_ct_model(model), "ct", covariances)
 
 
 def smooth_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None, covariances=True):
@@ -165,9 +182,7 @@ def smooth_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None, covariance
     ais[k] None or (dT1, dT2, state [4], highAccuracy) for a node that took a message: made dT1 behind the node in front and dT2 in
     front of the node itself (both positive, else ValueError), reporting [x, y, vx, vy] with sigma 1 (highAccuracy) or 3.  Entry 0 is
     not used.  Same outputs as `smooth_tracks`; a batch without any message gives its numbers bit for bit."""
-    nx = _check_ais_model(model)
-    ais = _ais_inputs(model, tracks)
-    return _smooth_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, covariances, False, ais=ais)
+    return _run(_smooth, [], ctx, device, model, radarPeriod, tracks, _check_ais_model(model), "ais", covariances)
 
 
 def _check_em(n_iter, start):
@@ -195,17 +210,26 @@ def smooth_tracks_em(model, radarPeriod, tracks, n_iter=5, start="model", device
     nx = _check_model(model)
     if not isinstance(likelihoods, (bool, np.bool_)):
         raise TypeError("smoothing: likelihoods is a bool (got %r)" % (likelihoods,))
-    return _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, False, em=_check_em(n_iter, start), likelihoods=bool(likelihoods))
+    return _run(_smooth, [], ctx, device, model, radarPeriod, tracks, nx, "linear", covariances, em=_check_em(n_iter, start), likelihoods=bool(likelihoods))
 
 
-def _smooth_on(ctx, device, model, radarPeriod, tracks, nx, covariances, constant_turn, ais=None, em=None, likelihoods=False):
+_MODEL_CHECKS = {"linear": _check_model, "ct": _check_ct_model, "ais": _check_ais_model}      # each returns nx
+
+
+def _run(family, empty, ctx, device, model, radarPeriod, tracks, nx, kind, *args, **kwargs):
+    """family(ctx, model, period, tracks, nx, *args, constant_turn, ais, **kwargs) on the caller's context, or on one of this call's own
+    that is closed behind it.  The callers have checked the model (nx) and their own arguments; the AIS inputs are checked here, before a
+    device is needed; an empty batch gives `empty` without one."""
+    ais = None
+    if kind == "ais":
+        ais, tracks = _ais_inputs(model, tracks), [t[:3] for t in tracks]
     if len(tracks) == 0:
-        return []
+        return empty
     own = ctx is None
     if own:
         ctx = Context(device, nx=nx)
     try:
-        return _smooth(ctx, model, float(radarPeriod), tracks, nx, covariances, constant_turn, ais, em, likelihoods)
+        return family(ctx, model, float(radarPeriod), tracks, nx, *args, kind == "ct", ais, **kwargs)
     finally:
         if own:
             ctx.close()
@@ -276,65 +300,90 @@ def _model_x(model, period, nx, constant_turn, identity_start=False):
     return _lib.MhtModelX(nx, fp(keep[0]), fp(keep[1]), fp(keep[2]), fp(keep[3]), 0.0, 0.0, 1 if constant_turn else 0, period), keep
 
 
-def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None, em=None, likelihoods=False, on_device=False):
-    """on_device=True (internal: Tracker.getNees): nothing is downloaded -- (xs_d [L_max, nx, n], Ps_d [L_max, ns, n], lens, order, L_max),
-    the seam's outputs where they lie, packed column j holding track order[j]."""
-    n, ns = len(tracks), nx * (nx + 1) // 2
-    identity_start = em is not None and em[1] == "reference"
-    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx, identity_start)
-    dev = ctx.device
-    # (the smoothers leave the rows behind a track's end as they were, the filters write NaN there: handed on as they lie, the arrays
-    # start as NaN, so that both read the same and nothing of an earlier allocation shows through)
-    alloc = (lambda shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)) if on_device else (lambda shape: torch.empty(shape, dtype=torch.float64, device=dev))
-    xs_d = alloc((L_max, nx, n))
-    Ps_d = alloc((L_max, ns, n)) if covariances else None
-    lib, extra, trace = ctx.lib, (), ()
-    if ais is not None:
-        extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
-    if em is not None:      # n_iter in front of the outputs, the learned Q (packed) and R behind them
-        Q_d = torch.empty((ns, n), dtype=torch.float64, device=dev)
-        R_d = torch.empty((3, n), dtype=torch.float64, device=dev)
-    seam, sizer, sizer_takes_nx = _SEAMS["em" if em is not None else "ais" if ais is not None else "ct" if constant_turn else "linear"]
-    if likelihoods:      # the same call with the trace of log-likelihoods behind its arguments
-        seam = "mht_smooth_tracks_em_ll"
-        ll_d = torch.empty((em[0] + 1, n), dtype=torch.float64, device=dev)
-        trace = (ll_d.data_ptr(),)
-    need = int(getattr(lib, sizer)(*((nx,) if sizer_takes_nx else ()), n, L_max))
+def _launch(ctx, model, period, tracks, nx, constant_turn, family, ais, middle, make_outs, trailing=0, identity_start=False):
+    """One seam call over a batch: the batch packed and uploaded (`_pack`, `_pack_ais`), the workspace the seam's sizer asks for, the
+    model, and the call through `_lib.check`.  middle: the seam's arguments between the batch and its outputs (ints as they are, NumPy
+    arrays as host pointers; the first is the count of modes / candidates where the sizer takes one); make_outs(L_max): its output
+    tensors in the seam's order (None for one left out), the last `trailing` of them behind the workspace.  Everything the seam reads
+    lives here until it has returned (it synchronises).  Returns (lens, order, L_max, hp, outs)."""
+    n, dev, lib = len(tracks), ctx.device, ctx.lib
+    lens, order, L_max, hp, batch = _pack(ctx, tracks, nx, identity_start)
+    extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max) if ais is not None else ((), None)
+    outs = list(make_outs(L_max))
+    seam, sizer, takes_nx, takes_count = _SEAMS[family, "ais" if ais is not None else "ct" if constant_turn else "linear"]
+    need = int(getattr(lib, sizer)(*((nx,) if takes_nx else ()), n, L_max, *((middle[0],) if takes_count else ())))
     work = torch.empty(need, dtype=torch.uint8, device=dev)
     mx, keep = _model_x(model, period, nx, constant_turn, identity_start)
     lens_sorted = np.ascontiguousarray(lens[order])
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if isinstance(a, np.ndarray) else a.data_ptr() if isinstance(a, torch.Tensor) else a
+    outs_p = [ptr(o) for o in outs]
     torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                                  z_d.data_ptr(), h_d.data_ptr(), *extra, *(() if em is None else (em[0],)), xs_d.data_ptr(),
-                                  Ps_d.data_ptr() if covariances else None, *(() if em is None else (Q_d.data_ptr(), R_d.data_ptr())),
-                                  work.data_ptr(), need, *trace), lib)
+    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, ptr(lens_sorted), *(ptr(b) for b in batch), *extra, *(ptr(m) for m in middle),
+                                  *outs_p[:len(outs) - trailing], work.data_ptr(), need, *outs_p[len(outs) - trailing:]), lib)
+    return lens, order, L_max, hp, outs
+
+
+def _unpack_index(nx, dev):
+    """Per entry (i, j) of a full nx x nx matrix, row-major, its place in the packed upper triangle (sym_idx, csrc/mht_smooth_math.h)"""
+    return torch.tensor([min(i, j) * nx - min(i, j) * (min(i, j) - 1) // 2 + abs(i - j) for i in range(nx) for j in range(nx)], device=dev)
+
+
+def _per_track(rows_d, nx=None):
+    """A per-node device array [L_max, elements, n] on the host as [track][node][element]; with nx the elements are a packed upper
+    triangle, unpacked on the device to [track][node][nx, nx]"""
+    if nx is None:
+        return rows_d.permute(2, 0, 1).contiguous().cpu().numpy()
+    full = rows_d.index_select(1, _unpack_index(nx, rows_d.device)).permute(2, 0, 1).contiguous().cpu().numpy()
+    return full.reshape(full.shape[0], full.shape[1], nx, nx)
+
+
+def _full(packed, nx):
+    """Host: symmetric [.., nx, nx] from a packed upper triangle [.., nx (nx + 1) / 2], row by row"""
+    iu = np.triu_indices(nx)
+    full = np.empty(packed.shape[:-1] + (nx, nx))
+    full[..., iu[0], iu[1]] = packed
+    full[..., iu[1], iu[0]] = packed
+    return full
+
+
+def _back(order):
+    """back[t]: the packed column the callers' track t sits in"""
+    back = np.empty(len(order), dtype=np.int64)
+    back[order] = np.arange(len(order))
+    return back
+
+
+def _smooth(ctx, model, period, tracks, nx, covariances, constant_turn, ais=None, em=None, likelihoods=False, on_device=False):
+    """on_device=True (internal: Tracker.getNees): nothing is downloaded -- (xs_d [L_max, nx, n], Ps_d [L_max, ns, n], lens, order, L_max),
+    the seam's outputs where they lie, packed column j holding track order[j]."""
+    n, ns, dev = len(tracks), nx * (nx + 1) // 2, ctx.device
+    # (the smoothers leave the rows behind a track's end as they were, the filters write NaN there: handed on as they lie, the arrays
+    # start as NaN, so that both read the same and nothing of an earlier allocation shows through)
+    rows = (lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)) if on_device else (lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev))
+
+    def make_outs(L_max):      # xs, Ps; EM: the learned Q (packed) and R behind them, and the trace of log-likelihoods behind the workspace
+        outs = [rows(L_max, nx, n), rows(L_max, ns, n) if covariances else None]
+        if em is not None:
+            outs += [torch.empty((ns, n), dtype=torch.float64, device=dev), torch.empty((3, n), dtype=torch.float64, device=dev)]
+        return outs + ([torch.empty((em[0] + 1, n), dtype=torch.float64, device=dev)] if likelihoods else [])
+    family = "smooth" if em is None else "em_ll" if likelihoods else "em"
+    lens, order, L_max, hp, outs = _launch(ctx, model, period, tracks, nx, constant_turn, family, ais, () if em is None else (em[0],), make_outs,
+                                           trailing=1 if likelihoods else 0, identity_start=em is not None and em[1] == "reference")
     if on_device:
-        return xs_d, Ps_d, lens, order, L_max
-    xs = xs_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
-    Ps = None
-    if covariances:      # packed upper triangle -> full matrices, still on the device
-        idx = torch.tensor([min(i, j) * nx - min(i, j) * (min(i, j) - 1) // 2 + abs(i - j) for i in range(nx) for j in range(nx)], device=dev)
-        Ps = Ps_d.index_select(1, idx).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
-    learned = ()
+        return outs[0], outs[1], lens, order, L_max
+    xs = _per_track(outs[0])
+    Ps = _per_track(outs[1], nx) if covariances else None
     if em is not None:
-        iu = np.triu_indices(nx)
-        Qp, Rp = Q_d.permute(1, 0).contiguous().cpu().numpy(), R_d.permute(1, 0).contiguous().cpu().numpy()
-        Q = np.empty((n, nx, nx))
-        Q[:, iu[0], iu[1]] = Qp
-        Q[:, iu[1], iu[0]] = Qp
-        R = Rp[:, [0, 1, 1, 2]].reshape(n, 2, 2)
+        Q = _full(outs[2].permute(1, 0).contiguous().cpu().numpy(), nx)
+        R = outs[3].permute(1, 0).contiguous().cpu().numpy()[:, [0, 1, 1, 2]].reshape(n, 2, 2)
     if likelihoods:
-        ll = ll_d.permute(1, 0).contiguous().cpu().numpy()      # [track][n_iter + 1]
+        ll = outs[4].permute(1, 0).contiguous().cpu().numpy()      # [track][n_iter + 1]
     out = [None] * n
     for j, t in enumerate(order):
         L = int(lens[t])
-        if em is not None:
-            learned = (Q[j], R[j]) + ((ll[j],) if likelihoods else ())
+        learned = () if em is None else (Q[j], R[j]) + ((ll[j],) if likelihoods else ())
         out[t] = (xs[j, :L], Ps[j, :L] if covariances else None) + learned
     return out
-
-
-_SCORE_SEAMS = {"linear": "mht_score_tracks", "ct": "mht_score_tracks_ct", "ais": "mht_score_tracks_ais"}
 
 
 def score_tracks(model, radarPeriod, tracks, device=0, ctx=None):
@@ -345,12 +394,12 @@ def score_tracks(model, radarPeriod, tracks, device=0, ctx=None):
         logLikelihood = -1/2 sum (ln det S + v' S^-1 v + 2 ln 2 pi)
     Node 0 is the initial state and is not an observation -- pykalman's loglikelihood() counts one at time 0, so these are not its
     figures.  A track of one node, or one never detected, gives (0.0, 0.0, 0).  One forward-only device launch (`mht_score_tracks`)."""
-    return _score_on(ctx, device, model, radarPeriod, tracks, _check_model(model), False)
+    return _run(_score, [], ctx, device, model, radarPeriod, tracks, _check_model(model), "linear")
 
 
 def score_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None):
     """`score_tracks` under the constant-turn model `smooth_tracks_ct` smooths with (anything else raises ValueError)."""
-    return _score_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), True)
+    return _run(_score, [], ctx, device, model, radarPeriod, tracks, _check_ct_model(model), "ct")
 
 
 def score_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None):
@@ -358,40 +407,14 @@ def score_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None):
     (logLikelihood, nis, nObs, nisAis, nAis).  A node that took a message is scored at the message's time as well, v = m - xp,
     S = Pp + sigma^2 I4: its ln N(m; xp, S) goes into logLikelihood, v' S^-1 v into nisAis (chi-square with 4 nAis degrees of freedom);
     nis and nObs stay radar-only.  A batch without any message gives `score_tracks`' numbers bit for bit."""
-    nx = _check_ais_model(model)
-    ais = _ais_inputs(model, tracks)
-    return _score_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, False, ais=ais)
-
-
-def _score_on(ctx, device, model, radarPeriod, tracks, nx, constant_turn, ais=None):
-    if len(tracks) == 0:
-        return []
-    own = ctx is None
-    if own:
-        ctx = Context(device, nx=nx)
-    try:
-        return _score(ctx, model, float(radarPeriod), tracks, nx, constant_turn, ais)
-    finally:
-        if own:
-            ctx.close()
+    return _run(_score, [], ctx, device, model, radarPeriod, tracks, _check_ais_model(model), "ais")
 
 
 def _score(ctx, model, period, tracks, nx, constant_turn, ais=None):
-    n = len(tracks)
-    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
-    dev, lib, extra = ctx.device, ctx.lib, ()
-    outs = [torch.empty(n, dtype=dt, device=dev) for dt in (torch.float64, torch.float64, torch.int32)]
-    if ais is not None:
-        extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
-        outs += [torch.empty(n, dtype=dt, device=dev) for dt in (torch.float64, torch.int32)]
-    need = int(lib.mht_score_work_bytes(nx, n, L_max))
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    mx, keep = _model_x(model, period, nx, constant_turn)
-    lens_sorted = np.ascontiguousarray(lens[order])
-    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    seam = _SCORE_SEAMS["ais" if ais is not None else "ct" if constant_turn else "linear"]
-    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                                  z_d.data_ptr(), h_d.data_ptr(), *extra, *(o.data_ptr() for o in outs), work.data_ptr(), need), lib)
+    n, dev = len(tracks), ctx.device
+    dtypes = (torch.float64, torch.float64, torch.int32) + ((torch.float64, torch.int32) if ais is not None else ())
+    lens, order, L_max, hp, outs = _launch(ctx, model, period, tracks, nx, constant_turn, "score", ais, (),
+                                           lambda L_max: [torch.empty(n, dtype=dt, device=dev) for dt in dtypes])
     cols = [o.cpu().numpy() for o in outs]
     out = [None] * n
     for j, t in enumerate(order):
@@ -399,7 +422,6 @@ def _score(ctx, model, period, tracks, nx, constant_turn, ais=None):
     return out
 
 
-_TRACE_SEAMS = {"linear": "mht_trace_tracks", "ct": "mht_trace_tracks_ct", "ais": "mht_trace_tracks_ais"}
 TRACE_RADAR_DOUBLES, TRACE_AIS_DOUBLES = 7, 16      # (csrc/mht_smooth_trace.h)
 
 
@@ -413,12 +435,12 @@ def trace_tracks(model, radarPeriod, tracks, device=0, ctx=None):
     logLikelihood and nis there, and observed.sum() its nObs -- the sums say whether a model fits a track, the sequence says where it
     stops (a manoeuvre, a misassociated plot, a run of correlated innovations from a Q too small: `consistency`).  An observed node
     whose det S is not positive keeps v and S and has NaN in nis and ll.  One device launch (`mht_trace_tracks`)."""
-    return _trace_on(ctx, device, model, radarPeriod, tracks, _check_model(model), False)
+    return _run(_trace, [], ctx, device, model, radarPeriod, tracks, _check_model(model), "linear")
 
 
 def trace_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None):
     """`trace_tracks` under the constant-turn model `score_tracks_ct` scores with (anything else raises ValueError)."""
-    return _trace_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), True)
+    return _run(_trace, [], ctx, device, model, radarPeriod, tracks, _check_ct_model(model), "ct")
 
 
 def trace_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None):
@@ -427,22 +449,7 @@ def trace_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None):
         vAis [L, 4]    SAis [L, 4, 4]    nisAis [L]    llAis [L] = -1/2 (ln det S + nisAis + 4 ln 2 pi)    message [L] bool
     `score_tracks_ais`' logLikelihood is llAis and ll added up in node order, llAis in front of ll at a node with both; nisAis adds
     up to its nisAis.  A batch without any message gives `trace_tracks`' radar arrays bit for bit."""
-    nx = _check_ais_model(model)
-    ais = _ais_inputs(model, tracks)
-    return _trace_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, False, ais=ais)
-
-
-def _trace_on(ctx, device, model, radarPeriod, tracks, nx, constant_turn, ais=None):
-    if len(tracks) == 0:
-        return []
-    own = ctx is None
-    if own:
-        ctx = Context(device, nx=nx)
-    try:
-        return _trace(ctx, model, float(radarPeriod), tracks, nx, constant_turn, ais)
-    finally:
-        if own:
-            ctx.close()
+    return _run(_trace, [], ctx, device, model, radarPeriod, tracks, _check_ais_model(model), "ais")
 
 
 def _trace_dict(radar, observed, ais=None, message=None):
@@ -451,11 +458,7 @@ def _trace_dict(radar, observed, ais=None, message=None):
     out = {"v": radar[:, 0:2].copy(), "S": radar[:, [2, 3, 3, 4]].reshape(L, 2, 2), "nis": radar[:, 5].copy(), "ll": radar[:, 6].copy(),
            "observed": np.asarray(observed, dtype=bool).copy()}
     if ais is not None:
-        iu = np.triu_indices(4)
-        S = np.empty((L, 4, 4))
-        S[:, iu[0], iu[1]] = ais[:, 4:14]
-        S[:, iu[1], iu[0]] = ais[:, 4:14]
-        out.update({"vAis": ais[:, 0:4].copy(), "SAis": S, "nisAis": ais[:, 14].copy(), "llAis": ais[:, 15].copy(),
+        out.update({"vAis": ais[:, 0:4].copy(), "SAis": _full(ais[:, 4:14], 4), "nisAis": ais[:, 14].copy(), "llAis": ais[:, 15].copy(),
                     "message": np.asarray(message, dtype=bool).copy()})
     return out
 
@@ -467,22 +470,11 @@ def _blank_trace(L, ais=False):
 
 
 def _trace(ctx, model, period, tracks, nx, constant_turn, ais=None):
-    n = len(tracks)
-    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
-    dev, lib, extra = ctx.device, ctx.lib, ()
-    outs = [torch.empty((L_max, TRACE_RADAR_DOUBLES, n), dtype=torch.float64, device=dev)]
-    if ais is not None:
-        extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
-        outs.append(torch.empty((L_max, TRACE_AIS_DOUBLES, n), dtype=torch.float64, device=dev))
-    need = int(lib.mht_trace_work_bytes(nx, n, L_max))
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    mx, keep = _model_x(model, period, nx, constant_turn)
-    lens_sorted = np.ascontiguousarray(lens[order])
-    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    seam = _TRACE_SEAMS["ais" if ais is not None else "ct" if constant_turn else "linear"]
-    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                                  z_d.data_ptr(), h_d.data_ptr(), *extra, *(o.data_ptr() for o in outs), work.data_ptr(), need), lib)
-    rows = [o.permute(2, 0, 1).contiguous().cpu().numpy() for o in outs]      # [track][node][element]
+    n, dev = len(tracks), ctx.device
+    widths = (TRACE_RADAR_DOUBLES,) + ((TRACE_AIS_DOUBLES,) if ais is not None else ())
+    lens, order, L_max, hp, outs = _launch(ctx, model, period, tracks, nx, constant_turn, "trace", ais, (),
+                                           lambda L_max: [torch.empty((L_max, w, n), dtype=torch.float64, device=dev) for w in widths])
+    rows = [_per_track(o) for o in outs]
     out = [None] * n
     for j, t in enumerate(order):
         L = int(lens[t])
@@ -495,24 +487,10 @@ def trace_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fals
     """`trace_tracks` for many track nodes in one device call, built on `chain_inputs` / `chain_ais` like `score_nodes` (the same
     switches and refusals): per node the dict of its chain, with ais also the message arrays.  A chain of fewer than two nodes has
     nothing to explain: its rows are NaN and not observed."""
-    if ais is not None and constantTurn:
-        raise ValueError("smoothing: AIS-aware tracing is for 4-state linear models, not together with constantTurn")
-    trace = trace_tracks_ais if ais is not None else trace_tracks_ct if constantTurn else trace_tracks
-    (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
-    out, batch, where = [None] * len(nodes), [], []
-    for i, node in enumerate(nodes):
-        chain, inputs = chain_inputs(node, model.P0)
-        if len(chain) < 2:
-            out[i] = _blank_trace(len(chain), ais is not None)
-        else:
-            batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
-            where.append(i)
-    for i, res in zip(where, trace(model, radarPeriod, batch, device=device, ctx=ctx)):
-        out[i] = res
-    return out
-
-
-_FILTER_SEAMS = {"linear": "mht_filter_tracks", "ct": "mht_filter_tracks_ct", "ais": "mht_filter_tracks_ais"}
+    kind = _kind(constantTurn, ais, "tracing")
+    nx = _MODEL_CHECKS[kind](model)
+    out, where, batch = _chains(model, nodes, lambda chain, inputs: _blank_trace(len(chain), ais is not None), ais)
+    return _fill(out, where, _run(_trace, [], ctx, device, model, radarPeriod, batch, nx, kind))
 
 
 def filter_tracks(model, radarPeriod, tracks, device=0, ctx=None):
@@ -525,69 +503,32 @@ def filter_tracks(model, radarPeriod, tracks, device=0, ctx=None):
     for bit (a track's last row is the last row of its xs and Ps) and the states behind `score_tracks` and `trace_tracks`.  They are NOT
     the forest's own chains bit for bit: the forest filters in float32 (float64 for AIS-fused covariances) with tabulated gains.
     One device launch (`mht_filter_tracks`), no host fallback."""
-    return _filter_on(ctx, device, model, radarPeriod, tracks, _check_model(model), False)
+    return _run(_filter, [], ctx, device, model, radarPeriod, tracks, _check_model(model), "linear")
 
 
 def filter_tracks_ct(model, radarPeriod, tracks, device=0, ctx=None):
     """`filter_tracks` under the constant-turn model `smooth_tracks_ct` smooths with (anything else raises ValueError): nx = 6,
     A_k = Phi(T, w) at the filtered turn rate of the node in front, no Jacobian."""
-    return _filter_on(ctx, device, model, radarPeriod, tracks, _check_ct_model(model), True)
+    return _run(_filter, [], ctx, device, model, radarPeriod, tracks, _check_ct_model(model), "ct")
 
 
 def filter_tracks_ais(model, radarPeriod, tracks, device=0, ctx=None):
     """`filter_tracks` under the AIS-aware model of `smooth_tracks_ais`, same `tracks` and refusals.  The state handed out for a node
     that took a message is the one at the SCAN's time, behind both legs and the radar update; the state at the message's time is an
     intermediate.  A batch without any message gives `filter_tracks`' numbers bit for bit."""
-    nx = _check_ais_model(model)
-    ais = _ais_inputs(model, tracks)
-    return _filter_on(ctx, device, model, radarPeriod, [t[:3] for t in tracks], nx, False, ais=ais)
-
-
-def _filter_on(ctx, device, model, radarPeriod, tracks, nx, constant_turn, ais=None):
-    if len(tracks) == 0:
-        return []
-    own = ctx is None
-    if own:
-        ctx = Context(device, nx=nx)
-    try:
-        return _filter(ctx, model, float(radarPeriod), tracks, nx, constant_turn, ais)
-    finally:
-        if own:
-            ctx.close()
-
-
-def _unpack_index(nx, dev):
-    """Per entry (i, j) of a full nx x nx matrix, row-major, its place in the packed upper triangle (sym_idx, csrc/mht_smooth_math.h)"""
-    return torch.tensor([min(i, j) * nx - min(i, j) * (min(i, j) - 1) // 2 + abs(i - j) for i in range(nx) for j in range(nx)], device=dev)
+    return _run(_filter, [], ctx, device, model, radarPeriod, tracks, _check_ais_model(model), "ais")
 
 
 def _filter(ctx, model, period, tracks, nx, constant_turn, ais=None, on_device=False):
     """on_device=True (internal: Tracker.getNees): nothing is downloaded -- (xf_d [L_max, nx, n], Pf_d [L_max, ns, n], lens, order, L_max),
     the seam's outputs where they lie, packed column j holding track order[j]."""
-    n, ns = len(tracks), nx * (nx + 1) // 2
-    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
-    dev, lib, extra = ctx.device, ctx.lib, ()
-    xf_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
-    Pf_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev)
-    if ais is not None:
-        extra, ais_keep = _pack_ais(ctx, ais, order, hp, L_max)
-    need = int(lib.mht_filter_work_bytes(nx, n, L_max))
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    mx, keep = _model_x(model, period, nx, constant_turn)
-    lens_sorted = np.ascontiguousarray(lens[order])
-    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    seam = _FILTER_SEAMS["ais" if ais is not None else "ct" if constant_turn else "linear"]
-    _lib.check(getattr(lib, seam)(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(),
-                                  z_d.data_ptr(), h_d.data_ptr(), *extra, xf_d.data_ptr(), Pf_d.data_ptr(), work.data_ptr(), need), lib)
+    n, dev = len(tracks), ctx.device
+    lens, order, L_max, hp, (xf_d, Pf_d) = _launch(ctx, model, period, tracks, nx, constant_turn, "filter", ais, (), lambda L_max: [
+        torch.empty((L_max, w, n), dtype=torch.float64, device=dev) for w in (nx, nx * (nx + 1) // 2)])
     if on_device:
         return xf_d, Pf_d, lens, order, L_max
-    xf = xf_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][nx]
-    Pf = Pf_d.index_select(1, _unpack_index(nx, dev)).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
-    out = [None] * n
-    for j, t in enumerate(order):
-        L = int(lens[t])
-        out[t] = (xf[j, :L], Pf[j, :L])
-    return out
+    xf, Pf = _per_track(xf_d), _per_track(Pf_d, nx)
+    return [(xf[j, :lens[t]], Pf[j, :lens[t]]) for t, j in enumerate(_back(order))]
 
 
 def filter_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None):
@@ -595,24 +536,28 @@ def filter_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fal
     switches and refusals): per node (xf [L, nx], Pf [L, nx, nx]) of its chain -- the float64 filter of the smoothers and scores, run
     over the history with `model` from the chain's initial state, not the forest's float32 / float64 chains bit for bit.  A chain of
     fewer than two nodes was never filtered: its initial state and covariance, and no device is needed to say so."""
-    if ais is not None and constantTurn:
-        raise ValueError("smoothing: AIS-aware filtering is for 4-state linear models, not together with constantTurn")
-    run = filter_tracks_ais if ais is not None else filter_tracks_ct if constantTurn else filter_tracks
-    nx = (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
-    out, batch, where = [None] * len(nodes), [], []
-    for i, node in enumerate(nodes):
-        chain, inputs = chain_inputs(node, model.P0)
-        if len(chain) < 2:
-            out[i] = (inputs[0].reshape(1, nx).copy(), inputs[1].reshape(1, nx, nx).copy())
-        else:
-            batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
-            where.append(i)
-    for i, res in zip(where, run(model, radarPeriod, batch, device=device, ctx=ctx)):
-        out[i] = res
-    return out
+    kind = _kind(constantTurn, ais, "filtering")
+    nx = _MODEL_CHECKS[kind](model)
+    out, where, batch = _chains(model, nodes, lambda chain, inputs: (inputs[0].reshape(1, nx).copy(), inputs[1].reshape(1, nx, nx).copy()), ais)
+    return _fill(out, where, _run(_filter, [], ctx, device, model, radarPeriod, batch, nx, kind))
 
 
 IMM_MAX_MODES = 4      # (IMM_MAX_MODES of csrc/mht_imm.h)
+
+
+def _check_scales(q, r):
+    """The scales of `imm_modes` and `noise_grid`: flat float64 arrays of finite positive factors, at least one each, else ValueError"""
+    for name, sc in (("qScales", q), ("rScales", r)):
+        if sc.size == 0 or not (np.isfinite(sc).all() and (sc > 0).all()):
+            raise ValueError("smoothing: %s are finite positive factors, at least one (got %r)" % (name, sc.tolist()))
+    return q, r
+
+
+def _noise32(model, radarPeriod):
+    """(Q(T) [nx, nx], R_RADAR() [2, 2]) as the float32 matrices every seam is handed (`_model_x`), widened to float64"""
+    nx = int(np.asarray(model.C_RADAR).shape[1])
+    return (np.asarray(model.Q(float(radarPeriod)), dtype=np.float32).astype(np.float64).reshape(nx, nx),
+            np.asarray(model.R_RADAR(), dtype=np.float32).astype(np.float64).reshape(2, 2))
 
 
 def imm_modes(model, radarPeriod, qScales, rScales=None, stay=0.95):
@@ -622,17 +567,13 @@ def imm_modes(model, radarPeriod, qScales, rScales=None, stay=0.95):
     length otherwise).  Pi has `stay` on the diagonal and (1 - stay) / (r - 1) elsewhere ([[1.]] for one mode), mu0 is uniform.  Scales
     that are not finite and positive, too many of them, or a `stay` outside (0, 1] raise ValueError."""
     q = np.asarray(qScales, dtype=np.float64).reshape(-1)
-    r = np.ones_like(q) if rScales is None else np.asarray(rScales, dtype=np.float64).reshape(-1)
-    for name, sc in (("qScales", q), ("rScales", r)):
-        if sc.size == 0 or not (np.isfinite(sc).all() and (sc > 0).all()):
-            raise ValueError("smoothing: %s are finite positive factors, at least one (got %r)" % (name, sc.tolist()))
+    q, r = _check_scales(q, np.ones_like(q) if rScales is None else np.asarray(rScales, dtype=np.float64).reshape(-1))
     if len(q) > IMM_MAX_MODES or len(r) != len(q):
         raise ValueError("smoothing: 1 .. %d modes, a scale of Q and of R each (got %d and %d)" % (IMM_MAX_MODES, len(q), len(r)))
     if isinstance(stay, bool) or not isinstance(stay, (int, float, np.integer, np.floating)) or not 0.0 < float(stay) <= 1.0:
         raise ValueError("smoothing: stay is the probability of keeping a mode, in (0, 1] (got %r)" % (stay,))
-    nx, n = int(np.asarray(model.C_RADAR).shape[1]), len(q)
-    Q32 = np.asarray(model.Q(float(radarPeriod)), dtype=np.float32).astype(np.float64).reshape(nx, nx)
-    R32 = np.asarray(model.R_RADAR(), dtype=np.float32).astype(np.float64).reshape(2, 2)
+    n = len(q)
+    Q32, R32 = _noise32(model, radarPeriod)
     Pi = np.ones((1, 1)) if n == 1 else np.where(np.eye(n, dtype=bool), float(stay), (1.0 - float(stay)) / (n - 1))
     return q[:, None, None] * Q32, r[:, None, None] * R32, Pi, np.full(n, 1.0 / n)
 
@@ -667,58 +608,37 @@ def imm_tracks(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, ctx=Non
     `filter_tracks`' bits and ll, nObs `score_tracks`'.  A mode that is no covariance (det S not positive at some plot) makes that
     track's ll NaN, and no other's.  An empty list gives ([], shape (0,), shape (0,)).  One device launch (`mht_imm_tracks`), one
     (track, mode) per lane, no host fallback."""
-    return _imm_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_model(model), False)
+    return _imm_run(_imm, ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_model(model), "linear")
 
 
 def imm_tracks_ct(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, ctx=None):
     """`imm_tracks` under the constant-turn model `filter_tracks_ct` filters with (anything else raises ValueError): nx = 6, every mode's
     Phi(T, w) taken at the turn rate of its own mixed state."""
-    return _imm_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_ct_model(model), True)
+    return _imm_run(_imm, ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_ct_model(model), "ct")
 
 
-def _imm_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, nx, constant_turn):
-    Q, R, Pi, mu0 = _check_modes(Q, R, Pi, mu0, nx)
-    if len(tracks) == 0:
-        return [], np.zeros(0), np.zeros(0, dtype=np.int32)
-    own = ctx is None
-    if own:
-        ctx = Context(device, nx=nx)
-    try:
-        return _imm(ctx, model, float(radarPeriod), tracks, Q, R, Pi, mu0, nx, constant_turn)
-    finally:
-        if own:
-            ctx.close()
+def _imm_run(family, ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, nx, kind):
+    """`_run` behind the check of the modes, which an empty batch is held to as well"""
+    empty = [] if family is _imm_smooth else ([], np.zeros(0), np.zeros(0, dtype=np.int32))
+    return _run(family, empty, ctx, device, model, radarPeriod, tracks, nx, kind, *_check_modes(Q, R, Pi, mu0, nx))
 
 
-def _imm(ctx, model, period, tracks, Q, R, Pi, mu0, nx, constant_turn):
-    n, r, ns = len(tracks), len(Q), nx * (nx + 1) // 2
-    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
-    dev, lib = ctx.device, ctx.lib
-    mu_d = torch.empty((L_max, r, n), dtype=torch.float64, device=dev)
-    xo_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
-    Po_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev)
-    ll_d = torch.empty(n, dtype=torch.float64, device=dev)
-    nobs_d = torch.empty(n, dtype=torch.int32, device=dev)
-    need = int(lib.mht_imm_work_bytes(nx, n, L_max, r))
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    mx, keep = _model_x(model, period, nx, constant_turn)
-    lens_sorted = np.ascontiguousarray(lens[order])
-    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    seam = lib.mht_imm_tracks_ct if constant_turn else lib.mht_imm_tracks
-    hostp = lambda a: a.ctypes.data_as(C.c_void_p)
-    _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, hostp(lens_sorted), x_d.data_ptr(), P_d.data_ptr(), z_d.data_ptr(), h_d.data_ptr(), r,
-                    hostp(Q), hostp(R), hostp(Pi), hostp(mu0), mu_d.data_ptr(), xo_d.data_ptr(), Po_d.data_ptr(), ll_d.data_ptr(),
-                    nobs_d.data_ptr(), work.data_ptr(), need), lib)
-    mu = mu_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][mode]
-    xo = xo_d.permute(2, 0, 1).contiguous().cpu().numpy()
-    Po = Po_d.index_select(1, _unpack_index(nx, dev)).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
-    out = [None] * n
-    for j, t in enumerate(order):
-        L = int(lens[t])
-        out[t] = (mu[j, :L], xo[j, :L], Po[j, :L])
-    back = np.empty(n, dtype=np.int64)      # the callers' track t sits in packed column back[t]
-    back[order] = np.arange(n)
-    return out, ll_d.cpu().numpy()[back], nobs_d.cpu().numpy()[back]
+def _imm_launch(ctx, model, period, tracks, nx, constant_turn, family, modes, n_mu):
+    """An IMM seam over a batch: n_mu arrays of mode probabilities [L_max, r, n] around the combined state and covariance, then ll and
+    nObs.  Returns (lens, order, the mode probabilities [track][node][mode] each, x, P, ll, nObs), the last two in packed order."""
+    n, r, dev = len(tracks), len(modes[0]), ctx.device
+    rows = lambda L_max, w: torch.empty((L_max, w, n), dtype=torch.float64, device=dev)
+    lens, order, L_max, hp, outs = _launch(ctx, model, period, tracks, nx, constant_turn, family, None, (r,) + tuple(modes), lambda L_max: [
+        rows(L_max, r), rows(L_max, nx), rows(L_max, nx * (nx + 1) // 2)] + [rows(L_max, r)] * (n_mu - 1) + [
+        torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)])
+    mus = [_per_track(outs[0])] + [_per_track(o) for o in outs[3:-2]]
+    return lens, order, mus, _per_track(outs[1]), _per_track(outs[2], nx), outs[-2].cpu().numpy(), outs[-1].cpu().numpy()
+
+
+def _imm(ctx, model, period, tracks, nx, Q, R, Pi, mu0, constant_turn, ais=None):
+    lens, order, (mu,), xo, Po, ll, nobs = _imm_launch(ctx, model, period, tracks, nx, constant_turn, "imm", (Q, R, Pi, mu0), 1)
+    back = _back(order)
+    return [(mu[j, :lens[t]], xo[j, :lens[t]], Po[j, :lens[t]]) for t, j in enumerate(back)], ll[back], nobs[back]
 
 
 def imm_nodes(model, radarPeriod, nodes, Q, R, Pi, mu0=None, device=0, ctx=None, constantTurn=False):
@@ -726,22 +646,15 @@ def imm_nodes(model, radarPeriod, nodes, Q, R, Pi, mu0=None, device=0, ctx=None,
     P [L, nx, nx]) of its chain, ll [n], nObs [n]).  A chain of fewer than two nodes was never filtered: mu0, its initial state and
     covariance, ll = 0.0, nObs = 0, and no device is needed to say so.  constantTurn as for `filter_nodes`; the messages of an AIS-aided
     tracker are not taken (there is no AIS-aware IMM)."""
-    run = imm_tracks_ct if constantTurn else imm_tracks
-    nx = (_check_ct_model if constantTurn else _check_model)(model)
+    kind = _kind(constantTurn)
+    nx = _MODEL_CHECKS[kind](model)
     Q, R, Pi, mu0 = _check_modes(Q, R, Pi, mu0, nx)
-    out, batch, where = [None] * len(nodes), [], []
+    out, where, batch = _chains(model, nodes, lambda chain, inputs: (mu0.reshape(1, -1).copy(), inputs[0].reshape(1, nx).copy(),
+                                                                     inputs[1].reshape(1, nx, nx).copy()))
     ll, nobs = np.zeros(len(nodes)), np.zeros(len(nodes), dtype=np.int32)
-    for i, node in enumerate(nodes):
-        chain, inputs = chain_inputs(node, model.P0)
-        if len(chain) < 2:
-            out[i] = (mu0.reshape(1, -1).copy(), inputs[0].reshape(1, nx).copy(), inputs[1].reshape(1, nx, nx).copy())
-        else:
-            batch.append(inputs)
-            where.append(i)
-    res, ll[where], nobs[where] = run(model, radarPeriod, batch, Q, R, Pi, mu0, device=device, ctx=ctx)
-    for i, one in zip(where, res):
-        out[i] = one
-    return out, ll, nobs
+    res, ll[where], nobs[where] = _imm_run(_imm, ctx, device, model, radarPeriod, batch, Q, R, Pi, mu0,
+                                           nx, kind)
+    return _fill(out, where, res), ll, nobs
 
 
 def imm_smooth_tracks(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, ctx=None):
@@ -755,80 +668,32 @@ def imm_smooth_tracks(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, 
         takes them as they are --, logLikelihood and nObs as `imm_tracks` gives them (its bits).
     At a track's last node mu, x, P are `imm_tracks`' bits.  With one mode (Pi = [[1.]]) x and P are `smooth_tracks`' bits and mu is
     exactly 1.  An empty list gives [].  One device launch (`mht_imm_smooth_tracks`), one (track, mode) per lane, no host fallback."""
-    return _imm_smooth_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_model(model), False)
+    return _imm_run(_imm_smooth, ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_model(model), "linear")
 
 
 def imm_smooth_tracks_ct(model, radarPeriod, tracks, Q, R, Pi, mu0=None, device=0, ctx=None):
     """`imm_smooth_tracks` under the constant-turn model `smooth_tracks_ct` smooths with (anything else raises ValueError): nx = 6, going
     backward every mode's Phi(T, w) is taken at the turn rate of its own filtered state."""
-    return _imm_smooth_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_ct_model(model), True)
+    return _imm_run(_imm_smooth, ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, _check_ct_model(model), "ct")
 
 
-def _imm_smooth_on(ctx, device, model, radarPeriod, tracks, Q, R, Pi, mu0, nx, constant_turn):
-    Q, R, Pi, mu0 = _check_modes(Q, R, Pi, mu0, nx)
-    if len(tracks) == 0:
-        return []
-    own = ctx is None
-    if own:
-        ctx = Context(device, nx=nx)
-    try:
-        return _imm_smooth(ctx, model, float(radarPeriod), tracks, Q, R, Pi, mu0, nx, constant_turn)
-    finally:
-        if own:
-            ctx.close()
-
-
-def _imm_smooth(ctx, model, period, tracks, Q, R, Pi, mu0, nx, constant_turn):
-    n, r, ns = len(tracks), len(Q), nx * (nx + 1) // 2
-    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
-    dev, lib = ctx.device, ctx.lib
-    mus_d = torch.empty((L_max, r, n), dtype=torch.float64, device=dev)
-    muf_d = torch.empty((L_max, r, n), dtype=torch.float64, device=dev)
-    xo_d = torch.empty((L_max, nx, n), dtype=torch.float64, device=dev)
-    Po_d = torch.empty((L_max, ns, n), dtype=torch.float64, device=dev)
-    ll_d = torch.empty(n, dtype=torch.float64, device=dev)
-    nobs_d = torch.empty(n, dtype=torch.int32, device=dev)
-    need = int(lib.mht_imm_smooth_work_bytes(nx, n, L_max, r))
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    mx, keep = _model_x(model, period, nx, constant_turn)
-    lens_sorted = np.ascontiguousarray(lens[order])
-    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    seam = lib.mht_imm_smooth_tracks_ct if constant_turn else lib.mht_imm_smooth_tracks
-    hostp = lambda a: a.ctypes.data_as(C.c_void_p)
-    _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, hostp(lens_sorted), x_d.data_ptr(), P_d.data_ptr(), z_d.data_ptr(), h_d.data_ptr(), r,
-                    hostp(Q), hostp(R), hostp(Pi), hostp(mu0), mus_d.data_ptr(), xo_d.data_ptr(), Po_d.data_ptr(), muf_d.data_ptr(),
-                    ll_d.data_ptr(), nobs_d.data_ptr(), work.data_ptr(), need), lib)
-    mus = mus_d.permute(2, 0, 1).contiguous().cpu().numpy()      # [track][node][mode]
-    muf = muf_d.permute(2, 0, 1).contiguous().cpu().numpy()
-    xo = xo_d.permute(2, 0, 1).contiguous().cpu().numpy()
-    Po = Po_d.index_select(1, _unpack_index(nx, dev)).permute(2, 0, 1).contiguous().cpu().numpy().reshape(n, L_max, nx, nx)
-    ll, nobs = ll_d.cpu().numpy(), nobs_d.cpu().numpy()
-    out = [None] * n
-    for j, t in enumerate(order):
-        L = int(lens[t])
-        out[t] = dict(mu=mus[j, :L], muFiltered=muf[j, :L], x=xo[j, :L], P=Po[j, :L], logLikelihood=float(ll[j]), nObs=int(nobs[j]))
-    return out
+def _imm_smooth(ctx, model, period, tracks, nx, Q, R, Pi, mu0, constant_turn, ais=None):
+    lens, order, (mus, muf), xo, Po, ll, nobs = _imm_launch(ctx, model, period, tracks, nx, constant_turn, "imm_smooth", (Q, R, Pi, mu0), 2)
+    return [dict(mu=mus[j, :lens[t]], muFiltered=muf[j, :lens[t]], x=xo[j, :lens[t]], P=Po[j, :lens[t]], logLikelihood=float(ll[j]), nObs=int(nobs[j]))
+            for t, j in enumerate(_back(order))]
 
 
 def imm_smooth_nodes(model, radarPeriod, nodes, Q, R, Pi, mu0=None, device=0, ctx=None, constantTurn=False):
     """`imm_smooth_tracks` for many track nodes in one device call, built on `chain_inputs` like `imm_nodes`: one dict per node.  A chain
     of fewer than two nodes was never filtered: mu0 twice, its initial state and covariance, logLikelihood 0.0, nObs 0, and no device
     is needed to say so.  constantTurn as for `imm_nodes`; AIS messages are not taken."""
-    run = imm_smooth_tracks_ct if constantTurn else imm_smooth_tracks
-    nx = (_check_ct_model if constantTurn else _check_model)(model)
+    kind = _kind(constantTurn)
+    nx = _MODEL_CHECKS[kind](model)
     Q, R, Pi, mu0 = _check_modes(Q, R, Pi, mu0, nx)
-    out, batch, where = [None] * len(nodes), [], []
-    for i, node in enumerate(nodes):
-        chain, inputs = chain_inputs(node, model.P0)
-        if len(chain) < 2:
-            out[i] = dict(mu=mu0.reshape(1, -1).copy(), muFiltered=mu0.reshape(1, -1).copy(), x=inputs[0].reshape(1, nx).copy(),
-                          P=inputs[1].reshape(1, nx, nx).copy(), logLikelihood=0.0, nObs=0)
-        else:
-            batch.append(inputs)
-            where.append(i)
-    for i, one in zip(where, run(model, radarPeriod, batch, Q, R, Pi, mu0, device=device, ctx=ctx)):
-        out[i] = one
-    return out
+    out, where, batch = _chains(model, nodes, lambda chain, inputs: dict(
+        mu=mu0.reshape(1, -1).copy(), muFiltered=mu0.reshape(1, -1).copy(), x=inputs[0].reshape(1, nx).copy(), P=inputs[1].reshape(1, nx, nx).copy(),
+        logLikelihood=0.0, nObs=0))
+    return _fill(out, where, _imm_run(_imm_smooth, ctx, device, model, radarPeriod, batch, Q, R, Pi, mu0, nx, kind))
 
 
 def consistency(traces, alpha=0.05):
@@ -904,13 +769,8 @@ def noise_grid(model, radarPeriod, qScales, rScales):
     G = len(qScales) * len(rScales), candidate iq * len(rScales) + ir being qScales[iq] * Q32 and rScales[ir] * R32 -- Q32 = Q(T) and
     R32 = R_RADAR() as float32, the matrices every seam is handed (`_model_x`), so that scale 1 is the tracker's model itself.  The
     products are float64: the grid is not rounded to float32.  Scales are finite and positive, else ValueError."""
-    q, r = (np.asarray(s, dtype=np.float64).reshape(-1) for s in (qScales, rScales))
-    for name, s in (("qScales", q), ("rScales", r)):
-        if s.size == 0 or not (np.isfinite(s).all() and (s > 0).all()):
-            raise ValueError("smoothing: %s are finite positive factors, at least one (got %r)" % (name, s.tolist()))
-    nx = int(np.asarray(model.C_RADAR).shape[1])
-    Q32 = np.asarray(model.Q(float(radarPeriod)), dtype=np.float32).astype(np.float64).reshape(nx, nx)
-    R32 = np.asarray(model.R_RADAR(), dtype=np.float32).astype(np.float64).reshape(2, 2)
+    q, r = _check_scales(*(np.asarray(s, dtype=np.float64).reshape(-1) for s in (qScales, rScales)))
+    Q32, R32 = _noise32(model, radarPeriod)
     Q = np.repeat(q, len(r))[:, None, None] * Q32
     R = np.tile(r, len(q))[:, None, None] * R32
     return Q, R
@@ -938,45 +798,27 @@ def score_tracks_grid(model, radarPeriod, tracks, Q, R, device=0, ctx=None):
     what `score_tracks` gives for a model that carries candidate g -- bit for bit where the candidate is representable in float32, the
     precision a model's matrices are handed over in; the candidates themselves are not rounded.  A candidate that is no covariance
     (det S not positive at some plot) gives NaN in its (candidate, track) cells only.  An empty list gives shapes (G, 0), (G, 0), (0,)."""
-    return _score_grid_on(ctx, device, model, radarPeriod, tracks, Q, R, _check_model(model), False)
+    return _score_grid_run(ctx, device, model, radarPeriod, tracks, Q, R, _check_model(model), "linear")
 
 
 def score_tracks_ct_grid(model, radarPeriod, tracks, Q, R, device=0, ctx=None):
     """`score_tracks_grid` under the constant-turn model `score_tracks_ct` scores with (anything else raises ValueError)."""
-    return _score_grid_on(ctx, device, model, radarPeriod, tracks, Q, R, _check_ct_model(model), True)
+    return _score_grid_run(ctx, device, model, radarPeriod, tracks, Q, R, _check_ct_model(model), "ct")
 
 
-def _score_grid_on(ctx, device, model, radarPeriod, tracks, Q, R, nx, constant_turn):
+def _score_grid_run(ctx, device, model, radarPeriod, tracks, Q, R, nx, kind):
+    """`_run` behind the check of the candidates, which an empty batch is held to as well"""
     Q, R = _check_candidates(Q, R, nx)
-    if len(tracks) == 0:
-        return np.zeros((len(Q), 0)), np.zeros((len(Q), 0)), np.zeros(0, dtype=np.int32)
-    own = ctx is None
-    if own:
-        ctx = Context(device, nx=nx)
-    try:
-        return _score_grid(ctx, model, float(radarPeriod), tracks, Q, R, nx, constant_turn)
-    finally:
-        if own:
-            ctx.close()
+    empty = np.zeros((len(Q), 0)), np.zeros((len(Q), 0)), np.zeros(0, dtype=np.int32)
+    return _run(_score_grid, empty, ctx, device, model, radarPeriod, tracks, nx, kind, Q, R)
 
 
-def _score_grid(ctx, model, period, tracks, Q, R, nx, constant_turn):
-    n, G = len(tracks), len(Q)
-    lens, order, L_max, hp, (x_d, P_d, z_d, h_d) = _pack(ctx, tracks, nx)
-    dev, lib = ctx.device, ctx.lib
-    ll_d, nis_d = (torch.empty((G, n), dtype=torch.float64, device=dev) for _ in range(2))
-    nobs_d = torch.empty(n, dtype=torch.int32, device=dev)
-    need = int(lib.mht_score_grid_work_bytes(nx, n, L_max, G))
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    mx, keep = _model_x(model, period, nx, constant_turn)
-    lens_sorted = np.ascontiguousarray(lens[order])
-    torch.cuda.current_stream(dev).synchronize()      # (the packing above ran on torch's stream)
-    seam = lib.mht_score_tracks_ct_grid if constant_turn else lib.mht_score_tracks_grid
-    _lib.check(seam(ctx.handle, C.byref(mx), n, L_max, lens_sorted.ctypes.data_as(C.c_void_p), x_d.data_ptr(), P_d.data_ptr(), z_d.data_ptr(),
-                    h_d.data_ptr(), G, Q.ctypes.data_as(C.c_void_p), R.ctypes.data_as(C.c_void_p), ll_d.data_ptr(), nis_d.data_ptr(),
-                    nobs_d.data_ptr(), work.data_ptr(), need), lib)
-    back = np.empty(n, dtype=np.int64)      # the callers' track t sits in packed column back[t]
-    back[order] = np.arange(n)
+def _score_grid(ctx, model, period, tracks, nx, Q, R, constant_turn, ais=None):
+    n, G, dev = len(tracks), len(Q), ctx.device
+    lens, order, L_max, hp, (ll_d, nis_d, nobs_d) = _launch(ctx, model, period, tracks, nx, constant_turn, "score_grid", None, (G, Q, R), lambda L_max: [
+        torch.empty((G, n), dtype=torch.float64, device=dev), torch.empty((G, n), dtype=torch.float64, device=dev),
+        torch.empty(n, dtype=torch.int32, device=dev)])
+    back = _back(order)
     return ll_d.cpu().numpy()[:, back], nis_d.cpu().numpy()[:, back], nobs_d.cpu().numpy()[back]
 
 
@@ -1007,6 +849,34 @@ def chain_ais(chain, lookup):
     return ais
 
 
+def _kind(constantTurn, ais=None, verb=None):
+    """The model kind behind a *_nodes function's switches; the AIS look-up and constantTurn together are refused"""
+    if ais is not None and constantTurn:
+        raise ValueError("smoothing: AIS-aware %s is for 4-state linear models, not together with constantTurn" % verb)
+    return "ais" if ais is not None else "ct" if constantTurn else "linear"
+
+
+def _chains(model, nodes, short, lookup=None):
+    """The chain loop of the *_nodes functions: (out, where, batch) -- out[i] = short(chain, inputs) for a chain of fewer than two
+    nodes, which no device is needed for; the `chain_inputs` of every other node i in `batch` (with `chain_ais` behind them under an AIS
+    look-up) and i in `where`"""
+    out, batch, where = [None] * len(nodes), [], []
+    for i, node in enumerate(nodes):
+        chain, inputs = chain_inputs(node, model.P0)
+        if len(chain) < 2:
+            out[i] = short(chain, inputs)
+        else:
+            batch.append(inputs if lookup is None else inputs + (chain_ais(chain, lookup),))
+            where.append(i)
+    return out, where, batch
+
+
+def _fill(out, where, results):
+    for i, res in zip(where, results):
+        out[i] = res
+    return out
+
+
 def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None, em=0, emStart="model"):
     """`Target.getSmoothTrack` for many track nodes in one device call: per node (positions [L, 2], velocities [L, 2], ok) as the
     reference returns them.  A chain of fewer than two nodes has nothing to smooth: its measurements, NaN velocities and False.
@@ -1016,48 +886,28 @@ def smooth_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=Fal
     `smooth_tracks_ais` with the messages their nodes took (`chain_ais`).  Not together with constantTurn (ValueError).
     em > 0: the chains go through `smooth_tracks_em(n_iter=em, start=emStart)`; not together with constantTurn or ais (ValueError before
     anything runs).  ok is then False as well for a track whose output is not finite."""
-    if ais is not None and constantTurn:
-        raise ValueError("smoothing: AIS-aware smoothing is for 4-state linear models, not together with constantTurn")
+    kind = _kind(constantTurn, ais, "smoothing")
     n_iter, emStart = _check_em(em, emStart)
-    if n_iter > 0 and (ais is not None or constantTurn):
+    if n_iter > 0 and kind != "linear":
         raise ValueError("smoothing: em learns the noise of the plain linear model, not together with constantTurn or ais")
-    smooth = smooth_tracks_ais if ais is not None else smooth_tracks_ct if constantTurn else smooth_tracks
-    if n_iter > 0:
-        smooth = lambda *a, **kw: smooth_tracks_em(*a, n_iter=n_iter, start=emStart, **kw)
-    (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
-    out, batch, where = [None] * len(nodes), [], []
-    for i, node in enumerate(nodes):
-        chain, inputs = chain_inputs(node, model.P0)
-        if len(chain) < 2:
-            pos = _measurement_array(inputs[2])
-            out[i] = (pos, np.full_like(pos, np.nan), False)
-        else:
-            batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
-            where.append(i)
-    for i, (xs, *_) in zip(where, smooth(model, radarPeriod, batch, device=device, ctx=ctx, covariances=False)):
-        out[i] = (xs[:, 0:2], xs[:, 2:4], n_iter == 0 or bool(np.isfinite(xs).all()))
-    return out
+    nx = _MODEL_CHECKS[kind](model)
+
+    def unsmoothed(chain, inputs):
+        pos = _measurement_array(inputs[2])
+        return pos, np.full_like(pos, np.nan), False
+    out, where, batch = _chains(model, nodes, unsmoothed, ais)
+    res = _run(_smooth, [], ctx, device, model, radarPeriod, batch, nx, kind, False, em=(n_iter, emStart) if n_iter > 0 else None)
+    return _fill(out, where, [(xs[:, 0:2], xs[:, 2:4], n_iter == 0 or bool(np.isfinite(xs).all())) for xs, *_ in res])
 
 
 def score_nodes(model, radarPeriod, nodes, device=0, ctx=None, constantTurn=False, ais=None):
     """`score_tracks` for many track nodes in one device call, built on `chain_inputs` / `chain_ais` like `smooth_nodes` (the same
     switches and refusals): per node (logLikelihood, nis, nObs), with ais also (.., nisAis, nAis).  A chain of fewer than two nodes has
     nothing to explain: (0.0, 0.0, 0)."""
-    if ais is not None and constantTurn:
-        raise ValueError("smoothing: AIS-aware scoring is for 4-state linear models, not together with constantTurn")
-    score = score_tracks_ais if ais is not None else score_tracks_ct if constantTurn else score_tracks
-    (_check_ais_model if ais is not None else _check_ct_model if constantTurn else _check_model)(model)
-    out, batch, where = [None] * len(nodes), [], []
-    for i, node in enumerate(nodes):
-        chain, inputs = chain_inputs(node, model.P0)
-        if len(chain) < 2:
-            out[i] = (0.0, 0.0, 0) + ((0.0, 0) if ais is not None else ())
-        else:
-            batch.append(inputs if ais is None else inputs + (chain_ais(chain, ais),))
-            where.append(i)
-    for i, res in zip(where, score(model, radarPeriod, batch, device=device, ctx=ctx)):
-        out[i] = res
-    return out
+    kind = _kind(constantTurn, ais, "scoring")
+    nx = _MODEL_CHECKS[kind](model)
+    out, where, batch = _chains(model, nodes, lambda chain, inputs: (0.0, 0.0, 0) + ((0.0, 0) if ais is not None else ()), ais)
+    return _fill(out, where, _run(_score, [], ctx, device, model, radarPeriod, batch, nx, kind))
 
 
 def best_cell(ll):
@@ -1074,15 +924,10 @@ def score_nodes_grid(model, radarPeriod, nodes, Q, R, device=0, ctx=None, consta
     """`score_tracks_grid` for many track nodes in one device call, built on `chain_inputs` like `score_nodes`: (ll [G, n], nis [G, n],
     nObs [n]) with a column per node.  A chain of fewer than two nodes has nothing to explain: zeros in its column.  constantTurn as
     for `score_nodes`; the messages of an AIS-aided tracker are not scored (the grid has no AIS model)."""
-    score = score_tracks_ct_grid if constantTurn else score_tracks_grid
-    nx = (_check_ct_model if constantTurn else _check_model)(model)
+    kind = _kind(constantTurn)
+    nx = _MODEL_CHECKS[kind](model)
     Q, R = _check_candidates(Q, R, nx)
-    batch, where = [], []
-    for i, node in enumerate(nodes):
-        chain, inputs = chain_inputs(node, model.P0)
-        if len(chain) >= 2:
-            batch.append(inputs)
-            where.append(i)
+    out, where, batch = _chains(model, nodes, lambda chain, inputs: None)
     ll, nis, nobs = np.zeros((len(Q), len(nodes))), np.zeros((len(Q), len(nodes))), np.zeros(len(nodes), dtype=np.int32)
-    ll[:, where], nis[:, where], nobs[where] = score(model, radarPeriod, batch, Q, R, device=device, ctx=ctx)
+    ll[:, where], nis[:, where], nobs[where] = _score_grid_run(ctx, device, model, radarPeriod, batch, Q, R, nx, kind)
     return ll, nis, nobs

@@ -186,6 +186,132 @@ def test_raw_abi_error_codes_leave_the_outputs_untouched(ctxs, lib_nx):
     assert not (got[:, :, 0] == -7.0).any() and (got[2:, :, 1] == -7.0).all() and not (got[:2, :, 1] == -7.0).any() and (got[1:, :, 2] == -7.0).all()
 
 
+# What every track seam of pymht_amd.smoothing._SEAMS returns for the six bad calls of the sweep below -- a null model, nx = 5, the other
+# kind's transition, a length 0 and a length L + 1 in the middle track, a workspace one byte short -- as read off the library in front
+# of the change that gave the seams one host path: -1 is MHT_E_INVALID, -3 MHT_E_CAPACITY, which only the smoothers return, and only for
+# the workspace (mht_smooth_tracks_em* document MHT_E_INVALID for theirs, include/mht_amd.h).
+SWEEP_CASES = ("null model", "nx", "transition", "length 0", "length L + 1", "workspace")
+SWEEP_CODES = {
+    "mht_smooth_tracks": (-1, -1, -1, -1, -1, -3), "mht_smooth_tracks_ct": (-1, -1, -1, -1, -1, -3), "mht_smooth_tracks_ais": (-1, -1, -1, -1, -1, -3),
+    "mht_smooth_tracks_em": (-1, -1, -1, -1, -1, -1), "mht_smooth_tracks_em_ll": (-1, -1, -1, -1, -1, -1),
+    "mht_score_tracks": (-1, -1, -1, -1, -1, -1), "mht_score_tracks_ct": (-1, -1, -1, -1, -1, -1), "mht_score_tracks_ais": (-1, -1, -1, -1, -1, -1),
+    "mht_score_tracks_grid": (-1, -1, -1, -1, -1, -1), "mht_score_tracks_ct_grid": (-1, -1, -1, -1, -1, -1),
+    "mht_trace_tracks": (-1, -1, -1, -1, -1, -1), "mht_trace_tracks_ct": (-1, -1, -1, -1, -1, -1), "mht_trace_tracks_ais": (-1, -1, -1, -1, -1, -1),
+    "mht_filter_tracks": (-1, -1, -1, -1, -1, -1), "mht_filter_tracks_ct": (-1, -1, -1, -1, -1, -1), "mht_filter_tracks_ais": (-1, -1, -1, -1, -1, -1),
+    "mht_imm_tracks": (-1, -1, -1, -1, -1, -1), "mht_imm_tracks_ct": (-1, -1, -1, -1, -1, -1),
+    "mht_imm_smooth_tracks": (-1, -1, -1, -1, -1, -1), "mht_imm_smooth_tracks_ct": (-1, -1, -1, -1, -1, -1)}
+
+
+@pytest.mark.parametrize("seam", sorted(SWEEP_CODES))
+def test_every_track_seam_refuses_on_the_host_and_leaves_the_outputs_untouched(ctxs, seam):
+    """One sweep over all track seams of the Python table at n = 3, L = 5 through the raw ABI, both builds: every bad call returns the
+    code of SWEEP_CODES, leaves the -7 prefill of every output as it was and a message that starts with the seam's name; one good call
+    returns MHT_OK.  Every bad call is refused on the host, before anything is launched."""
+    import torch
+    from pymht_amd import _lib, smoothing
+    from pymht_amd.models import ct, pv
+    assert sorted(SWEEP_CODES) == sorted(row[0] for row in smoothing._SEAMS.values())      # (the sweep is over ALL seams of the table)
+    (family, kind), (_, sizer, takes_nx, takes_count) = next(item for item in smoothing._SEAMS.items() if item[1][0] == seam)
+    assert (_lib.MHT_E_INVALID, _lib.MHT_E_CAPACITY) == (-1, -3)
+    nx, n, L, r = 6 if kind == "ct" else 4, 3, 5, 2
+    ns = nx * (nx + 1) // 2
+    mx, keep = smoothing._model_x(ct if kind == "ct" else pv, PERIOD, nx, kind == "ct")
+    host = lambda a: a.ctypes.data_as(C.c_void_p)
+    Qm, Rm, Pi, mu0 = np.stack([np.eye(nx)] * r), np.stack([np.eye(2)] * r), np.full((r, r), 0.5), np.full(r, 0.5)
+    for lib_nx in (4, 6):
+        ctx = ctxs[lib_nx]
+        lib, dev = ctx.lib, ctx.device
+        f64 = lambda *shape: torch.full(shape, -7.0, dtype=torch.float64, device=dev)
+        i32 = lambda *shape: torch.full(shape, -7, dtype=torch.int32, device=dev)
+        x = torch.zeros((nx, n), dtype=torch.float64, device=dev)
+        P = torch.eye(nx, dtype=torch.float64, device=dev).reshape(nx * nx, 1).repeat(1, n).contiguous()
+        z = torch.zeros((L, 2, n), dtype=torch.float64, device=dev)
+        h = torch.ones((L, n), dtype=torch.uint8, device=dev)
+        extra, middle, trailing = (), (), ()
+        if kind == "ais":      # no node took a message: kind = has_z, an empty leg table
+            ais_z, ais_r = torch.zeros((L, 4, n), dtype=torch.float64, device=dev), torch.ones((L, n), dtype=torch.float64, device=dev)
+            leg = torch.zeros((L, n), dtype=torch.int32, device=dev)
+            extra = (h.data_ptr(), ais_z.data_ptr(), ais_r.data_ptr(), leg.data_ptr(), None, 0)
+        if family == "smooth":
+            outs = [f64(L, nx, n), f64(L, ns, n)]
+        elif family in ("em", "em_ll"):
+            middle, outs = (2,), [f64(L, nx, n), f64(L, ns, n), f64(ns, n), f64(3, n)]
+            if family == "em_ll":
+                outs.append(f64(3, n))
+                trailing = (outs[-1].data_ptr(),)
+        elif family == "score":
+            outs = [f64(n), f64(n), i32(n)] + ([f64(n), i32(n)] if kind == "ais" else [])
+        elif family == "score_grid":
+            middle, outs = (r, host(Qm), host(Rm)), [f64(r, n), f64(r, n), i32(n)]
+        elif family == "trace":
+            outs = [f64(L, 7, n)] + ([f64(L, 16, n)] if kind == "ais" else [])
+        elif family == "filter":
+            outs = [f64(L, nx, n), f64(L, ns, n)]
+        else:
+            assert family in ("imm", "imm_smooth")
+            middle = (r, host(Qm), host(Rm), host(Pi), host(mu0))
+            outs = [f64(L, r, n), f64(L, nx, n), f64(L, ns, n)] + ([f64(L, r, n)] if family == "imm_smooth" else []) + [f64(n), i32(n)]
+        need = int(getattr(lib, sizer)(*((nx,) if takes_nx else ()), n, L, *((r,) if takes_count else ())))
+        assert need > 0
+        work = torch.zeros(need, dtype=torch.uint8, device=dev)
+        out_ptrs = [o.data_ptr() for o in outs[:len(outs) - len(trailing)]]
+
+        def call(model, lens, work_bytes):
+            lens = np.asarray(lens, dtype=np.int32)
+            return getattr(lib, seam)(ctx.handle, model, n, L, host(lens), x.data_ptr(), P.data_ptr(), z.data_ptr(), h.data_ptr(), *extra, *middle,
+                                      *out_ptrs, work.data_ptr(), work_bytes, *trailing)
+
+        def altered(field, value):      # (a copy of the struct: it points into `keep` as mx does)
+            m = _lib.MhtModelX.from_buffer_copy(mx)
+            setattr(m, field, value)
+            return m
+
+        wrong_nx, wrong_transition = altered("nx", 5), altered("transition", 0 if kind == "ct" else 1)
+        bad = {"null model": (None, [5, 5, 5], need), "nx": (C.byref(wrong_nx), [5, 5, 5], need),
+               "transition": (C.byref(wrong_transition), [5, 5, 5], need), "length 0": (C.byref(mx), [5, 0, 5], need),
+               "length L + 1": (C.byref(mx), [5, 6, 5], need), "workspace": (C.byref(mx), [5, 5, 5], need - 1)}
+        for case, want in zip(SWEEP_CASES, SWEEP_CODES[seam]):
+            model, lens, work_bytes = bad[case]
+            rc = call(model, lens, work_bytes)
+            torch.cuda.synchronize(dev)
+            label = "%s, %d-state build, %s" % (seam, lib_nx, case)
+            print("%s: %d" % (label, rc))
+            assert rc == want, (label, rc, want)
+            assert all(bool((o == -7).all()) for o in outs), label
+            message = lib.mht_last_error()
+            assert message and message.startswith(seam.encode() + b":"), (label, message)
+            if case == "workspace":
+                assert b"workspace" in message and sizer.encode() in message, (label, message)
+        assert call(C.byref(mx), [5, 2, 1], need) == _lib.MHT_OK, seam
+        torch.cuda.synchronize(dev)
+        assert not bool((outs[0] == -7).all()), seam
+
+
+@pytest.mark.parametrize("n", [1, 64, 65])
+@pytest.mark.parametrize("name", ["pv", "ca"])
+def test_filter_smooth_score_and_trace_agree_bit_for_bit_across_a_wavefront(ctxs, name, n):
+    """Tracks of mixed lengths 1 .. 7, one wavefront's worth, one more and a single track, at four and at six states, all four families
+    through one launch driver: a track's last filtered row is its last smoothed row, and its score is its trace added up in node
+    order -- the same bits."""
+    import smooth_trace_ref as tref
+    from pymht_amd.smoothing import filter_tracks, score_tracks, smooth_tracks, trace_tracks
+    model = _model(name)
+    rng = np.random.default_rng(100 + n)
+    lengths = [int(v) for v in rng.integers(1, 8, n)]
+    if n > 1:
+        lengths[0], lengths[-1] = 7, 1
+    tracks = sr.make_batch(model, PERIOD, lengths, seed=31 + n, p_detect=0.8)
+    ctx = ctxs[4 if name == "pv" else 6]
+    smoothed, filtered = smooth_tracks(model, PERIOD, tracks, ctx=ctx), filter_tracks(model, PERIOD, tracks, ctx=ctx)
+    scores, traces = score_tracks(model, PERIOD, tracks, ctx=ctx), trace_tracks(model, PERIOD, tracks, ctx=ctx)
+    assert len(smoothed) == len(filtered) == len(scores) == len(traces) == n
+    for L, (xs, Ps), (xf, Pf), score, trace in zip(lengths, smoothed, filtered, scores, traces):
+        assert len(xs) == len(xf) == len(trace["ll"]) == L and not np.isnan(xf).any() and not np.isnan(Pf).any()
+        assert np.array_equal(xf[-1], xs[-1]) and np.array_equal(Pf[-1], Ps[-1])
+        s = tref.resum(trace)
+        assert np.array_equal(np.array([s["ll"], s["nis"], s["nobs"]], dtype=np.float64), np.array(score, dtype=np.float64)), (s, score)
+
+
 def _run_scenario():
     from pymht_amd.tracker import Tracker
     from pymht_amd.models import pv
