@@ -695,6 +695,39 @@ int mht_mc_pair_encounters(mht_ctx* ctx, int32_t nx, int32_t transition, int32_t
                            const double* P, const int32_t* first, const double* cdf, const int32_t* pairs, uint32_t* within,
                            uint32_t* firstAt, uint32_t* ever, uint32_t* valid, int32_t* status, void* work, size_t work_bytes);
 
+/* mht_mc_zone_encounters: Monte-Carlo GUARD ZONES -- will a target enter a place (a restricted area, a shoal contour, an anchorage, a
+ * traffic-separation zone), with what probability within the horizon, and when -- with the engine of mht_mc_encounters: the particles
+ * are drawn from their target's mixture and walked exactly as mht_mc_encounters walks them (the same Philox stream keyed by
+ * (seed, target), the same sums, the constant-turn model included), and held against nZone simple polygons by a point-in-polygon test
+ * at every step and a segment-against-edges test between two steps, so that a zone thinner than one step's travel is not stepped over
+ * (csrc/mht_mc_zone.h states the definition, every operation in one order).
+ *   nx, transition, nComp, nTarget, steps, particles, seed, dt, Phi, Q, x, P, first, cdf   as for mht_mc_encounters; there is no radius
+ *   nZone, nVert     1 .. MHT_MC_ZONE_MAX_ZONES zones of 3 vertices each at least, MHT_MC_ZONE_MAX_VERTS vertices in all at most
+ *   zoneFirst        dev [nZone + 1] int32: zone z owns the vertices zoneFirst[z] .. zoneFirst[z + 1] - 1; zoneFirst[0] = 0, ascending in
+ *                    strides of 3 at least, zoneFirst[nZone] = nVert.  Read back and checked before anything is launched
+ *   zoneXY           dev [nVert][2] f64, finite, metres in the frame of the states: the vertices, either orientation, concave polygons
+ *                    included; the edge from a zone's last vertex to its first is implied.  Read back and checked as zoneFirst is
+ *   inside           dev [nZone][steps + 1][nTarget] uint32 out: the particles inside the zone at step k
+ *   firstAt          dev [nZone][steps + 1][nTarget] uint32 out: the particles that are inside the zone, or whose path segment k - 1 -> k
+ *                    meets an edge of it, FIRST at step k: the distribution of the time of entry; its sum over k is ever
+ *   ever             dev [nZone][nTarget] uint32 out: the particles that enter the zone at all; ever >= inside at every step
+ *   valid, status    dev [nTarget] out, as for mht_mc_encounters
+ *   work             dev, at least mht_mc_zone_work_bytes(nx, nComp, nTarget, nZone, steps, particles) bytes (0 for arguments out of range)
+ * Three launches (the factors and the fold of mht_mc_encounters; a workgroup per slab of a target's particles, a particle per lane, the
+ * zones staged in LDS, a far zone skipped by a whole wavefront), no atomic.  Synchronises.
+ * MHT_E_INVALID: as for mht_mc_encounters, and an nZone or nVert out of range, a zoneFirst that does not ascend from 0 to nVert in
+ * strides of 3 at least, a vertex that is not finite; nothing has then been launched or written.  Out of scope: zones that move with
+ * the own ship (a polygonal ship domain), open gates and polylines (a thin quadrilateral serves), holes, geodetic coordinates, the
+ * dwell time inside a zone.  Exported by both builds. */
+#define MHT_MC_ZONE_MAX_ZONES 32       /* zones per call */
+#define MHT_MC_ZONE_MAX_VERTS 1024     /* vertices of all zones of a call together */
+size_t mht_mc_zone_work_bytes(int32_t nx, int32_t nComp, int32_t nTarget, int32_t nZone, int32_t steps, int32_t particles);
+int mht_mc_zone_encounters(mht_ctx* ctx, int32_t nx, int32_t transition, int32_t nComp, int32_t nTarget, int32_t nZone, int32_t nVert,
+                           int32_t steps, int32_t particles, uint64_t seed, double dt, const double* Phi, const double* Q, const double* x,
+                           const double* P, const int32_t* first, const double* cdf, const int32_t* zoneFirst, const double* zoneXY,
+                           uint32_t* inside, uint32_t* firstAt, uint32_t* ever, uint32_t* valid, int32_t* status, void* work,
+                           size_t work_bytes);
+
 /* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
  * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);
  * with d_ij = sqrt(dx dx + dy dy) in float64 and only pairs with d_ij < c (strictly) assignable,

@@ -15,15 +15,17 @@
 // loop in the code object moved by 1 to 2.5 %).
 //
 // The per-kernel paragraphs stand with the kernels.
+//
+// mht_mc_seam.h declares what a seam in another unit launches through (mht_mc_zone.hip, the guard zones): the factor and the fold
+// launches, the layout and the shared checks, all defined here.
 #include <vector>
 #include "mht_common.h"
 #include "mht_mc_pair.h"
+#include "mht_mc_seam.h"
 
 namespace mht {
 
-constexpr int MC_MAX_BLOCKS = 2048;
-constexpr int MC_WAVES = MC_THREADS / 64;
-constexpr int MC_ROW = MC_MAX_STEPS + 1;            // words of a path's row (own ship) or of an array (pair) in LDS, whatever K is
+// (MC_ROW, mht_mc_seam.h: the words of a path's row (own ship) or of an array (pair) in LDS, whatever K is)
 constexpr int MC_PAIR_WORDS = 2 * MC_ROW + 1;       // within, firstAt, ever
 
 template <int N>
@@ -66,16 +68,6 @@ struct McPairWalkArgs {
     uint32_t* part;            // [chunks][2 (K + 1) + 1][nPair]: within [K + 1], firstAt [K + 1], ever
     int32_t* pstatus;          // [nPair]
     int32_t pair, chunk, ta, tb;      // (not arguments: the workgroup's pair, chunk and targets, put here by its first lane)
-};
-
-struct McFoldArgs {
-    int32_t items, words, chunks, S;
-    const uint32_t* part;        // [chunks][words][items]
-    const int32_t* istatus;      // [items]
-    uint32_t *out0, *out1, *out2;      // words 0 .. end0 - 1, end0 .. end1 - 1 and end1 .. words - 1, each [..][items]
-    int32_t end0, end1;
-    uint32_t* valid;             // [items]
-    int32_t* status;             // [items]
 };
 
 // What mc_walk hands its predicates to, in a workgroup
@@ -126,21 +118,7 @@ struct McPairWaveSink {
     __device__ void done(bool came) { ev += (uint32_t)__popcll(__ballot(came)); }
 };
 
-// The by-value arguments of a walk kernel into the workgroup's LDS, dword-wise (why: the head of the file)
-template <class Args>
-__device__ void mc_stage(Args& s, const Args& a, int tid) {
-    static_assert(sizeof(Args) % 4 == 0, "the arguments are copied dword-wise");
-    for (int i = tid; i < (int)(sizeof(Args) / 4); i += MC_THREADS) reinterpret_cast<uint32_t*>(&s)[i] = reinterpret_cast<const uint32_t*>(&a)[i];
-}
-
-// A lane's share of the status of target t's components (mc_target_status, strided over the workgroup); the caller ORs over the lanes
-__device__ void mc_target_flags(const int32_t* first, const int32_t* cstatus, int t, int tid, int& nan, int& indefinite) {
-    for (int c = first[t] + tid; c < first[t + 1]; c += MC_THREADS) {
-        const int st = cstatus[c];
-        nan |= st == 1;
-        indefinite |= st == 2;
-    }
-}
+// (mc_stage, the by-value arguments of a walk kernel into the workgroup's LDS, and mc_target_flags: mht_mc_seam.h)
 
 // ONE COMPONENT PER LANE, mc_component: the factor of its P, packed and component-minor, and its status into the work buffer.  (The
 // factor of Q is computed once on the host side of the seam with the same function and travels in the arguments.)
@@ -280,13 +258,8 @@ __global__ void __launch_bounds__(MC_THREADS) mc_fold_kernel(const McFoldArgs a)
     }
 }
 
-// The work buffer of a call over `items` targets or pairs of `words` words each
-struct McLayout {
-    size_t Lw, part, cstatus, istatus, bytes;      // offsets in bytes, and their total
-    McSplit split;
-};
-
-static McLayout mc_layout(int32_t nx, int32_t nComp, int32_t items, int32_t words, int32_t S) {
+// The work buffer of a call over `items` targets or pairs of `words` words each (McLayout: mht_mc_seam.h)
+McLayout mc_layout(int32_t nx, int32_t nComp, int32_t items, int32_t words, int32_t S) {
     McLayout l;
     l.split = mc_chunks(items, S);
     l.Lw = 0;
@@ -297,7 +270,7 @@ static McLayout mc_layout(int32_t nx, int32_t nComp, int32_t items, int32_t word
     return l;
 }
 
-static bool mc_sizes_fit(int32_t nx, int32_t nComp, int32_t T, int32_t K, int32_t S) {
+bool mc_sizes_fit(int32_t nx, int32_t nComp, int32_t T, int32_t K, int32_t S) {
     return (nx == 4 || nx == 6) && nComp >= 1 && T >= 1 && T <= nComp && K >= 1 && K <= MC_MAX_STEPS && S >= MC_WARP && S <= MC_MAX_PARTICLES && S % MC_WARP == 0;
 }
 
@@ -312,7 +285,11 @@ static int mc_launch_factor(mht_ctx* ctx, int32_t nComp, const double* x, const 
     return launch_kernel(ctx, K_SMOOTH_SCORE, mc_factor_kernel<N>, dim3(mc_blocks((size_t)nComp)), dim3(MC_THREADS), 0, false, fa);
 }
 
-static int mc_launch_fold(mht_ctx* ctx, const McFoldArgs& ga) {
+int mc_launch_factor(mht_ctx* ctx, int32_t nx, int32_t nComp, const double* x, const double* P, const double* cdf, double* Lw, int32_t* cstatus) {
+    return nx == 4 ? mc_launch_factor<4>(ctx, nComp, x, P, cdf, Lw, cstatus) : mc_launch_factor<6>(ctx, nComp, x, P, cdf, Lw, cstatus);
+}
+
+int mc_launch_fold(mht_ctx* ctx, const McFoldArgs& ga) {
     return launch_kernel(ctx, K_SMOOTH_SCORE, mc_fold_kernel, dim3(mc_blocks((size_t)(ga.words + 1) * (size_t)ga.items)), dim3(MC_THREADS), 0, false, ga);
 }
 
@@ -351,14 +328,14 @@ static int mc_pair_run(mht_ctx* ctx, int32_t nComp, int32_t nPair, int32_t K, in
     return mc_launch_fold(ctx, McFoldArgs{nPair, words, l.split.chunks, S, part, ps, within, firstAt, ever, K + 1, 2 * (K + 1), valid, status});
 }
 
-// The checks the two seams share, under the seam's name `who`, in the seams' order: nx, transition, nComp and nTarget, steps,
+// The checks the seams share, under the seam's name `who`, in the seams' order: nx, transition, nComp and nTarget, steps,
 // particles, radius and dt, Phi and Q finite (the seam has checked that they are there), and -- first lives on the device: it is read
 // back and checked before anything is launched, a walk indexes the components with it -- first itself.  `also` (n words, into
-// alsoHost) is the seam's own index array, read back in the same trip.  A seam makes its own checks -- the number of own paths or of
-// pairs, the null arrays, the work buffer -- in front of this, so a call with one fault is refused with the text it always had, and of
-// two faults the seam's own is the one named.
-static int mc_seam_checks(const char* who, mht_ctx* ctx, int32_t nx, int32_t transition, int32_t nComp, int32_t nTarget, int32_t steps, int32_t particles, double dt,
-                          double radius, const double* Phi, const double* Q, const int32_t* first, const int32_t* also, size_t n, std::vector<int32_t>& alsoHost) {
+// alsoHost) is the seam's own index array, read back in the same trip.  A seam makes its own checks -- the number of own paths, of
+// pairs or of zones, the null arrays, the work buffer -- in front of this, so a call with one fault is refused with the text it always
+// had, and of two faults the seam's own is the one named.  A seam without a radius (the zones') passes 1.
+int mc_seam_checks(const char* who, mht_ctx* ctx, int32_t nx, int32_t transition, int32_t nComp, int32_t nTarget, int32_t steps, int32_t particles, double dt,
+                   double radius, const double* Phi, const double* Q, const int32_t* first, const int32_t* also, size_t n, std::vector<int32_t>& alsoHost) {
     MHT_REQUIRE(nx == 4 || nx == 6, "%s: nx must be 4 or 6 (got %d)", who, nx);
     MHT_REQUIRE(transition == 0 || (transition == 1 && nx == 6), "%s: transition is 0 (linear) or, with nx 6, 1 (constant turn) (got %d, nx %d)", who, transition, nx);
     MHT_REQUIRE(nComp >= 1 && nTarget >= 1 && nTarget <= nComp, "%s: 1 <= nTarget <= nComp is wanted (got %d targets, %d components)", who, nTarget, nComp);

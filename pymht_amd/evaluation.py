@@ -947,8 +947,13 @@ def _mc_call(a, sizer, seam, extra, mid, shapes, dt, radius, seed, transition, d
     """The device call `mc_encounters` and `mc_pair_encounters` share, on `_mc_arguments`' dict `a`: x and P packed in `order`, one
     upload (with `extra`, the seam's own device input: the own paths or the pairs' ranks), the work buffer of `sizer`, one int32 tensor
     per entry of `shapes` (name -> shape, in the seam's order), the call of `seam` with `mid` as its middle size argument (G or n),
-    and the arrays read back: uint32 counts, `status` int32.  A context of its own where `ctx` is None."""
+    and the arrays read back: uint32 counts, `status` int32.  A context of its own where `ctx` is None.  `mc_zone_encounters` calls
+    with two device inputs (`extra` a tuple), two middle sizes (`mid` a tuple, of which the sizer takes the first) and no radius
+    (None: the seam has none)."""
     nx, L, T, steps, S, order = a["nx"], a["L"], a["T"], a["steps"], a["S"], a["order"]
+    extras = extra if isinstance(extra, tuple) else (extra,)
+    mids = mid if isinstance(mid, tuple) else (mid,)
+    scalars = (int(seed), float(dt)) + (() if radius is None else (float(radius),))
     iu = np.triu_indices(nx)
     xp, Pp = np.ascontiguousarray(a["x"][order].T), np.ascontiguousarray(a["P"][order][:, iu[0], iu[1]].T)
     Phi, Q = np.ascontiguousarray(a["Phi"]), np.ascontiguousarray(a["Q"])
@@ -957,14 +962,14 @@ def _mc_call(a, sizer, seam, extra, mid, shapes, dt, radius, seed, transition, d
         ctx = Context(device, nx=nx)
     try:
         dev, lib = ctx.device, ctx.lib
-        x_d, P_d, f_d, c_d, e_d = [torch.from_numpy(v).to(dev) for v in (xp, Pp, a["first"], a["cdf"], extra)]
-        need = int(getattr(lib, sizer)(nx, L, T, mid, steps, S))
+        x_d, P_d, f_d, c_d, *e_d = [torch.from_numpy(v).to(dev) for v in (xp, Pp, a["first"], a["cdf"]) + extras]
+        need = int(getattr(lib, sizer)(nx, L, T, mids[0], steps, S))
         work = torch.empty(need, dtype=torch.uint8, device=dev)
         # (uint32 counts in int32 tensors: the same bits)
         out = {name: torch.empty(shape, dtype=torch.int32, device=dev) for name, shape in shapes.items()}
         torch.cuda.current_stream(dev).synchronize()      # (the uploads ran on torch's stream)
-        _lib.check(getattr(lib, seam)(ctx.handle, nx, 1 if transition == "ct" else 0, L, T, mid, steps, S, int(seed), float(dt), float(radius), Phi.ctypes.data,
-                                      Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(), f_d.data_ptr(), c_d.data_ptr(), e_d.data_ptr(),
+        _lib.check(getattr(lib, seam)(ctx.handle, nx, 1 if transition == "ct" else 0, L, T, *mids, steps, S, *scalars, Phi.ctypes.data,
+                                      Q.ctypes.data, x_d.data_ptr(), P_d.data_ptr(), f_d.data_ptr(), c_d.data_ptr(), *[t.data_ptr() for t in e_d],
                                       *[t.data_ptr() for t in out.values()], work.data_ptr(), need), lib)
         return {name: t.cpu().numpy() if name == "status" else t.cpu().numpy().view(np.uint32) for name, t in out.items()}
     finally:
@@ -1157,6 +1162,84 @@ def mc_pair_screen(x, target, weight, horizon, distance, block=256):
         keep.append(np.stack([targets[a + lo], targets[b]], axis=1))
     out = np.concatenate(keep, axis=0) if keep else np.zeros((0, 2))
     return np.ascontiguousarray(out, dtype=np.int64).reshape(-1, 2)
+
+
+# ---- guard zones by Monte Carlo: targets entering polygons, with entry times ---------------------------------------------------------
+MC_ZONE_MAX_ZONES, MC_ZONE_MAX_VERTS = 32, 1024      # MHT_MC_ZONE_*, include/mht_amd.h
+
+
+def mc_zone_pack(zones, who="mc_zone_pack"):
+    """A list of polygons, each a finite [V, 2] array with V >= 3, as `mht_mc_zone_encounters` takes them: (zoneFirst int32 [Z + 1],
+    zoneXY float64 [nVert, 2]).  At most 32 zones and 1 024 vertices in all.  ValueError (under the caller's name `who`) otherwise."""
+    if isinstance(zones, np.ndarray) and zones.ndim != 3:
+        raise ValueError("%s: zones is a LIST of [V, 2] arrays, one per zone (got an array of shape %r)" % (who, zones.shape))
+    try:
+        polys = [np.asarray(z, dtype=np.float64) for z in zones]
+    except (TypeError, ValueError):
+        raise ValueError("%s: zones is a list of [V, 2] arrays of numbers (got %r)" % (who, zones))
+    if len(polys) > MC_ZONE_MAX_ZONES:
+        raise ValueError("%s: at most %d zones (got %d)" % (who, MC_ZONE_MAX_ZONES, len(polys)))
+    for z, poly in enumerate(polys):
+        if poly.ndim != 2 or poly.shape[1] != 2 or len(poly) < 3:
+            raise ValueError("%s: zone %d is a [V, 2] array with V >= 3 (got shape %r)" % (who, z, poly.shape))
+        if not np.isfinite(poly).all():
+            raise ValueError("%s: zone %d has a vertex that is not finite" % (who, z))
+    first = np.concatenate([[0], np.cumsum([len(p) for p in polys])]).astype(np.int32)
+    if first[-1] > MC_ZONE_MAX_VERTS:
+        raise ValueError("%s: at most %d vertices in all zones together (got %d)" % (who, MC_ZONE_MAX_VERTS, int(first[-1])))
+    xy = np.concatenate(polys, axis=0) if polys else np.zeros((0, 2))
+    return first, np.ascontiguousarray(xy, dtype=np.float64)
+
+
+def mc_zone_derive(inside, firstAt, ever, valid, dt):
+    """The host's figures of `mc_zone_encounters` from its counts (inside, firstAt [Z, K + 1, T]; ever [Z, T]; valid [T]): pInside =
+    inside / valid; pInsideMax [Z, T] and tInside, the largest pInside over the steps and the time k dt of the EARLIEST largest; pEver =
+    ever / valid; pEverBy [Z, K + 1, T] = cumsum(firstAt) / valid, the probability of having entered by the time k dt (its last row is
+    pEver); sePInsideMax and sePEver by `mc_standard_error`.  NaN where valid is 0."""
+    d = mc_derive(inside, ever, valid, dt)
+    v = np.asarray(valid, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        by = np.where(v > 0, np.cumsum(np.asarray(firstAt, dtype=np.int64), axis=1) / v, np.nan)
+    return dict(pInside=d["pc"], pInsideMax=d["pcMax"], tInside=d["tpc"], pEver=d["pEver"], pEverBy=by, sePInsideMax=d["sePcMax"], sePEver=d["sePEver"])
+
+
+def mc_zone_encounters(x, P, target, weight, Phi, Q, steps, dt, zones, particles=4096, seed=0, transition="linear", device=0, ctx=None):
+    """GUARD ZONES by MONTE CARLO: will a target enter a PLACE -- a restricted area, a shoal contour, an anchorage, a traffic-separation
+    zone --, with what probability within the horizon, and when.  The engine is `mc_encounters`' (csrc/mht_mc_zone.h states the
+    definition): every target is the Gaussian mixture of its components, its particles are walked over steps * dt seconds with the
+    model's process noise -- exactly the particles `mc_encounters` and `mc_pair_encounters` walk for the same seed, the constant-turn
+    model with Phi(dt, w) at every particle's own turn rate included -- and held against every zone: a point-in-polygon test at every
+    step (the zone's box, then the crossing number) and the path segment between two steps against the zone's edges, so that a zone
+    thinner than one step's travel is not stepped over.
+
+    x, P, target, weight, Phi, Q, steps, dt, particles, seed, transition   as for `mc_encounters`; there is no radius
+    zones      a list of at most 32 simple polygons, each a finite [V, 2] array of vertices in metres, V >= 3, at most 1 024 vertices
+               in all; either orientation, concave polygons included; the edge from the last vertex to the first is implied
+    ValueError for arguments that do not fit -- before any device is needed.  No zone or no component: empty arrays, no device call.
+    Returns a dict.  As the device wrote them: `inside` [Z, steps + 1, T] (the particles inside the zone at step k), `firstAt`
+    [Z, steps + 1, T] (the particles that are inside the zone, or whose segment k - 1 -> k meets an edge of it, FIRST at step k: the
+    distribution of the time of entry), `ever` [Z, T] = the sum of firstAt over the steps, `valid` [T] and `status` [T] as for
+    `mc_encounters`.  Derived on the host by `mc_zone_derive`, NaN where valid is 0: `pInside`, `pInsideMax`, `tInside`, `pEver`,
+    `pEverBy`, `sePInsideMax`, `sePEver`.  And `zoneFirst` [Z + 1], `zoneXY` [nVert, 2], `targets` [T], `first` [T + 1], `cdf` [L] and
+    `order` [L] as they were used.
+    Out of scope: zones that move with the own ship (a polygonal ship domain), open gates and polylines (a thin quadrilateral
+    serves), holes, geodetic coordinates, the dwell time inside a zone.
+    One upload, one call of `mht_mc_zone_encounters` (three launches), no host fallback."""
+    who = "mc_zone_encounters"
+    a = _mc_arguments(who, x, P, target, weight, Phi, Q, steps, dt, 1.0, particles, seed, transition)
+    L, steps, order, targets, first, cdf, T = a["L"], a["steps"], a["order"], a["targets"], a["first"], a["cdf"], a["T"]
+    zf, zxy = mc_zone_pack(zones, who)
+    Z = len(zf) - 1
+    res = dict(zoneFirst=zf, zoneXY=zxy, targets=targets.astype(np.int64), first=first, cdf=cdf, order=order.astype(np.int64))
+    if L == 0 or Z == 0:
+        T = T if Z else 0
+        res.update(inside=np.zeros((Z, steps + 1, T), dtype=np.uint32), firstAt=np.zeros((Z, steps + 1, T), dtype=np.uint32), ever=np.zeros((Z, T), dtype=np.uint32),
+                   valid=np.zeros(T, dtype=np.uint32), status=np.zeros(T, dtype=np.int32))
+    else:
+        res.update(_mc_call(a, "mht_mc_zone_work_bytes", "mht_mc_zone_encounters", (zf, zxy), (Z, len(zxy)),
+                            dict(inside=(Z, steps + 1, T), firstAt=(Z, steps + 1, T), ever=(Z, T), valid=(T,), status=(T,)), dt, None, seed, transition, device, ctx))
+    res.update(mc_zone_derive(res["inside"], res["firstAt"], res["ever"], res["valid"], float(dt)))
+    return res
 
 
 # ---- the k best global hypotheses ---------------------------------------------------------------------------------------------------

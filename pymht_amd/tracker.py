@@ -1670,6 +1670,49 @@ class Tracker():
         out["worst"] = int(out["ranking"][0]) if n else None
         return out
 
+    def getMonteCarloZoneEncounters(self, horizon, zones, particles=4096, seed=0, steps=None, hypotheses=True, weights=None):
+        """GUARD ZONES by MONTE CARLO (evaluation.mc_zone_encounters defines the figures): will a target enter a PLACE -- a restricted
+        area, a shoal contour, an anchorage, a traffic-separation zone --, with what probability within `horizon`, and when.  The other
+        forward-looking outputs measure a target against something that moves (the own ship, another target); this one measures it
+        against polygons that stand still, with the engine of getMonteCarloEncounters -- particles drawn from the forest's own leaves, a
+        Gaussian mixture per target, walked with the model's process noise, the same particles for the same seed.  A zone thinner than
+        one step's travel is not stepped over: the path between two steps is held against the zone's edges.  Works for models/pv,
+        models/ca and models/ct, and for AIS-aided trackers.  Times count from the current scan.
+
+        horizon, particles, seed, steps, hypotheses, weights   as for getMonteCarloEncounters
+        zones          a list of [V, 2] arrays: the vertices of every zone in metres, the tracker's frame; at most 32 zones of 3
+                       vertices at least, 1 024 vertices in all; either orientation, concave polygons included
+        Returns evaluation.mc_zone_encounters' dict -- inside, firstAt, ever, valid, status, pInside, pInsideMax, tInside, pEver,
+        pEverBy, sePInsideMax, sePEver, zoneFirst, zoneXY, targets, first, cdf, order -- plus `ids` (the id of every target of the
+        result, in its order), `leafIds` (the target id of every leaf used) and `ranking` [n, 2]: the (zone, target) cells by
+        descending pEver, ties by zone and then target, cells without a figure last.  No live target or no zone: empty arrays, no
+        device call.
+        Out of scope: zones that move with the own ship (a polygonal ship domain), open gates and polylines (a thin quadrilateral
+        serves), holes, geodetic coordinates, the dwell time inside a zone."""
+        from . import evaluation
+        name = "getMonteCarloZoneEncounters"
+        steps, dt, nx, Phi, Q, ct = self._mc_horizon(name, horizon, 1.0, steps)
+        try:
+            evaluation.mc_zone_pack(zones, name)      # (before the leaves are gathered: a zone that does not fit costs no device read)
+            if len(zones) == 0:      # (no zone: no leaf is read and nothing is uploaded)
+                x, P, tg, leaf_ids, w, ids = np.zeros((0, nx)), np.zeros((0, nx, nx)), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64), np.zeros(0), []
+            else:
+                x, P, tg, leaf_ids, w, ids = self._mc_leaves(name, nx, hypotheses, weights)
+            out = evaluation.mc_zone_encounters(x, P, tg, w, Phi, Q, steps, dt, zones, particles=particles, seed=seed, transition="ct" if ct else "linear",
+                                                ctx=self._ctx)
+        except ValueError as exc:
+            text = str(exc)
+            raise ValueError(text if text.startswith(name) else "%s: %s" % (name, text))
+        out["ids"] = [ids[t] if t < len(ids) else -1 for t in out["targets"]]
+        out["leafIds"] = leaf_ids
+        p = out["pEver"]
+        Z, T = p.shape
+        zz, tt = np.divmod(np.arange(Z * T), max(T, 1))
+        flat = p.reshape(-1)
+        order = np.lexsort((np.arange(Z * T), np.where(np.isnan(flat), np.inf, -flat)))
+        out["ranking"] = np.stack([zz[order], tt[order]], axis=1).astype(np.int64).reshape(-1, 2)
+        return out
+
     def leafRows(self):
         """The keys of the plots on every current leaf's window path, [L, N + 1] int32 in leafBatch() order (`mht_forest_leaf_rows`): per
         ancestor with a measurement, from the leaf up to its target's window root (the root itself only where it is the leaf),
