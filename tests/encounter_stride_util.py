@@ -1,0 +1,228 @@
+"""The scenes of tests/test_encounter_strides_gpu.py and tests/test_encounter_strides_cpu.py: the smallest calls of `mht_encounters`,
+`mht_trial_manoeuvres` and `mht_trial_hypotheses` whose kernels go round their grid-stride loops more than once -- every launch is
+capped at 2048 workgroups of 256 lanes -- with the references' evaluations of them, each computed once per process.
+
+    E1  encounters        n = first = 683           3 chunks, 2049 tiles: the pair kernel strides
+    E2  encounters        n = 524 588, first = 1    the propagate kernel strides (2050 workgroups' worth), row 0 spans 2050 tiles
+    T1  trial manoeuvres  n = 524 588, G = 1        propagate and cell stride, the summary's lanes take 33 chunks each; planted ties
+    T2  trial manoeuvres  n = 257, G = 1025         2 chunks, 2050 tiles: g changes from trip to trip; five workgroups of candidates
+    T3  trial manoeuvres  n = 1, G = 4096           4096 tiles of one live lane, the summary's grid strides
+    H1  trial hypotheses  L = 513, T = 4, G = 683   segments 250, 12, 250, 1: 3 chunks, 2049 tiles
+    H2  trial hypotheses  L = T = 129, G = 4096     528 384 (g, t): the target kernel strides
+
+K = 1, dt = 5, R = 80 everywhere.  The large tables are a FLEET: entries spread over +-500 km, so that the rule gives pc = 0 exactly for
+almost all of them, and a few hundred entries PLANTED next to the own ship at the indices where an indexing slip would show."""
+import numpy as np
+
+import encounter_ref as eref
+import trial_hyp_ref as href
+import trial_ref as tref
+from test_encounter_cpu import RADIUS
+
+DT = 5.0
+K = 1
+TILE = 256
+BIG = 524288 + 300                       # 2048 full workgroups of entries and 300 more: 2050 tiles a row
+E1_N = 683
+T2_N, T2_G, T2_NAN = 257, 1025, 600
+T3_G = 4096
+H1_SIZES, H1_G, H1_NO_SELECTED = (250, 12, 250, 1), 683, 2
+H2_L, H2_G = 129, 4096
+# planted entries: tile 0; around 255 / 256 / 257; around 524 287 / 524 288 / 524 289 and on into tile 2048; all of the last tile (2049),
+# which holds 44 entries
+PLANTED = np.concatenate([np.arange(1, 100), np.arange(250, 263), np.arange(524280, 524401), np.arange(2049 * TILE, BIG)])
+NAN_ENTRY = 524290                       # a planted entry with a NaN in x
+OWN = np.array([0.0, 0.0, 6.0, 3.0])     # the own ship of the fleets: entry 0 of E2, `own` of T1
+# T1's ties, (the largest pc's pair, the smallest dcpa's pair): between chunks c and c + 64, one lane of the summary kernel, and in the
+# second call between chunks 63 and 64, two lanes
+TIES_SAME_LANE = ((5 * TILE + 17, 69 * TILE + 3), (7 * TILE + 200, 71 * TILE + 100))
+TIES_TWO_LANES = ((63 * TILE + 255, 64 * TILE), (63 * TILE + 10, 64 * TILE + 20))
+T1_CANDIDATE = tref.CANDIDATES[1:2]      # 40 degrees to port at once
+
+
+def model_of(N):
+    from pymht_amd.models import ca, pv
+    return pv if N == 4 else ca
+
+
+def covariances(model, rng, n, block=1 << 16):
+    """P [n, N, N] as encounter_ref.make_batch draws it -- the model's P0 with the axes scaled by 0.1 .. 30 and the plane turned -- without
+    a Python loop over the entries"""
+    P0 = np.asarray(model.P0, dtype=np.float64)
+    N = P0.shape[0]
+    P = np.empty((n, N, N))
+    for a in range(0, n, block):
+        m = min(block, n - a)
+        d = np.tile(np.sqrt(rng.uniform(0.1, 30, (m, 2))), (1, N // 2))
+        phi = rng.uniform(0, 2 * np.pi, m)
+        G = np.zeros((m, N, N))
+        for b in range(0, N, 2):
+            G[:, b, b], G[:, b, b + 1], G[:, b + 1, b], G[:, b + 1, b + 1] = np.cos(phi), -np.sin(phi), np.sin(phi), np.cos(phi)
+        M = G @ (d[:, :, None] * P0[None] * d[:, None, :]) @ np.transpose(G, (0, 2, 1))
+        P[a:a + m] = 0.5 * (M + np.transpose(M, (0, 2, 1)))
+    return P
+
+
+def fleet(model, seed, near, far, dv):
+    """BIG entries (x [n, N], P [n, N, N]) over +-500 km at 0 .. 15 m/s; the PLANTED ones `near` .. `far` metres from OWN's position on
+    any bearing, with OWN's velocity and up to `dv` m/s more a component; NAN_ENTRY has a NaN in x."""
+    rng = np.random.default_rng(seed)
+    N = int(np.asarray(model.P0).shape[0])
+    x = np.zeros((BIG, N))
+    x[:, :2] = rng.uniform(-5e5, 5e5, (BIG, 2))
+    speed, head = rng.uniform(0, 15, BIG), rng.uniform(0, 2 * np.pi, BIG)
+    x[:, 2], x[:, 3] = speed * np.cos(head), speed * np.sin(head)
+    if N == 6:
+        x[:, 4:] = rng.uniform(-0.02, 0.02, (BIG, 2))
+    P = covariances(model, rng, BIG)
+    m = len(PLANTED)
+    dist, bearing = rng.uniform(near, far, m), rng.uniform(0, 2 * np.pi, m)
+    x[PLANTED, 0], x[PLANTED, 1] = OWN[0] + dist * np.cos(bearing), OWN[1] + dist * np.sin(bearing)
+    x[PLANTED, 2:4] = OWN[2:] + rng.uniform(-dv, dv, (m, 2))
+    x[NAN_ENTRY, N - 1] = np.nan
+    return x, P
+
+
+def places(n=BIG):
+    """The four places a fleet must have live cells in, as masks over the entries: tile 0, a tile with index >= 2048 (tile 2048), the
+    entries from 524 288 on, the last tile"""
+    j = np.arange(n)
+    return {"tile 0": j < TILE, "tile 2048": j // TILE == 2048, "entries >= 524288": j >= 524288, "last tile": j // TILE == (n - 1) // TILE}
+
+
+def cycle(G, shift=0):
+    """(cand [G, 3], kind [G]): trial_ref.CANDIDATES repeated cyclically from `shift` on, and which of them each row is"""
+    kind = (np.arange(G) + shift) % len(tref.CANDIDATES)
+    return tref.CANDIDATES[kind].copy(), kind
+
+
+_cache = {}
+
+
+def _once(key, make):
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+def _both(key, fn, args, truth):
+    """(f64, truth or None) of a reference on one scene; the truth's pc is the float64 rule's on the longdouble d_k, Sigma_k"""
+    f64 = _once((key, "f64"), lambda: fn(*args))
+    return f64, (_once((key, "truth"), lambda: fn(*args, truth=True, pc_mp=False)) if truth else None)
+
+
+# ---- encounters ----------------------------------------------------------------------------------------------------------------------
+def e1_scene(N=4):
+    model = model_of(N)
+    return _once(("e1 scene", N), lambda: eref.make_batch(model, E1_N, seed=3) + eref.model_matrices(model, DT))
+
+
+def e1(N=4, truth=True):
+    """(x, P, Phi, Q, f64, truth): encounter_ref.make_batch, 683 entries, all pairs"""
+    x, P, Phi, Q = e1_scene(N)
+    return (x, P, Phi, Q) + _both(("e1", N), eref.encounters, (x, P, Phi, Q, K, DT, RADIUS), truth)
+
+
+def e2_scene(N=6):
+    def make():
+        model = model_of(N)
+        x, P = fleet(model, seed=11, near=5.0, far=150.0, dv=1.0)
+        x[0] = 0.0
+        x[0, :4] = OWN
+        return (x, P) + eref.model_matrices(model, DT)
+    return _once(("e2 scene", N), make)
+
+
+def e2(N=6, truth=True):
+    """(x, P, Phi, Q, f64, truth): the fleet with the own ship as entry 0, first = 1"""
+    x, P, Phi, Q = e2_scene(N)
+    row = lambda *a, **kw: eref.encounters(*a, first=1, **kw)
+    return (x, P, Phi, Q) + _both(("e2", N), row, (x, P, Phi, Q, K, DT, RADIUS), truth)
+
+
+# ---- trial manoeuvres ----------------------------------------------------------------------------------------------------------------
+def t1_scene(N=4):
+    """(x, P, Phi, Q, own, Sown) with the ties of TIES_SAME_LANE: the planted tracks lie 82 .. 100 m from the own ship, their centres
+    outside the radius; the pc pair, two identical tracks 50 m away with the own ship's velocity, has the row's largest pc; the dcpa pair,
+    20 m away with a covariance 2000 times the model's P0 (so that its pc is small), the smallest dcpa."""
+    def make():
+        model = model_of(N)
+        x, P = fleet(model, seed=12, near=82.0, far=100.0, dv=0.3)
+        P0 = np.asarray(model.P0, dtype=np.float64)
+        (p1, p2), (d1, d2) = TIES_SAME_LANE
+        for j in (p1, p2, d1, d2):
+            x[j] = 0.0
+            x[j, 2:4] = OWN[2:]
+        x[[p1, p2], :2] = OWN[:2] + np.array([30.0, -40.0])
+        x[[d1, d2], :2] = OWN[:2] + np.array([-12.0, 16.0])
+        P[[p1, p2]], P[[d1, d2]] = P0, 2000.0 * P0
+        return (x, P) + eref.model_matrices(model, DT) + (OWN.copy(), tref.OWN_COV.copy())
+    return _once(("t1 scene", N), make)
+
+
+def t1_swap():
+    """The permutation of the tracks that moves T1's ties from TIES_SAME_LANE to TIES_TWO_LANES: the tied tracks change places with the
+    (far) tracks there.  A column of the table depends on its track alone, so the second call's reference is the first's, permuted."""
+    perm = np.arange(BIG)
+    a, b = np.ravel(TIES_SAME_LANE), np.ravel(TIES_TWO_LANES)
+    perm[a], perm[b] = b, a
+    return perm
+
+
+def t1(N=4, truth=True):
+    """(x, P, Phi, Q, own, Sown, f64, truth): the fleet as tracks, one candidate"""
+    x, P, Phi, Q, own, Sown = t1_scene(N)
+    return (x, P, Phi, Q, own, Sown) + _both(("t1", N), tref.manoeuvres, (x, P, Phi, Q, K, DT, RADIUS, own, Sown, tref.TURN_RATE, T1_CANDIDATE), truth)
+
+
+def permuted(ev, perm):
+    """An evaluation (dict of [..., n] arrays) of the tracks taken in the order perm"""
+    return {k: np.ascontiguousarray(v[..., perm]) for k, v in ev.items()}
+
+
+def distinct_rows(x, P, Phi, Q, own, Sown, key, truth=True):
+    """(f64, truth) of trial_ref.manoeuvres for the five rows of trial_ref.CANDIDATES"""
+    return _both(key, tref.manoeuvres, (x, P, Phi, Q, K, DT, RADIUS, own, Sown, tref.TURN_RATE, tref.CANDIDATES), truth)
+
+
+def t2_scene(N=6):
+    """(x, P, Phi, Q, own, Sown, cand, kind): trial_ref.make_scene, 257 tracks; 1025 candidates, row T2_NAN with a NaN (kind -1)"""
+    def make():
+        model = model_of(N)
+        cand, kind = cycle(T2_G, shift=2)      # (the last row, the one the second trips reach, alters course)
+        cand[T2_NAN, 0], kind[T2_NAN] = np.nan, -1
+        return tref.make_scene(model, T2_N, seed=3) + eref.model_matrices(model, DT) + (cand, kind)
+    x, P, own, Sown, Phi, Q, cand, kind = _once(("t2 scene", N), make)
+    return x, P, Phi, Q, own, Sown, cand, kind
+
+
+def t3_scene(N=4):
+    """(x, P, Phi, Q, own, Sown, cand, kind): one track, 100 m off the own ship and closing at 6 m/s, so that its pc is that of t = 5 and differs with the candidate; 4096 candidates"""
+    def make():
+        model = model_of(N)
+        x, P, own, Sown = tref.make_scene(model, 52, seed=3)
+        x, P = x[:1].copy(), P[:1].copy()
+        x[0, :2], x[0, 2:4] = own[:2] + np.array([80.0, 60.0]), own[2:] + np.array([-4.8, -3.6])
+        return (x, P) + eref.model_matrices(model, DT) + (own, Sown) + cycle(T3_G, shift=1)
+    return _once(("t3 scene", N), make)
+
+
+# ---- trial hypotheses ----------------------------------------------------------------------------------------------------------------
+def h1_scene(N=6):
+    """(x, P, cnllr, seg, sel, own, Sown, Phi, Q, cand, kind): trial_hyp_ref.make_leaves with its special leaves for segments of 250, 12,
+    250 and 1 leaves -- the second straddles leaf 256, the third ends exactly at 512, the last begins a tile alone -- sel = -1 for the
+    third; 683 candidates"""
+    def make():
+        model = model_of(N)
+        x, P, cnllr, target, sel, own, Sown = href.make_leaves(model, H1_SIZES, seed=3, no_selected=H1_NO_SELECTED)
+        return (x, P, cnllr, href.segments(target, len(H1_SIZES)), sel, own, Sown) + eref.model_matrices(model, DT) + cycle(H1_G)
+    return _once(("h1 scene", N), make)
+
+
+def h2_scene(N=4):
+    """(x, P, cnllr, seg, sel, own, Sown, Phi, Q, cand, kind): 129 targets of one leaf each, 4096 candidates"""
+    def make():
+        model = model_of(N)
+        x, P, cnllr, target, sel, own, Sown = href.make_leaves(model, (1,) * H2_L, seed=5, special=False)
+        return (x, P, cnllr, href.segments(target, H2_L), sel, own, Sown) + eref.model_matrices(model, DT) + cycle(H2_G, shift=3)
+    return _once(("h2 scene", N), make)

@@ -12,7 +12,8 @@ Every test prints the device's own ratios -- measured on an MI355X, tcpa / dcpa 
     against mpmath           N 4: 1 / 1 / 1 / 1      N 6: 1 / 1 / 1 / 1
     getEncounters            all pairs 1 / 1 / 1 / 0.056      own ship 1 / 1 / 1 / 0.39
 both builds alike: the device does the reference's operations in the reference's order, and its largest errors are the same cells'
--- and tools/encounter_cost.py writes them into profiles/encounter_cost.txt.  Nothing here is larger than 70 entries and 7 steps."""
+-- and tools/encounter_cost.py writes them into profiles/encounter_cost.txt.  Nothing here is larger than 70 entries and 7 steps.  The shapes at which the kernels go round their grid-stride loops are
+held in tests/test_encounter_strides_gpu.py."""
 import numpy as np
 import pytest
 
@@ -37,8 +38,23 @@ def ctxs():
         v.close()
 
 
-def _raw(ctx, x, P, Phi, Q, K, dt, R, first=None, nulls=(), nx=None, n=None, short=0):
-    """One call of the seam on x [n, N], P [n, N, N], the output preset to SENTINEL: (return code, out [5, first, n])"""
+GUARD_BYTE = 0xA5
+
+
+def guarded_work(need, guard, dev):
+    """The work buffer of a raw call: `need` bytes (256 at least) and `guard` bytes behind them, all of it GUARD_BYTE -- as doubles about
+    -1e-127 -- so that nothing a call forgets to write is found there from an earlier call"""
+    import torch
+    return torch.full((max(need, 256) + guard,), GUARD_BYTE, dtype=torch.uint8, device=dev)
+
+
+def guard_untouched(work, need):
+    return bool((work[max(need, 256):] == GUARD_BYTE).all())
+
+
+def _raw(ctx, x, P, Phi, Q, K, dt, R, first=None, nulls=(), nx=None, n=None, short=0, guard=0):
+    """One call of the seam on x [n, N], P [n, N, N], the output preset to SENTINEL: (return code, out [5, first, n]).  guard > 0: that
+    many bytes of a pattern lie behind the sizer's figure and must be the pattern after the call."""
     import torch
     dev = ctx.device
     N = x.shape[1]
@@ -49,13 +65,14 @@ def _raw(ctx, x, P, Phi, Q, K, dt, R, first=None, nulls=(), nx=None, n=None, sho
     arrays = dict(x=torch.from_numpy(xp).to(dev), P=torch.from_numpy(Pp).to(dev))
     out = torch.full((5, max(first, 0), max(n, 0)), SENTINEL, dtype=torch.float64, device=dev)
     need = int(ctx.lib.mht_encounter_work_bytes(len(x), min(max(K, 1), 64)))
-    work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    work = guarded_work(need, guard, dev)
     host = dict(Phi=Phi.ctypes.data, Q=Q.ctypes.data)
     ptr = lambda k: None if k in nulls else host[k] if k in host else arrays[k].data_ptr()
     torch.cuda.synchronize(dev)
     rc = ctx.lib.mht_encounters(ctx.handle, N if nx is None else nx, n, first, K, dt, R, ptr("Phi"), ptr("Q"), ptr("x"), ptr("P"),
                                 None if "out" in nulls else out.data_ptr(), None if "work" in nulls else work.data_ptr(), need - short)
     torch.cuda.synchronize(dev)
+    assert guard_untouched(work, need), "the call wrote behind the work buffer the sizer asks for"
     return rc, out.cpu().numpy()
 
 

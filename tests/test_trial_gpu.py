@@ -13,13 +13,15 @@ MI355X, tcpa / dcpa / md2 / pc:
     against mpmath           N 4: 1 / 1 / 1 / 1      N 6: 1 / 1 / 1 / 1
     getTrialManoeuvres       1 / 1 / 1 / 0.051
 both builds alike -- and tools/trial_cost.py writes them into profiles/trial_cost.txt.  Nothing here is larger than 300 tracks, 5
-candidates and 7 steps."""
+candidates and 7 steps.  The shapes at which the kernels go round their grid-stride loops are
+held in tests/test_encounter_strides_gpu.py."""
 import numpy as np
 import pytest
 
 import encounter_ref as eref
 import trial_ref as ref
 from test_encounter_cpu import RADIUS, hold
+from test_encounter_gpu import guard_untouched, guarded_work
 from test_trial_cpu import DT, cell_case, check_special_columns, check_summary, mp_case
 
 pytestmark = pytest.mark.gpu
@@ -39,8 +41,9 @@ def ctxs():
         v.close()
 
 
-def _raw(ctx, x, P, Phi, Q, K, dt, R, own, Sown, w, cand, nulls=(), nx=None, n=None, G=None, short=0):
-    """One call of the seam on x [n, N], P [n, N, N], the outputs preset to SENTINEL: (return code, out [5, G, n], summary [4, G])"""
+def _raw(ctx, x, P, Phi, Q, K, dt, R, own, Sown, w, cand, nulls=(), nx=None, n=None, G=None, short=0, guard=0):
+    """One call of the seam on x [n, N], P [n, N, N], the outputs preset to SENTINEL: (return code, out [5, G, n], summary [4, G]).
+    guard > 0: that many bytes of a pattern lie behind the sizer's figure and must be the pattern after the call."""
     import torch
     dev = ctx.device
     N = x.shape[1]
@@ -54,12 +57,13 @@ def _raw(ctx, x, P, Phi, Q, K, dt, R, own, Sown, w, cand, nulls=(), nx=None, n=N
     arrays["out"] = torch.full((5, len(cand), len(x)), SENTINEL, dtype=torch.float64, device=dev)
     arrays["summary"] = torch.full((4, len(cand)), SENTINEL, dtype=torch.float64, device=dev)
     need = int(ctx.lib.mht_trial_work_bytes(len(x), len(cand), min(max(K, 1), 64)))
-    arrays["work"] = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    arrays["work"] = guarded_work(need, guard, dev)
     ptr = lambda k: None if k in nulls else host[k].ctypes.data if k in host else arrays[k].data_ptr()
     torch.cuda.synchronize(dev)
     rc = ctx.lib.mht_trial_manoeuvres(ctx.handle, N if nx is None else nx, n, G, K, dt, R, ptr("Phi"), ptr("Q"), ptr("x"), ptr("P"), ptr("own"), ptr("Sown"), w,
                                       ptr("cand"), ptr("out"), ptr("summary"), ptr("work"), need - short)
     torch.cuda.synchronize(dev)
+    assert guard_untouched(arrays["work"], need), "the call wrote behind the work buffer the sizer asks for"
     return rc, arrays["out"].cpu().numpy(), arrays["summary"].cpu().numpy()
 
 

@@ -11,7 +11,8 @@ The properties are those tests/test_trial_hyp_cpu.py states and holds the host t
 Every case prints the worst ratio to the bound of property 8 -- measured on an MI355X over all cases here, both builds alike:
     pcMean 0.0077, weight 0.0081   (the device's exp is within an ulp where it matters: the bound is not close)
 and tools/trial_hyp_cost.py writes them into profiles/trial_hyp_cost.txt.  Nothing here is larger than 600 leaves, 3 candidates and 7
-steps."""
+steps.  The shapes at which the kernels go round their grid-stride loops are
+held in tests/test_encounter_strides_gpu.py."""
 import numpy as np
 import pytest
 
@@ -19,6 +20,7 @@ import encounter_ref as eref
 import trial_hyp_ref as ref
 import trial_ref
 from test_encounter_cpu import RADIUS
+from test_encounter_gpu import guard_untouched, guarded_work
 from test_trial_hyp_cpu import CASES, DT, LAYOUTS, check_figures, scene
 
 pytestmark = pytest.mark.gpu
@@ -38,9 +40,11 @@ def ctxs():
         v.close()
 
 
-def _raw(ctx, x, P, cnllr, seg, sel, Phi, Q, K, dt, R, own, Sown, w, cand, table=True, nulls=(), nx=None, L=None, T=None, G=None, short=0):
+def _raw(ctx, x, P, cnllr, seg, sel, Phi, Q, K, dt, R, own, Sown, w, cand, table=True, nulls=(), nx=None, L=None, T=None, G=None, short=0,
+         guard=0):
     """One call of the seam on x [L, N], P [L, N, N], the outputs preset to SENTINEL: (return code, table [5, G, L] or None, fig [8, G, T],
-    weight [L])"""
+    weight [L], the table's array whether it was passed or not).  guard > 0: that many bytes of a pattern lie behind the sizer's figure
+    and must be the pattern after the call."""
     import torch
     dev = ctx.device
     N = x.shape[1]
@@ -54,13 +58,14 @@ def _raw(ctx, x, P, cnllr, seg, sel, Phi, Q, K, dt, R, own, Sown, w, cand, table
     arrays["fig"] = torch.full((8, n_g, n_t), SENTINEL, dtype=torch.float64, device=dev)
     arrays["weight"] = torch.full((n_l,), SENTINEL, dtype=torch.float64, device=dev)
     need = int(ctx.lib.mht_trial_hyp_work_bytes(n_l, n_t, n_g, min(max(K, 1), 64)))
-    arrays["work"] = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    arrays["work"] = guarded_work(need, guard, dev)
     ptr = lambda k: None if k in nulls or (k == "table" and not table) else host[k].ctypes.data if k in host else arrays[k].data_ptr()
     torch.cuda.synchronize(dev)
     rc = ctx.lib.mht_trial_hypotheses(ctx.handle, N if nx is None else nx, n_l if L is None else L, n_t if T is None else T, n_g if G is None else G, K, dt, R,
                                       ptr("Phi"), ptr("Q"), ptr("x"), ptr("P"), ptr("cnllr"), ptr("seg"), ptr("sel"), ptr("own"), ptr("Sown"), w, ptr("cand"),
                                       ptr("table"), ptr("fig"), ptr("weight"), ptr("work"), need - short)
     torch.cuda.synchronize(dev)
+    assert guard_untouched(arrays["work"], need), "the call wrote behind the work buffer the sizer asks for"
     tab = arrays["table"].cpu().numpy()
     return rc, (tab if table else None), arrays["fig"].cpu().numpy(), arrays["weight"].cpu().numpy(), tab
 
