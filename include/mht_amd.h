@@ -716,9 +716,9 @@ int mht_mc_pair_encounters(mht_ctx* ctx, int32_t nx, int32_t transition, int32_t
  * Three launches (the factors and the fold of mht_mc_encounters; a workgroup per slab of a target's particles, a particle per lane, the
  * zones staged in LDS, a far zone skipped by a whole wavefront), no atomic.  Synchronises.
  * MHT_E_INVALID: as for mht_mc_encounters, and an nZone or nVert out of range, a zoneFirst that does not ascend from 0 to nVert in
- * strides of 3 at least, a vertex that is not finite; nothing has then been launched or written.  Out of scope: zones that move with
- * the own ship (a polygonal ship domain), open gates and polylines (a thin quadrilateral serves), holes, geodetic coordinates, the
- * dwell time inside a zone.  Exported by both builds. */
+ * strides of 3 at least, a vertex that is not finite; nothing has then been launched or written.  Zones that move with
+ * the own ship (a polygonal ship domain) are mht_mc_domain_encounters' case.  Out of scope: open gates and polylines (a thin
+ * quadrilateral serves), holes, geodetic coordinates, the dwell time inside a zone.  Exported by both builds. */
 #define MHT_MC_ZONE_MAX_ZONES 32       /* zones per call */
 #define MHT_MC_ZONE_MAX_VERTS 1024     /* vertices of all zones of a call together */
 size_t mht_mc_zone_work_bytes(int32_t nx, int32_t nComp, int32_t nTarget, int32_t nZone, int32_t steps, int32_t particles);
@@ -727,6 +727,51 @@ int mht_mc_zone_encounters(mht_ctx* ctx, int32_t nx, int32_t transition, int32_t
                            const double* P, const int32_t* first, const double* cdf, const int32_t* zoneFirst, const double* zoneXY,
                            uint32_t* inside, uint32_t* firstAt, uint32_t* ever, uint32_t* valid, int32_t* status, void* work,
                            size_t work_bytes);
+
+/* mht_mc_domain_encounters: Monte-Carlo SHIP DOMAINS -- will a target enter the safety region around the own ship, a polygon that is
+ * longer ahead than astern and usually wider to starboard than to port, with what probability within the horizon, and when, for every
+ * candidate path of the own ship -- with the engine of mht_mc_encounters: the particles are drawn and walked exactly as
+ * mht_mc_encounters walks them (the same Philox stream keyed by (seed, target), the same sums, the constant-turn model included), taken
+ * into the own ship's BODY FRAME under the pose of every (path, step) and held there against nDomain simple polygons with the geometry
+ * of mht_mc_zone_encounters (csrc/mht_mc_domain.h states the definition, every operation in one order).
+ *   nx, transition, nComp, nTarget, steps, particles, seed, dt, Phi, Q, x, P, first, cdf   as for mht_mc_encounters; there is no radius
+ *   G, nDomain       G >= 1 own paths and 1 .. MHT_MC_DOMAIN_MAX_DOMAINS domains; a (domain, path) is a CELL, cell = d * G + g, and
+ *                    nDomain * G <= MHT_MC_DOMAIN_MAX_CELLS
+ *   nVert            3 vertices per domain at least, MHT_MC_DOMAIN_MAX_VERTS in all at most
+ *   ownPose          dev [G][steps + 1][4] f64, finite: (ox, oy, ux, uy), the own ship's position and its UNIT heading vector at every
+ *                    step, |ux^2 + uy^2 - 1| <= 1e-9 (a vector, not an angle: the device evaluates no sin or cos for the transform).
+ *                    Read back and checked before anything is launched
+ *   domFirst         dev [nDomain + 1] int32: domain d owns the vertices domFirst[d] .. domFirst[d + 1] - 1; domFirst[0] = 0, ascending
+ *                    in strides of 3 at least, domFirst[nDomain] = nVert.  Read back and checked as ownPose is
+ *   domXY            dev [nVert][2] f64, finite, metres in the BODY FRAME: the first coordinate to the right of the heading, the second
+ *                    ahead (x east, y north: starboard and ahead; a domain is drawn bow-up).  Either orientation, concave allowed, no
+ *                    holes.  Read back and checked
+ *   The body-frame point of a position (X0, X1) under a pose: dx = X0 - ox, dy = X1 - oy, qx = dx * uy - dy * ux, qy = dx * ux + dy * uy.
+ *   THE BODY-FRAME PATH BETWEEN TWO STEPS IS TAKEN AS STRAIGHT, from the point under pose k - 1 to the point under pose k: exact where
+ *   the own ship does not turn between the two steps, a chord of a curved path on a step inside an arc (shorter steps are the remedy).
+ *   inside           dev [nDomain][G][steps + 1][nTarget] uint32 out: the particles inside the domain at step k
+ *   firstAt          dev [nDomain][G][steps + 1][nTarget] uint32 out: the particles that are inside the domain, or whose body-frame
+ *                    segment k - 1 -> k meets an edge of it, FIRST at step k; its sum over k is ever
+ *   ever             dev [nDomain][G][nTarget] uint32 out: the particles that enter at all; ever >= inside at every step
+ *   valid, status    dev [nTarget] out, as for mht_mc_encounters
+ *   work             dev, at least mht_mc_domain_work_bytes(nx, nComp, nTarget, G, nDomain, steps, particles) bytes (0 for arguments out
+ *                    of range)
+ * Three launches (the factors and the fold of mht_mc_encounters; a workgroup per slab of a target's particles, a particle per lane, a
+ * cell per lane of the first wavefront, the domains staged in LDS, a far cell skipped by a whole wavefront), no atomic.  Synchronises.
+ * MHT_E_INVALID: as for mht_mc_encounters, and a G, nDomain, nDomain * G or nVert out of range, a domFirst that does not ascend from 0
+ * to nVert in strides of 3 at least, a vertex or a pose that is not finite, a heading that is not a unit vector; nothing has then been
+ * launched or written.  Out of scope: domains around targets or between pairs of targets, a domain that scales with speed, the own
+ * ship's covariance, a curved body-frame path inside a turning step, holes, more than 64 cells, a stationary own ship (it has no
+ * heading: a guard ring about it is mht_mc_zone_encounters' case).  Exported by both builds. */
+#define MHT_MC_DOMAIN_MAX_DOMAINS 4    /* domains per call */
+#define MHT_MC_DOMAIN_MAX_VERTS 256    /* vertices of all domains of a call together */
+#define MHT_MC_DOMAIN_MAX_CELLS 64     /* nDomain * G */
+size_t mht_mc_domain_work_bytes(int32_t nx, int32_t nComp, int32_t nTarget, int32_t G, int32_t nDomain, int32_t steps, int32_t particles);
+int mht_mc_domain_encounters(mht_ctx* ctx, int32_t nx, int32_t transition, int32_t nComp, int32_t nTarget, int32_t G, int32_t nDomain,
+                             int32_t nVert, int32_t steps, int32_t particles, uint64_t seed, double dt, const double* Phi, const double* Q,
+                             const double* x, const double* P, const int32_t* first, const double* cdf, const double* ownPose,
+                             const int32_t* domFirst, const double* domXY, uint32_t* inside, uint32_t* firstAt, uint32_t* ever,
+                             uint32_t* valid, int32_t* status, void* work, size_t work_bytes);
 
 /* mht_gospa_steps: a tracking result scored against ground truth -- GOSPA (generalised optimal sub-pattern assignment, Rahmathullah,
  * Garcia-Fernandez, Svensson 2017, alpha = 2) of a batch of independent steps.  A step has n estimates and m true positions (2-D);

@@ -165,6 +165,8 @@ def _declare(lib, nx=4):
         "mht_mc_encounters": [vp, i32, i32, i32, i32, i32, i32, i32, C.c_uint64, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_mc_pair_encounters": [vp, i32, i32, i32, i32, i32, i32, i32, C.c_uint64, dbl, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
         "mht_mc_zone_encounters": [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_uint64, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
+        "mht_mc_domain_encounters": [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.c_uint64, dbl, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                     C.c_size_t],
         "mht_gospa_steps": [vp, i32, vp, vp, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
         "mht_ospa2_windows": [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, dbl, i32, vp, vp, vp, vp, C.c_size_t],
         "mht_kbest_hypotheses": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t],
@@ -246,6 +248,8 @@ def _declare(lib, nx=4):
     lib.mht_mc_pair_work_bytes.restype = C.c_size_t
     lib.mht_mc_zone_work_bytes.argtypes = [i32, i32, i32, i32, i32, i32]
     lib.mht_mc_zone_work_bytes.restype = C.c_size_t
+    lib.mht_mc_domain_work_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+    lib.mht_mc_domain_work_bytes.restype = C.c_size_t
     lib.mht_gospa_work_bytes.argtypes = [i32, i32, i32]
     lib.mht_gospa_work_bytes.restype = C.c_size_t
     lib.mht_ospa2_work_bytes.argtypes = [i32, i32, i32, i32]

@@ -1,5 +1,5 @@
 // INTERNAL: what the Monte-Carlo seams share across translation units.  mht_mc.hip holds the factor and the fold kernels, the layout of
-// a call's work buffer and the checks every seam makes, and DEFINES what is declared here; mht_mc_zone.hip launches through these
+// a call's work buffer and the checks every seam makes, and DEFINES what is declared here; mht_mc_zone.hip and mht_mc_domain.hip launch through these
 // declarations, so the kernels of mht_mc.hip stay in their unit (tests/test_mc_resources.py pins that unit's nine kernels).  The two
 // device helpers every walk kernel starts with are here as inline code.
 #pragma once

@@ -943,13 +943,13 @@ def _mc_arguments(who, x, P, target, weight, Phi, Q, steps, dt, radius, particle
     return dict(x=X, P=Pm, Phi=Phi, Q=Q, nx=nx, L=L, steps=int(steps), S=int(particles), order=order, targets=targets, first=first, cdf=cdf, T=T)
 
 
-def _mc_call(a, sizer, seam, extra, mid, shapes, dt, radius, seed, transition, device, ctx):
+def _mc_call(a, sizer, seam, extra, mid, shapes, dt, radius, seed, transition, device, ctx, sized=1):
     """The device call `mc_encounters` and `mc_pair_encounters` share, on `_mc_arguments`' dict `a`: x and P packed in `order`, one
     upload (with `extra`, the seam's own device input: the own paths or the pairs' ranks), the work buffer of `sizer`, one int32 tensor
     per entry of `shapes` (name -> shape, in the seam's order), the call of `seam` with `mid` as its middle size argument (G or n),
     and the arrays read back: uint32 counts, `status` int32.  A context of its own where `ctx` is None.  `mc_zone_encounters` calls
     with two device inputs (`extra` a tuple), two middle sizes (`mid` a tuple, of which the sizer takes the first) and no radius
-    (None: the seam has none)."""
+    (None: the seam has none); `mc_domain_encounters` with three of each, of which its sizer takes the first `sized` = 2 middle sizes."""
     nx, L, T, steps, S, order = a["nx"], a["L"], a["T"], a["steps"], a["S"], a["order"]
     extras = extra if isinstance(extra, tuple) else (extra,)
     mids = mid if isinstance(mid, tuple) else (mid,)
@@ -963,7 +963,7 @@ def _mc_call(a, sizer, seam, extra, mid, shapes, dt, radius, seed, transition, d
     try:
         dev, lib = ctx.device, ctx.lib
         x_d, P_d, f_d, c_d, *e_d = [torch.from_numpy(v).to(dev) for v in (xp, Pp, a["first"], a["cdf"]) + extras]
-        need = int(getattr(lib, sizer)(nx, L, T, mids[0], steps, S))
+        need = int(getattr(lib, sizer)(nx, L, T, *mids[:sized], steps, S))
         work = torch.empty(need, dtype=torch.uint8, device=dev)
         # (uint32 counts in int32 tensors: the same bits)
         out = {name: torch.empty(shape, dtype=torch.int32, device=dev) for name, shape in shapes.items()}
@@ -1222,8 +1222,8 @@ def mc_zone_encounters(x, P, target, weight, Phi, Q, steps, dt, zones, particles
     `mc_encounters`.  Derived on the host by `mc_zone_derive`, NaN where valid is 0: `pInside`, `pInsideMax`, `tInside`, `pEver`,
     `pEverBy`, `sePInsideMax`, `sePEver`.  And `zoneFirst` [Z + 1], `zoneXY` [nVert, 2], `targets` [T], `first` [T + 1], `cdf` [L] and
     `order` [L] as they were used.
-    Out of scope: zones that move with the own ship (a polygonal ship domain), open gates and polylines (a thin quadrilateral
-    serves), holes, geodetic coordinates, the dwell time inside a zone.
+    Zones that move with the own ship (a polygonal ship domain) are `mc_domain_encounters`' case.  Out of scope: open gates and
+    polylines (a thin quadrilateral serves), holes, geodetic coordinates, the dwell time inside a zone.
     One upload, one call of `mht_mc_zone_encounters` (three launches), no host fallback."""
     who = "mc_zone_encounters"
     a = _mc_arguments(who, x, P, target, weight, Phi, Q, steps, dt, 1.0, particles, seed, transition)
@@ -1239,6 +1239,136 @@ def mc_zone_encounters(x, P, target, weight, Phi, Q, steps, dt, zones, particles
         res.update(_mc_call(a, "mht_mc_zone_work_bytes", "mht_mc_zone_encounters", (zf, zxy), (Z, len(zxy)),
                             dict(inside=(Z, steps + 1, T), firstAt=(Z, steps + 1, T), ever=(Z, T), valid=(T,), status=(T,)), dt, None, seed, transition, device, ctx))
     res.update(mc_zone_derive(res["inside"], res["firstAt"], res["ever"], res["valid"], float(dt)))
+    return res
+
+
+# ---- ship domains by Monte Carlo: a polygon carried along the own ship's paths ---------------------------------------------------------
+MC_DOMAIN_MAX_DOMAINS, MC_DOMAIN_MAX_VERTS, MC_DOMAIN_MAX_CELLS = 4, 256, 64      # MHT_MC_DOMAIN_*, include/mht_amd.h
+MC_DOMAIN_COUNT_NAMES = ("inside", "firstAt", "ever", "valid", "status")
+
+
+def mc_own_poses(own, candidates, turnRate, steps, dt):
+    """The own ship's POSES at t = k dt, k = 0 .. steps, for every candidate manoeuvre (dpsi, f, t0): float64 [G, steps + 1, 4] =
+    (x, y, ux, uy).  Columns 0:2 are `mc_own_paths`' positions, bit for bit (it is called, not restated); columns 2:4 are the unit
+    heading vector: u0 = v0 / hypot(v0x, v0y) rotated by the manoeuvre's own angle -- 0 until t0, sg w (t - t0) on the arc,
+    sg |dpsi| after te = t0 + |dpsi| / w, counter-clockwise for dpsi > 0 as csrc/mht_trial.h defines a candidate --, with sin and cos of
+    those angles.  An own ship of speed 0 has no heading: ValueError (a stationary ship with a guard ring is `mc_zone_encounters`'
+    case).  A NaN in a candidate or in `own` makes that candidate's poses NaN.  ValueError otherwise as `mc_own_paths` raises them."""
+    try:
+        paths = mc_own_paths(own, candidates, turnRate, steps, dt)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("mc_own_paths", "mc_own_poses", 1))
+    w, dt = float(turnRate), float(dt)
+    cand = trial_candidates(candidates)
+    _, _, v0x, v0y = np.ascontiguousarray(own, dtype=np.float64)
+    speed = np.hypot(v0x, v0y)
+    if speed == 0:
+        raise ValueError("mc_own_poses: an own ship of speed 0 has no heading (got own = %r)" % (own,))
+    u0x, u0y = v0x / speed, v0y / speed
+    dpsi, t0 = cand[:, 0], cand[:, 2]
+    out = np.zeros((len(cand), int(steps) + 1, 4))
+    out[:, :, :2] = paths
+    with np.errstate(all="ignore"):
+        ad = np.abs(dpsi)
+        sg = np.where(dpsi > 0, 1.0, np.where(dpsi < 0, -1.0, 0.0))
+        te = t0 + ad / w
+        for k in range(int(steps) + 1):
+            t = float(k) * dt
+            ang = np.where(t <= t0, 0.0, np.where(t <= te, sg * (w * (t - t0)), sg * ad))
+            s, c = np.sin(ang), np.cos(ang)
+            out[:, k, 2] = c * u0x - s * u0y
+            out[:, k, 3] = s * u0x + c * u0y
+    out[np.isnan(paths).any(axis=(1, 2))] = np.nan
+    return out
+
+
+def mc_domain_pack(domains, who="mc_domain_pack"):
+    """A list of polygons in the own ship's BODY FRAME (first coordinate to the right of the heading, second ahead; drawn bow-up), each a
+    finite [V, 2] array with V >= 3, as `mht_mc_domain_encounters` takes them: (domFirst int32 [nDomain + 1], domXY float64 [nVert, 2]).
+    At most 4 domains and 256 vertices in all.  ValueError (under the caller's name `who`) otherwise."""
+    if isinstance(domains, np.ndarray) and domains.ndim != 3:
+        raise ValueError("%s: domains is a LIST of [V, 2] arrays, one per domain (got an array of shape %r)" % (who, domains.shape))
+    try:
+        polys = [np.asarray(d, dtype=np.float64) for d in domains]
+    except (TypeError, ValueError):
+        raise ValueError("%s: domains is a list of [V, 2] arrays of numbers (got %r)" % (who, domains))
+    if len(polys) > MC_DOMAIN_MAX_DOMAINS:
+        raise ValueError("%s: at most %d domains (got %d)" % (who, MC_DOMAIN_MAX_DOMAINS, len(polys)))
+    for d, poly in enumerate(polys):
+        if poly.ndim != 2 or poly.shape[1] != 2 or len(poly) < 3:
+            raise ValueError("%s: domain %d is a [V, 2] array with V >= 3 (got shape %r)" % (who, d, poly.shape))
+        if not np.isfinite(poly).all():
+            raise ValueError("%s: domain %d has a vertex that is not finite" % (who, d))
+    first = np.concatenate([[0], np.cumsum([len(p) for p in polys])]).astype(np.int32)
+    if first[-1] > MC_DOMAIN_MAX_VERTS:
+        raise ValueError("%s: at most %d vertices in all domains together (got %d)" % (who, MC_DOMAIN_MAX_VERTS, int(first[-1])))
+    xy = np.concatenate(polys, axis=0) if polys else np.zeros((0, 2))
+    return first, np.ascontiguousarray(xy, dtype=np.float64)
+
+
+def mc_domain_derive(inside, firstAt, ever, valid, dt):
+    """The host's figures of `mc_domain_encounters` from its counts (inside, firstAt [nDomain, G, K + 1, T]; ever [nDomain, G, T]; valid
+    [T]): `mc_zone_derive`'s fields -- pInside, pInsideMax, tInside, pEver, pEverBy, sePInsideMax, sePEver, NaN where valid is 0 -- over
+    the cell axes [nDomain, G]."""
+    inside, firstAt, ever = np.asarray(inside), np.asarray(firstAt), np.asarray(ever)
+    D, G, K1, T = inside.shape
+    d = mc_zone_derive(inside.reshape(D * G, K1, T), firstAt.reshape(D * G, K1, T), ever.reshape(D * G, T), valid, dt)
+    return {k: v.reshape((D, G) + v.shape[1:]) for k, v in d.items()}
+
+
+def mc_domain_encounters(x, P, target, weight, Phi, Q, steps, dt, domains, ownPoses, particles=4096, seed=0, transition="linear", device=0, ctx=None):
+    """SHIP DOMAINS by MONTE CARLO: will a target enter the safety region AROUND THE OWN SHIP -- a polygon, longer ahead than astern and
+    usually wider to starboard than to port, that translates and rotates with the ship --, with what probability within the horizon,
+    and when, for every candidate path of the own ship.  A disc (`mc_encounters`) cannot tell "passes 300 m astern" from "passes 300 m
+    ahead", and a fixed zone (`mc_zone_encounters`) cannot follow a candidate manoeuvre.  The engine is theirs (csrc/mht_mc_domain.h
+    states the definition): exactly the particles they walk for the same seed, taken into the own ship's body frame under the pose of
+    every (path, step) and held there against every domain with `mc_zone_encounters`' geometry -- a point-in-polygon test at every step
+    and the segment between two steps against the domain's edges.
+
+    x, P, target, weight, Phi, Q, steps, dt, particles, seed, transition   as for `mc_encounters`; there is no radius
+    domains    a list of at most 4 simple polygons IN THE BODY FRAME, each a finite [V, 2] array of vertices in metres, V >= 3, at most
+               256 vertices in all: THE FIRST COORDINATE IS TO THE RIGHT OF THE HEADING, THE SECOND AHEAD (x east, y north: starboard
+               and ahead; a domain is drawn bow-up).  Either orientation, concave allowed, no holes
+    ownPoses   [G, steps + 1, 4] = (x, y, ux, uy), finite, G >= 1 and nDomain * G <= 64: the own ship's position and UNIT heading vector
+               (|ux^2 + uy^2 - 1| <= 1e-9) at every step, e.g. `mc_own_poses`
+    THE BODY-FRAME PATH BETWEEN TWO STEPS IS TAKEN AS STRAIGHT, from the point under pose k - 1 to the point under pose k: exact where the
+    own ship does not turn between the two steps, a chord of a curved path on a step inside an arc.  Shorter steps during a manoeuvre
+    are the remedy.
+    ValueError for arguments that do not fit -- before any device is needed.  No component: empty arrays and no device call.
+    Returns a dict.  As the device wrote them: `inside` and `firstAt` [nDomain, G, steps + 1, T], `ever` [nDomain, G, T] (the counts of
+    `mc_zone_encounters` per (domain, path)), `valid` [T] and `status` [T].  Derived on the host by `mc_domain_derive`, NaN where valid
+    is 0: `pInside`, `pInsideMax`, `tInside`, `pEver`, `pEverBy`, `sePInsideMax`, `sePEver`.  And `domFirst`, `domXY`, `ownPoses`,
+    `targets` [T], `first` [T + 1], `cdf` [L] and `order` [L] as they were used.
+    Out of scope: domains around targets or between pairs of targets, a domain that scales with speed, the own ship's covariance, a
+    curved body-frame path inside a turning step, holes, more than 64 cells, a stationary own ship.
+    One upload, one call of `mht_mc_domain_encounters` (three launches), no host fallback."""
+    who = "mc_domain_encounters"
+    a = _mc_arguments(who, x, P, target, weight, Phi, Q, steps, dt, 1.0, particles, seed, transition)
+    L, steps, order, targets, first, cdf, T = a["L"], a["steps"], a["order"], a["targets"], a["first"], a["cdf"], a["T"]
+    df, dxy = mc_domain_pack(domains, who)
+    D = len(df) - 1
+    if D < 1:
+        raise ValueError("%s: one domain at least is wanted" % who)
+    try:
+        pose = np.ascontiguousarray(ownPoses, dtype=np.float64)
+    except (TypeError, ValueError):
+        pose = np.zeros(0)
+    if pose.ndim != 3 or pose.shape[1:] != (steps + 1, 4) or len(pose) < 1 or not np.isfinite(pose).all():
+        raise ValueError("%s: ownPoses is a finite [G, steps + 1, 4] = [G, %d, 4] array, G >= 1 (got shape %r)" % (who, steps + 1, pose.shape))
+    G = len(pose)
+    if D * G > MC_DOMAIN_MAX_CELLS:
+        raise ValueError("%s: at most %d cells, nDomain * G (got %d domains x %d paths)" % (who, MC_DOMAIN_MAX_CELLS, D, G))
+    if (np.abs(pose[..., 2] * pose[..., 2] + pose[..., 3] * pose[..., 3] - 1.0) > 1e-9).any():
+        raise ValueError("%s: every heading (ownPoses[..., 2:4]) is a unit vector, |ux^2 + uy^2 - 1| <= 1e-9" % who)
+    res = dict(domFirst=df, domXY=dxy, ownPoses=pose, targets=targets.astype(np.int64), first=first, cdf=cdf, order=order.astype(np.int64))
+    if L == 0:
+        res.update(inside=np.zeros((D, G, steps + 1, 0), dtype=np.uint32), firstAt=np.zeros((D, G, steps + 1, 0), dtype=np.uint32),
+                   ever=np.zeros((D, G, 0), dtype=np.uint32), valid=np.zeros(0, dtype=np.uint32), status=np.zeros(0, dtype=np.int32))
+    else:
+        res.update(_mc_call(a, "mht_mc_domain_work_bytes", "mht_mc_domain_encounters", (pose, df, dxy), (G, D, len(dxy)),
+                            dict(inside=(D, G, steps + 1, T), firstAt=(D, G, steps + 1, T), ever=(D, G, T), valid=(T,), status=(T,)), dt, None, seed, transition, device,
+                            ctx, sized=2))
+    res.update(mc_domain_derive(res["inside"], res["firstAt"], res["ever"], res["valid"], float(dt)))
     return res
 
 

@@ -1548,6 +1548,33 @@ class Tracker():
             nx, Phi, Q = evaluation.encounter_model(model, dt)
         return steps, dt, nx, Phi, Q, ct
 
+    def _mc_candidates(self, name, horizon, radius, steps, ownShip, courseChanges, turnRate, speedFactors, delay, make):
+        """The candidate handling getMonteCarloEncounters and getMonteCarloDomainEncounters share, ValueError under the caller's `name`:
+        the delay, `_mc_horizon`, the own ship, the candidates (every course change with every speed factor, at most 64, none NaN) and
+        what `make` (evaluation.mc_own_paths or evaluation.mc_own_poses) makes of them.  (steps, dt, nx, Phi, Q, ct, cand [G, 3], made)."""
+        from . import evaluation
+        if isinstance(delay, bool) or not isinstance(delay, (int, float, np.integer, np.floating)) or not np.isfinite(delay) or delay < 0:
+            raise ValueError("%s: delay must be a finite number >= 0 (got %r)" % (name, delay))
+        steps, dt, nx, Phi, Q, ct = self._mc_horizon(name, horizon, radius, steps)
+        own = np.asarray(ownShip, dtype=np.float64).reshape(-1)
+        if len(own) != 4 or not np.isfinite(own).all():
+            raise ValueError("%s: ownShip is a finite [x, y, vx, vy] (got %r)" % (name, ownShip))
+        dpsi, fs = np.asarray(courseChanges, dtype=np.float64).reshape(-1), np.asarray(speedFactors, dtype=np.float64).reshape(-1)
+        if len(dpsi) == 0 or len(fs) == 0:
+            raise ValueError("%s: courseChanges and speedFactors need one value at least" % name)
+        if turnRate is None:
+            if np.any(dpsi != 0):
+                raise ValueError("%s: turnRate is required with a course change that is not 0" % name)
+            turnRate = 1.0      # (no candidate turns: the rate enters no figure)
+        try:
+            cand = evaluation.trial_candidates([(a, f, float(delay)) for a in dpsi for f in fs])
+            if len(cand) > evaluation.MC_MAX_PATHS or np.isnan(cand).any():
+                raise ValueError("at most %d candidates, none of them NaN (got %d)" % (evaluation.MC_MAX_PATHS, len(cand)))
+            made = make(own, cand, turnRate, steps, dt)
+        except ValueError as exc:
+            raise ValueError("%s: %s" % (name, exc))
+        return steps, dt, nx, Phi, Q, ct, cand, made
+
     def getMonteCarloEncounters(self, horizon, radius, ownShip, particles=4096, seed=0, courseChanges=(0.0,), turnRate=None, speedFactors=(1.0,), delay=0.0,
                                 steps=None, hypotheses=True, weights=None):
         """Encounters by MONTE CARLO (evaluation.mc_encounters defines the figures): particles drawn from the forest's own leaves -- a
@@ -1577,26 +1604,8 @@ class Tracker():
         candidate has a figure.  No live track: empty arrays, no device call."""
         from . import evaluation
         name = "getMonteCarloEncounters"
-        if isinstance(delay, bool) or not isinstance(delay, (int, float, np.integer, np.floating)) or not np.isfinite(delay) or delay < 0:
-            raise ValueError("%s: delay must be a finite number >= 0 (got %r)" % (name, delay))
-        steps, dt, nx, Phi, Q, ct = self._mc_horizon(name, horizon, radius, steps)
-        own = np.asarray(ownShip, dtype=np.float64).reshape(-1)
-        if len(own) != 4 or not np.isfinite(own).all():
-            raise ValueError("%s: ownShip is a finite [x, y, vx, vy] (got %r)" % (name, ownShip))
-        dpsi, fs = np.asarray(courseChanges, dtype=np.float64).reshape(-1), np.asarray(speedFactors, dtype=np.float64).reshape(-1)
-        if len(dpsi) == 0 or len(fs) == 0:
-            raise ValueError("%s: courseChanges and speedFactors need one value at least" % name)
-        if turnRate is None:
-            if np.any(dpsi != 0):
-                raise ValueError("%s: turnRate is required with a course change that is not 0" % name)
-            turnRate = 1.0      # (no candidate turns: the rate enters no figure)
-        try:
-            cand = evaluation.trial_candidates([(a, f, float(delay)) for a in dpsi for f in fs])
-            if len(cand) > evaluation.MC_MAX_PATHS or np.isnan(cand).any():
-                raise ValueError("at most %d candidates, none of them NaN (got %d)" % (evaluation.MC_MAX_PATHS, len(cand)))
-            paths = evaluation.mc_own_paths(own, cand, turnRate, steps, dt)
-        except ValueError as exc:
-            raise ValueError("%s: %s" % (name, exc))
+        steps, dt, nx, Phi, Q, ct, cand, paths = self._mc_candidates(name, horizon, radius, steps, ownShip, courseChanges, turnRate, speedFactors, delay,
+                                                                     evaluation.mc_own_paths)
         x, P, tg, leaf_ids, w, ids = self._mc_leaves(name, nx, hypotheses, weights)
         try:
             out = evaluation.mc_encounters(x, P, tg, w, Phi, Q, steps, dt, float(radius), paths, particles=particles, seed=seed,
@@ -1687,8 +1696,8 @@ class Tracker():
         result, in its order), `leafIds` (the target id of every leaf used) and `ranking` [n, 2]: the (zone, target) cells by
         descending pEver, ties by zone and then target, cells without a figure last.  No live target or no zone: empty arrays, no
         device call.
-        Out of scope: zones that move with the own ship (a polygonal ship domain), open gates and polylines (a thin quadrilateral
-        serves), holes, geodetic coordinates, the dwell time inside a zone."""
+        Zones that move with the own ship (a polygonal ship domain) are getMonteCarloDomainEncounters' case.  Out of scope: open gates
+        and polylines (a thin quadrilateral serves), holes, geodetic coordinates, the dwell time inside a zone."""
         from . import evaluation
         name = "getMonteCarloZoneEncounters"
         steps, dt, nx, Phi, Q, ct = self._mc_horizon(name, horizon, 1.0, steps)
@@ -1711,6 +1720,60 @@ class Tracker():
         flat = p.reshape(-1)
         order = np.lexsort((np.arange(Z * T), np.where(np.isnan(flat), np.inf, -flat)))
         out["ranking"] = np.stack([zz[order], tt[order]], axis=1).astype(np.int64).reshape(-1, 2)
+        return out
+
+    def getMonteCarloDomainEncounters(self, horizon, domains, ownShip, particles=4096, seed=0, courseChanges=(0.0,), turnRate=None, speedFactors=(1.0,), delay=0.0,
+                                      steps=None, hypotheses=True, weights=None):
+        """SHIP DOMAINS by MONTE CARLO (evaluation.mc_domain_encounters defines the figures): will a target enter the safety region
+        AROUND THE OWN SHIP -- a polygon in the ship's body frame, longer ahead than astern and usually wider to starboard than to port,
+        carried along and turned with every candidate path --, with what probability within `horizon`, and when.  The disc of
+        getMonteCarloEncounters cannot tell a target that passes astern from one that passes ahead; the zones of
+        getMonteCarloZoneEncounters stand still.  The engine is theirs: particles drawn from the forest's own leaves, a Gaussian mixture
+        per target, walked with the model's process noise, the same particles for the same seed.  Works for models/pv, models/ca and
+        models/ct.  Times count from the current scan.
+
+        horizon, ownShip, courseChanges, turnRate, speedFactors, delay, steps, particles, seed, hypotheses, weights   as for
+                       getMonteCarloEncounters; the own ship must move (a ship of speed 0 has no heading: ValueError)
+        domains        a list of 1 .. 4 [V, 2] arrays: the vertices of every domain in metres IN THE BODY FRAME, the first coordinate to
+                       the right of the heading and the second ahead (drawn bow-up), 3 vertices each at least, 256 in all at most;
+                       (domains) x (candidates) <= 64 cells.  THE DECIDING DOMAIN GOES FIRST: `best` looks at domain 0 alone (an inner
+                       "collision" domain first, an outer "comfort" domain behind it)
+        The body-frame path between two steps is taken as STRAIGHT: on a step inside a turn of the own ship it is a chord of a curved
+        path (shorter steps are the remedy).
+        Returns evaluation.mc_domain_encounters' dict -- inside, firstAt, ever, valid, status, pInside, pInsideMax, tInside, pEver,
+        pEverBy, sePInsideMax, sePEver, domFirst, domXY, ownPoses, targets, first, cdf, order -- plus `ids` (the id of every target of
+        the result, in its order), `leafIds` (the target id of every leaf used), `candidates` [G, 3], per (domain, candidate) `pEverMax`
+        [nDomain, G] with `pEverMaxTarget` (the largest pEver over the targets and its index into the result's targets; NaN and -1
+        without a figure) and `best`: the candidate with the smallest pEverMax of DOMAIN 0, among equal ones the lowest index; None if
+        no candidate has a figure.  No live track: empty arrays, no device call.
+        Out of scope: domains around targets or between pairs of targets, a domain that scales with speed, the own ship's covariance,
+        a curved body-frame path inside a turning step, holes, more than 64 cells, a stationary own ship."""
+        from . import evaluation
+        name = "getMonteCarloDomainEncounters"
+        steps, dt, nx, Phi, Q, ct, cand, poses = self._mc_candidates(name, horizon, 1.0, steps, ownShip, courseChanges, turnRate, speedFactors, delay,
+                                                                     evaluation.mc_own_poses)
+        try:
+            df, _ = evaluation.mc_domain_pack(domains, name)      # (before the leaves are gathered: a domain that does not fit costs no device read)
+            if (len(df) - 1) * len(cand) > evaluation.MC_DOMAIN_MAX_CELLS:
+                raise ValueError("%s: at most %d cells, (domains) x (candidates) (got %d x %d)" % (name, evaluation.MC_DOMAIN_MAX_CELLS, len(df) - 1, len(cand)))
+            x, P, tg, leaf_ids, w, ids = self._mc_leaves(name, nx, hypotheses, weights)
+            out = evaluation.mc_domain_encounters(x, P, tg, w, Phi, Q, steps, dt, domains, poses, particles=particles, seed=seed,
+                                                  transition="ct" if ct else "linear", ctx=self._ctx)
+        except ValueError as exc:
+            text = str(exc)
+            raise ValueError(text if text.startswith(name) else "%s: %s" % (name, text))
+        out["ids"] = [ids[t] if t < len(ids) else -1 for t in out["targets"]]
+        out["leafIds"], out["candidates"] = leaf_ids, cand
+        D, G = out["pEver"].shape[:2]
+        val, arg = np.full((D, G), np.nan), np.full((D, G), -1, dtype=np.int64)
+        for d in range(D):
+            for g in range(G):
+                row = out["pEver"][d, g]
+                if len(row) and not np.isnan(row).all():
+                    val[d, g] = np.nanmax(row)
+                    arg[d, g] = int(np.flatnonzero(row == val[d, g])[0])
+        out["pEverMax"], out["pEverMaxTarget"] = val, arg
+        out["best"] = evaluation.trial_best(val[0], np.zeros(G))
         return out
 
     def leafRows(self):
