@@ -9,6 +9,8 @@ capped at 2048 workgroups of 256 lanes -- with the references' evaluations of th
     T3  trial manoeuvres  n = 1, G = 4096           4096 tiles of one live lane, the summary's grid strides
     H1  trial hypotheses  L = 513, T = 4, G = 683   segments 250, 12, 250, 1: 3 chunks, 2049 tiles
     H2  trial hypotheses  L = T = 129, G = 4096     528 384 (g, t): the target kernel strides
+    H3  trial hypotheses  L = 524 588, T = 524 573, G = 1   the weight and the propagate kernel stride; ten targets of two or three
+                                                    leaves behind target 524 288
 
 K = 1, dt = 5, R = 80 everywhere.  The large tables are a FLEET: entries spread over +-500 km, so that the rule gives pc = 0 exactly for
 almost all of them, and a few hundred entries PLANTED next to the own ship at the indices where an indexing slip would show."""
@@ -28,6 +30,10 @@ T2_N, T2_G, T2_NAN = 257, 1025, 600
 T3_G = 4096
 H1_SIZES, H1_G, H1_NO_SELECTED = (250, 12, 250, 1), 683, 2
 H2_L, H2_G = 129, 4096
+# H3: the fleet as leaves, one a target but for ten targets of two and three leaves in turn, every tenth from target 524 290 on: their
+# leaves, 524 290 .. 524 395, are planted ones
+H3_MULTI, H3_SIZES = 524290 + 10 * np.arange(10), np.tile([2, 3], 5)
+H3_T = BIG - int(np.sum(H3_SIZES - 1))
 # planted entries: tile 0; around 255 / 256 / 257; around 524 287 / 524 288 / 524 289 and on into tile 2048; all of the last tile (2049),
 # which holds 44 entries
 PLANTED = np.concatenate([np.arange(1, 100), np.arange(250, 263), np.arange(524280, 524401), np.arange(2049 * TILE, BIG)])
@@ -226,3 +232,27 @@ def h2_scene(N=4):
         x, P, cnllr, target, sel, own, Sown = href.make_leaves(model, (1,) * H2_L, seed=5, special=False)
         return (x, P, cnllr, href.segments(target, H2_L), sel, own, Sown) + eref.model_matrices(model, DT) + cycle(H2_G, shift=3)
     return _once(("h2 scene", N), make)
+
+
+def h3_scene(N=4):
+    """(x, P, cnllr, seg, sel, own, Sown, Phi, Q, cand): E2's kind of fleet as 524 588 leaves of 524 573 targets, cnllr uniform over 0 ..
+    12, sel the leaf with the smallest cnllr of each target, one candidate"""
+    def make():
+        model = model_of(N)
+        x, P = fleet(model, seed=13, near=5.0, far=150.0, dv=1.0)
+        sizes = np.ones(H3_T, dtype=np.int64)
+        sizes[H3_MULTI] = H3_SIZES
+        seg = href.segments(np.repeat(np.arange(H3_T), sizes), H3_T)
+        cnllr = np.random.default_rng(13).uniform(0.0, 12.0, BIG)
+        sel = seg[:-1].copy()
+        for t in H3_MULTI:
+            sel[t] = seg[t] + int(np.argmin(cnllr[seg[t]:seg[t + 1]]))
+        return (x, P, cnllr, seg, sel, OWN.copy(), tref.OWN_COV.copy()) + eref.model_matrices(model, DT) + (T1_CANDIDATE,)
+    return _once(("h3 scene", N), make)
+
+
+def h3(N=4, truth=True):
+    """h3_scene and (f64, truth) of its table, trial_ref.manoeuvres with the leaves as the tracks"""
+    sc = h3_scene(N)
+    x, P, cnllr, seg, sel, own, Sown, Phi, Q, cand = sc
+    return sc + _both(("h3", N), tref.manoeuvres, (x, P, Phi, Q, K, DT, RADIUS, own, Sown, tref.TURN_RATE, cand), truth)

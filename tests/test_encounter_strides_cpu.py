@@ -47,6 +47,11 @@ def test_every_case_lies_behind_the_threshold_it_is_there_for():
     assert tiles(u.H1_G, L) == 2049 > cap >= tiles(u.H1_G - 1, L) and ceil_div(L, tile) == 3 and ceil_div(L - 1, tile) == 2
     assert u.H2_G == most and u.H2_G * u.H2_L == 528384 > entries >= u.H2_G * (u.H2_L - 1)
     assert tiles(u.H2_G, u.H2_L) == 4096 > cap
+    # H3: the weight kernel (a target a lane) and the propagate kernel (a leaf a lane) stride; the targets of several leaves lie in the
+    # weight kernel's second trip and their leaves, planted ones, in the propagate kernel's
+    assert u.H3_T == 524573 > entries and u.BIG > entries + tile and (u.H3_MULTI >= entries).all() and len(u.H3_MULTI) >= 8
+    assert set(u.H3_SIZES.tolist()) == {2, 3} and u.H3_T + int(np.sum(u.H3_SIZES - 1)) == u.BIG
+    assert np.isin(np.arange(u.H3_MULTI[0], u.H3_MULTI[-1] + int(np.sum(u.H3_SIZES - 1)) + 1), u.PLANTED).all()
     # the planted entries and the ties sit where they are meant to
     assert {0, 1, 2047, 2048, 2049} <= set((u.PLANTED // tile).tolist()) and {255, 256, 257, 524287, 524288, 524289, u.BIG - 1} <= set(u.PLANTED.tolist())
     for a, b in u.TIES_SAME_LANE:
@@ -91,6 +96,19 @@ def test_t1_has_live_cells_in_the_four_places_and_its_ties_are_the_rows_extremes
     x, P = u.t1_scene(4)[:2]
     for a, b in u.TIES_SAME_LANE:
         assert np.array_equal(x[a], x[b]) and np.array_equal(P[a], P[b])
+
+
+def test_h3_has_live_cells_in_the_four_places_and_its_targets_of_several_leaves_are_live():
+    x, P, cnllr, seg, sel, own, Sown, Phi, Q, cand, f64, _ = u.h3(4, truth=False)
+    live_in_every_place(f64["pc"][0])
+    assert len(seg) == u.H3_T + 1 and seg[-1] == u.BIG == len(x) and np.array_equal(np.diff(seg)[u.H3_MULTI], u.H3_SIZES) and int(np.diff(seg).max()) == 3
+    assert np.array_equal(seg[:u.H3_MULTI[0] + 1], np.arange(u.H3_MULTI[0] + 1)) and ((seg[:-1] <= sel) & (sel < seg[1:])).all()
+    good = 0
+    for t in u.H3_MULTI:
+        c, pc = cnllr[seg[t]:seg[t + 1]], f64["pc"][0, seg[t]:seg[t + 1]]
+        good += len(set(c.tolist())) == len(c) and int(np.sum(pc > 0)) >= 2 and len(set(pc[pc > 0].tolist())) >= 2
+    print("H3: %d targets behind 524 288 have two or three leaves of different cnllr with different pc > 0" % good)
+    assert good >= 8
 
 
 def test_the_candidate_scenes_are_as_stated():

@@ -12,6 +12,7 @@ cases here (tests/encounter_stride_util.py) are the smallest that reach each of 
     T3  n = 1, G = 4096            every tile has one live lane, a cell workgroup makes two trips, trial_summary_kernel's grid strides
     H1  L = 513, T = 4, G = 683    segments of 250, 12, 250 and 1 leaves: 3 chunks, 2049 tiles of hyp_cell_kernel
     H2  L = T = 129, G = 4096      528 384 (candidate, target): hyp_target_kernel strides
+    H3  L = 524 588, T = 524 573, G = 1   hyp_weight_kernel (a target a lane) and hyp_propagate_kernel (a leaf a lane) stride
 
 The criterion is the project's, test_encounter_cpu.hold as the 70-entry cell cases use it: per figure e = max |got - truth| / (1 + |truth|)
 <= 8 max(e_np, eps64) against the np.longdouble truth (pc: the float64 rule on the longdouble d_k and Sigma_k, with e_np from the mpmath
@@ -21,8 +22,7 @@ each is held to the reference, and the summary is trial_ref.fold of the device's
 outputs to a sentinel, none of which may be left, and has 4 KB of a pattern behind the work buffer the sizer asks for, which must be
 untouched: an overrun from a wrong stride lands there.
 
-NOT held: hyp_weight_kernel's stride (T > 524 288 targets) and hyp_propagate_kernel's (L > 524 288 leaves) -- they run the loop form that
-E2 and T1 exercise and would need a forest of 524 289 leaves -- and the Monte-Carlo and NEES launches, which have the same cap.
+The Monte-Carlo and the NEES launches, which have the same cap, are held in tests/test_mc_strides_gpu.py and test_nees_strides_gpu.py.
 
 Every test prints the device's ratios, the time of the seam's call and the time of its reference; profiles/encounter_stride_shapes.txt
 records them -- measured on an MI355X, tcpa / dcpa / md2 / pc:
@@ -44,6 +44,7 @@ from test_encounter_gpu import SENTINEL
 from test_encounter_gpu import _raw as raw_encounters
 from test_trial_cpu import check_summary, mp_case
 from test_trial_gpu import _raw as raw_trial
+from test_encounter_strides_cpu import live_in_every_place
 from test_trial_hyp_cpu import check_figures
 from test_trial_hyp_gpu import _raw as raw_hyp
 
@@ -240,3 +241,42 @@ def test_h2_4096_candidates_against_129_targets_of_one_leaf_the_target_kernel_st
     assert np.array_equal(fig[2], table[1], equal_nan=True) and np.array_equal(fig[6], table[1], equal_nan=True) and np.array_equal(fig[7], table[0], equal_nan=True)
     assert np.array_equal(fig[1], np.where(np.isnan(table[3]), -1, leaf)) and np.array_equal(fig[3], np.where(np.isnan(table[1]), -1, leaf))
     assert int(np.sum(table[3] > 0)) >= 64 * 20
+
+
+def test_h3_524573_targets_the_weight_and_the_propagate_kernel_stride(ctxs):
+    """H3, models/pv on the four-state build, table = NULL: 524 588 leaves of 524 573 targets, G = 1, K = 1.  hyp_weight_kernel's second
+    trip is targets 524 288 .. 524 572, ten of them with two or three leaves of different cnllr; hyp_propagate_kernel's is leaves
+    524 288 .. 524 587, planted beside the own ship.  The criterion is held_hypotheses' with the table taken from mht_trial_manoeuvres
+    on the same leaves (the call has none): that table to the truth, every cell; check_figures -- whose fold is a Python loop over the
+    targets -- on the targets from 524 280 on, the leaves 524 280 .. 524 587 with all the targets of several leaves among them; and
+    for the 524 280 targets of one leaf before them property 4 on the whole rows, bit for bit: every figure is the leaf's cell, the
+    weight is 1."""
+    label = "H3 L 524588 T 524573 G 1, pv, 4-state build"
+    x, P, cnllr, seg, sel, own, Sown, Phi, Q, cand, f64, truth = reference(label, lambda: u.h3(4))
+    ctx, args = ctxs[4], (Phi, Q, K, DT, RADIUS, own, Sown, tref.TURN_RATE)
+    with seam_time(label, ctx, "mht_trial_hypotheses"):
+        rc, _, fig, weight, untouched = raw_hyp(ctx, x, P, cnllr, seg, sel, *args, cand, table=False, guard=GUARD)
+    assert rc == 0 and not (fig == SENTINEL).any() and not (weight == SENTINEL).any() and (untouched == SENTINEL).all()
+    rc, table, _ = raw_trial(ctx, x, P, *args, cand, guard=GUARD)
+    assert rc == 0 and not (table == SENTINEL).any()
+    got = eref.seam_dict(table)
+    hold(label, got, truth, f64, DT, pc_scale=trial_scale(4))
+    live_in_every_place(got["pc"][0])
+    # the targets of one leaf in front: leaf l is target l
+    t0 = 524280
+    assert np.array_equal(seg[:t0 + 1], np.arange(t0 + 1)) and t0 < u.H3_MULTI[0] and np.isfinite(cnllr).all()
+    leaf = np.arange(t0)
+    nan = lambda row: np.isnan(row[0, :t0])
+    assert all(np.array_equal(fig[f][:, :t0], table[3][:, :t0], equal_nan=True) for f in (0, 4, 5)) and (weight[:t0] == 1.0).all()
+    assert np.array_equal(fig[2][:, :t0], table[1][:, :t0], equal_nan=True) and np.array_equal(fig[6][:, :t0], table[1][:, :t0], equal_nan=True)
+    assert np.array_equal(fig[7][:, :t0], table[0][:, :t0], equal_nan=True)
+    assert np.array_equal(fig[1][0, :t0], np.where(nan(table[3]), -1, leaf)) and np.array_equal(fig[3][0, :t0], np.where(nan(table[1]), -1, leaf))
+    # the rest, behind the threshold but for eight leaves: the fold in np.longdouble, with the leaves numbered from t0 on
+    t = time.perf_counter()
+    tail = fig[:, :, t0:].copy()
+    for f in (1, 3):
+        tail[f] = np.where(tail[f] >= 0, tail[f] - t0, tail[f])
+    r_mean, r_weight = check_figures(label, tail, weight[t0:], table[:, :, t0:], cnllr[t0:], seg[t0:] - t0, np.where(sel[t0:] >= 0, sel[t0:] - t0, -1))
+    print("%s: check_figures on %d targets %.1f s" % (label, u.H3_T - t0, time.perf_counter() - t))
+    several = [int(tt) for tt in u.H3_MULTI if np.nansum(weight[seg[tt]:seg[tt + 1]] > 0) >= 2 and fig[4][0, tt] > 0]
+    assert len(several) >= 8 and all(0 < weight[seg[tt]:seg[tt + 1]].max() < 1 for tt in several)

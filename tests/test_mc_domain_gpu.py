@@ -13,11 +13,13 @@ import encounter_ref as eref
 import mc_domain_ref as dref
 import mc_ref as ref
 import mc_zone_ref as zref
+from test_encounter_gpu import GUARD_BYTE, guard_untouched, guarded_work
 from test_mc_domain_cpu import check_shape
 from test_mc_gpu import _scans, _weights
 
 pytestmark = pytest.mark.gpu
 GUARD = 256      # bytes behind the work buffer that no call may touch
+assert GUARD_BYTE == 0xA5      # (the tests below look for the pattern by its value)
 
 
 @pytest.fixture(scope="module")
@@ -37,10 +39,10 @@ def twin(tmp_path_factory):
     return dref.build_twin(tmp_path_factory.mktemp("mc_domain_twin"))
 
 
-def _raw(ctx, sc, domains, poses, nulls=(), short=0, packed=None, **over):
+def _raw(ctx, sc, domains, poses, nulls=(), short=0, packed=None, guard=GUARD, **over):
     """One call of the seam on a scene of tests/mc_ref.py, a list of domains (or packed = (domFirst, domXY) as they are) and poses, the
-    outputs preset to a sentinel and the work buffer, with GUARD bytes behind it, to 0xA5: (return code, outputs, the buffer after
-    the call as bytes)"""
+    outputs preset to a sentinel and the work buffer, with `guard` bytes behind it that must be the pattern after the call, to 0xA5:
+    (return code, outputs, the buffer after the call as bytes)"""
     import torch
     dev = ctx.device
     df, dxy = packed if packed is not None else dref.pack(domains)
@@ -59,7 +61,7 @@ def _raw(ctx, sc, domains, poses, nulls=(), short=0, packed=None, **over):
     a.update(over)
     need = int(ctx.lib.mht_mc_domain_work_bytes(N, len(sc["x"]), T, G, D, sc["K"], sc["S"]))
     assert need > 0 and need == dref.work_bytes(N, len(sc["x"]), T, G, D, sc["K"], sc["S"])
-    arrays["work"] = torch.full((need + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+    arrays["work"] = guarded_work(need, guard, dev)
     ptr = lambda k: None if k in nulls else host[k].ctypes.data if k in host else arrays[k].data_ptr()
     torch.cuda.synchronize(dev)
     rc = ctx.lib.mht_mc_domain_encounters(None if "ctx" in nulls else ctx.handle, a["nx"], a["transition"], a["nComp"], a["T"], a["G"], a["nDomain"], a["nVert"], a["K"],
@@ -67,6 +69,7 @@ def _raw(ctx, sc, domains, poses, nulls=(), short=0, packed=None, **over):
                                           ptr("domFirst"), ptr("domXY"), ptr("inside"), ptr("firstAt"), ptr("ever"), ptr("valid"), ptr("status"), ptr("work"),
                                           need - short)
     torch.cuda.synchronize(dev)
+    assert guard_untouched(arrays["work"], need), "the call wrote behind the work buffer the sizer asks for"
     return rc, {k: arrays[k].cpu().numpy().view(o[k].dtype) for k in dref.COUNTS}, arrays["work"].cpu().numpy()
 
 

@@ -9,6 +9,7 @@ import pytest
 
 import encounter_ref as eref
 import mc_ref as ref
+from test_encounter_gpu import guard_untouched, guarded_work
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +31,9 @@ def twin(tmp_path_factory):
     return ref.build_twin(tmp_path_factory.mktemp("mc_twin"))
 
 
-def _raw(ctx, sc, nulls=(), short=0, **over):
-    """One call of the seam on a scene of tests/mc_ref.py, the outputs preset to a sentinel: (return code, dict of the outputs)"""
+def _raw(ctx, sc, nulls=(), short=0, guard=0, **over):
+    """One call of the seam on a scene of tests/mc_ref.py, the outputs preset to a sentinel and the work buffer to a pattern: (return code,
+    dict of the outputs).  guard > 0: that many bytes of the pattern lie behind the sizer's figure and must be the pattern after the call."""
     import torch
     dev = ctx.device
     N, T, G = sc["x"].shape[1], len(sc["first"]) - 1, len(sc["own"])
@@ -47,13 +49,14 @@ def _raw(ctx, sc, nulls=(), short=0, **over):
     a.update(over)
     need = int(ctx.lib.mht_mc_work_bytes(N, len(sc["x"]), T, G, sc["K"], sc["S"]))
     assert need > 0
-    arrays["work"] = torch.empty(need, dtype=torch.uint8, device=dev)
+    arrays["work"] = guarded_work(need, guard, dev)
     ptr = lambda k: None if k in nulls else host[k].ctypes.data if k in host else arrays[k].data_ptr()
     torch.cuda.synchronize(dev)
     rc = ctx.lib.mht_mc_encounters(None if "ctx" in nulls else ctx.handle, a["nx"], a["transition"], a["nComp"], a["T"], a["G"], a["K"], a["S"], a["seed"], a["dt"], a["R"],
                                    ptr("Phi"), ptr("Q"), ptr("x"), ptr("P"), ptr("first"), ptr("cdf"), ptr("own"), ptr("within"), ptr("ever"), ptr("valid"),
                                    ptr("status"), ptr("work"), need - short)
     torch.cuda.synchronize(dev)
+    assert guard_untouched(arrays["work"], need), "the call wrote behind the work buffer the sizer asks for"
     out = {k: arrays[k].cpu().numpy().view(o[k].dtype) for k in ("within", "ever", "valid", "status")}
     return rc, out
 

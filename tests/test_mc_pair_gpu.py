@@ -10,6 +10,7 @@ import pytest
 import encounter_ref as eref
 import mc_pair_ref as pref
 import mc_ref as ref
+from test_encounter_gpu import guard_untouched, guarded_work
 from test_mc_gpu import _scans, _weights
 
 pytestmark = pytest.mark.gpu
@@ -32,8 +33,9 @@ def twin(tmp_path_factory):
     return pref.build_twin(tmp_path_factory.mktemp("mc_pair_twin"))
 
 
-def _raw(ctx, sc, pairs, nulls=(), short=0, **over):
-    """One call of the seam on a scene of tests/mc_ref.py and pairs [n, 2], the outputs preset to a sentinel: (return code, outputs)"""
+def _raw(ctx, sc, pairs, nulls=(), short=0, guard=0, **over):
+    """One call of the seam on a scene of tests/mc_ref.py and pairs [n, 2], the outputs preset to a sentinel and the work buffer to a pattern:
+    (return code, outputs).  guard > 0: that many bytes of the pattern lie behind the sizer's figure and must be the pattern after the call."""
     import torch
     dev = ctx.device
     pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
@@ -50,13 +52,14 @@ def _raw(ctx, sc, pairs, nulls=(), short=0, **over):
     a.update(over)
     need = int(ctx.lib.mht_mc_pair_work_bytes(N, len(sc["x"]), T, n, sc["K"], sc["S"]))
     assert need > 0 and need == pref.work_bytes(N, len(sc["x"]), T, n, sc["K"], sc["S"])
-    arrays["work"] = torch.empty(need, dtype=torch.uint8, device=dev)
+    arrays["work"] = guarded_work(need, guard, dev)
     ptr = lambda k: None if k in nulls else host[k].ctypes.data if k in host else arrays[k].data_ptr()
     torch.cuda.synchronize(dev)
     rc = ctx.lib.mht_mc_pair_encounters(None if "ctx" in nulls else ctx.handle, a["nx"], a["transition"], a["nComp"], a["T"], a["nPair"], a["K"], a["S"], a["seed"],
                                         a["dt"], a["R"], ptr("Phi"), ptr("Q"), ptr("x"), ptr("P"), ptr("first"), ptr("cdf"), ptr("pairs"), ptr("within"),
                                         ptr("firstAt"), ptr("ever"), ptr("valid"), ptr("status"), ptr("work"), need - short)
     torch.cuda.synchronize(dev)
+    assert guard_untouched(arrays["work"], need), "the call wrote behind the work buffer the sizer asks for"
     return rc, {k: arrays[k].cpu().numpy().view(o[k].dtype) for k in pref.COUNTS}
 
 

@@ -10,6 +10,7 @@ import pytest
 import encounter_ref as eref
 import mc_ref as ref
 import mc_zone_ref as zref
+from test_encounter_gpu import guard_untouched, guarded_work
 from test_mc_gpu import _scans, _weights
 
 pytestmark = pytest.mark.gpu
@@ -32,9 +33,10 @@ def twin(tmp_path_factory):
     return zref.build_twin(tmp_path_factory.mktemp("mc_zone_twin"))
 
 
-def _raw(ctx, sc, zones, nulls=(), short=0, packed=None, **over):
+def _raw(ctx, sc, zones, nulls=(), short=0, packed=None, guard=0, **over):
     """One call of the seam on a scene of tests/mc_ref.py and a list of zones (or packed = (zoneFirst, zoneXY) as they are), the outputs
-    preset to a sentinel: (return code, outputs)"""
+    preset to a sentinel and the work buffer to a pattern: (return code, outputs).  guard > 0: that many bytes of the pattern lie behind
+    the sizer's figure and must be the pattern after the call."""
     import torch
     dev = ctx.device
     zf, zxy = packed if packed is not None else zref.pack(zones)
@@ -52,13 +54,14 @@ def _raw(ctx, sc, zones, nulls=(), short=0, packed=None, **over):
     a.update(over)
     need = int(ctx.lib.mht_mc_zone_work_bytes(N, len(sc["x"]), T, Z, sc["K"], sc["S"]))
     assert need > 0 and need == zref.work_bytes(N, len(sc["x"]), T, Z, sc["K"], sc["S"])
-    arrays["work"] = torch.empty(need, dtype=torch.uint8, device=dev)
+    arrays["work"] = guarded_work(need, guard, dev)
     ptr = lambda k: None if k in nulls else host[k].ctypes.data if k in host else arrays[k].data_ptr()
     torch.cuda.synchronize(dev)
     rc = ctx.lib.mht_mc_zone_encounters(None if "ctx" in nulls else ctx.handle, a["nx"], a["transition"], a["nComp"], a["T"], a["nZone"], a["nVert"], a["K"], a["S"],
                                         a["seed"], a["dt"], ptr("Phi"), ptr("Q"), ptr("x"), ptr("P"), ptr("first"), ptr("cdf"), ptr("zoneFirst"), ptr("zoneXY"),
                                         ptr("inside"), ptr("firstAt"), ptr("ever"), ptr("valid"), ptr("status"), ptr("work"), need - short)
     torch.cuda.synchronize(dev)
+    assert guard_untouched(arrays["work"], need), "the call wrote behind the work buffer the sizer asks for"
     return rc, {k: arrays[k].cpu().numpy().view(o[k].dtype) for k in zref.COUNTS}
 
 
